@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark: batched 1-D c2c f32, N=2^20, batch=4096 per GPU (BASELINE.json config 3).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--no-graph] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--no-graph] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds the measurements that take runs of their own:
+the live copy ceiling (roofline.attainable), per-pass kernel times of two-pass routes and the CPU baselines.  --dump-outputs DIR
+writes what the last timed step computed to DIR/output.npy (float32, rank 0's shard; a seeded sample of rows when it exceeds 64 MB).
 
 One "step" = one pass of the hot path (plan.exec recorded once into a command list, replayed per step) over
 one batch of synthetic complex input already resident in HBM (device-side twin of the oracle's seeded PRNG,
@@ -214,6 +218,29 @@ def time_single_pass(mi355fft, dev, ev, opts, inp, out, which, reps):
     return ms * 1e3 / (reps * max(launches, 1)), launches
 
 
+DUMP_LIMIT_BYTES = 63 * 1000 * 1000   # below 64 MB with the .npy header
+DUMP_SEED = 0x5EED00D0
+
+
+def dump_outputs(mi355fft, dev, out, out_bytes, batch, dirpath):
+    """Writes the output buffer to dirpath/output.npy as float32 [units, floats per unit].  A unit is one transform's output row
+    (a slice of DUMP_LIMIT_BYTES / 4 when a row is larger); beyond DUMP_LIMIT_BYTES a seeded sample of units is kept, in ascending order."""
+    import numpy as np
+    unit = out_bytes // batch
+    if unit > DUMP_LIMIT_BYTES // 4:
+        unit = DUMP_LIMIT_BYTES // 4
+    count = out_bytes // unit
+    keep = min(count, DUMP_LIMIT_BYTES // unit)
+    picks = (list(range(count)) if keep == count
+             else sorted(int(i) for i in np.random.default_rng(DUMP_SEED).choice(count, keep, replace=False)))
+    data = np.stack([mi355fft.downloadF32(dev, out, unit // 4, p * unit) for p in picks])
+    os.makedirs(dirpath, exist_ok=True)
+    np.save(os.path.join(dirpath, "output.npy"), data)
+    return {"dir": dirpath, "file": "output.npy", "dtype": "float32", "shape": list(data.shape), "unit_bytes": unit,
+            "units_total": count,
+            "sample": "all" if keep == count else f"sorted(numpy.random.default_rng({DUMP_SEED:#x}).choice(units_total, {keep}, replace=False))"}
+
+
 def launch_ranks(n):
     """parent side of `bench.py --gpus N`: torch.distributed.run with one rank per GPU on this node, as a child process"""
     with socket.socket() as sk:
@@ -249,8 +276,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default=os.environ.get("MI355FFT_BENCH_WORKLOAD", "c2c_2p20_b4096"))
     ap.add_argument("--no-graph", action="store_true", help="replay the op list instead of a hipGraph")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--full", action="store_true", help="also measure the copy ceiling, per-pass kernel times and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/output.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     gpus_given = any(a == "--gpus" or a.startswith("--gpus=") for a in sys.argv[1:])
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -415,8 +446,11 @@ def main():
     # MAX over ranks of the wall time around the K steps (and of the device-event time)
     wall_max, dev_max = group.reduce_max([wall, dev_ms / 1e3])
 
+    # before anything under --full: the copy ceiling and the single-pass plans write into `out`
+    dumped = dump_outputs(mi355fft, dev, out, out_bytes, batch, args.dump_outputs) if (rank == 0 and args.dump_outputs) else None
+
     per_kernel = None
-    if rank == 0 and typ == "c2c" and "two-pass" in route:
+    if args.full and rank == 0 and typ == "c2c" and "two-pass" in route:
         # per-kernel averages, measured live with hipEvents on the library's stream (must agree with the rocprofv3
         # kernel-trace summary committed under profiles/).  Pass B alone reads whatever pass A left in the workspace.
         ua, la = time_single_pass(mi355fft, dev, ev, opts, inp, out, 1, 3)
@@ -473,37 +507,40 @@ def main():
             line["roofline"]["note"] = ("one " + kname + " launch per step carries the whole batch (column FFTs -> per-XCD workspace slot -> "
                                         "XCD barrier -> four-step roots + row FFTs); the only other launch of a step is the 8 KiB zero_kernel "
                                         "that resets its control block (<3 us), so the step's device time is that kernel's launch duration")
-        try:
-            ceil_gbs, ceil_bytes = fabric_ceiling(dev, ev, inp, out, min(in_bytes, out_bytes))
-            moved = (traffic / (float(n) * batch)) if traffic else None          # bytes per point through the fabric (PMC passes)
-            line["roofline"]["attainable"] = {
-                "fabric_ceiling_GBps": ceil_gbs, "fabric_ceiling_source": f"copyBufferToBuffer of {ceil_bytes >> 20} MiB timed in this run (read + write bytes / device time)",
-                "bytes_per_point_moved": moved,
-                "moved_GBps": (moved * float(n) * batch / step_dev_s / 1e9) if moved else None,
-                "frac_of_attainable": (moved * float(n) * batch / step_dev_s / 1e9 / ceil_gbs) if moved else None,
-                "ceiling_for_this_traffic_frac_of_peak": (bytes_per_point / moved * ceil_gbs / HBM_PEAK_GBS) if moved else None,
-                "note": "frac (of the 8 TB/s roofline, algorithmic bytes) is the figure of merit; this block says how much of the gap is the chip's copy ceiling "
-                        "and how much is traffic beyond the algorithmic bytes (the four-step intermediate crosses the fabric once in each direction)"}
-        except Exception as e:   # never lose the line over the side measurement
-            line["roofline"]["attainable"] = {"error": str(e)}
-        if per_kernel:
-            line["roofline"]["per_kernel"] = per_kernel
-            line["roofline"]["note"] = ("a launch in the roofline sense is the pass A + pass B pair that moves each point in and out once: "
-                                        "algorithmic 16 B/point over the pair; each pass alone moves 16 B/point through the fabric")
-        if world > 1:
-            line["cpu_baseline"] = None
-            line["cpu_baseline_note"] = "reported at N=1 only (rank 0 of a single-GPU run): see the n_gpus=1 line"
-        elif not args.no_cpu_baseline:
-            # the baseline the north_star names: the reference's Node.js CPU correctness path on the host cores; the C/pthreads
-            # port of the same algorithm is kept beside it.  Reported numbers, never a reason to lose the GPU line.
+        if dumped:
+            line["outputs"] = dumped
+        if args.full:
             try:
-                line["cpu_baseline"] = cpu_baseline_node(n)
-            except Exception as e:
-                line["cpu_baseline"] = {"value": None, "unit": "GPoints/s", "cores": 0, "kind": "node", "sample": f"failed: {e}"}
-            try:
-                line["cpu_baseline_port"] = cpu_baseline(n, seconds_target=6.0)
-            except Exception as e:
-                line["cpu_baseline_port"] = {"value": None, "unit": "GPoints/s", "cores": 0, "kind": "port", "sample": f"failed: {e}"}
+                ceil_gbs, ceil_bytes = fabric_ceiling(dev, ev, inp, out, min(in_bytes, out_bytes))
+                moved = (traffic / (float(n) * batch)) if traffic else None          # bytes per point through the fabric (PMC passes)
+                line["roofline"]["attainable"] = {
+                    "fabric_ceiling_GBps": ceil_gbs, "fabric_ceiling_source": f"copyBufferToBuffer of {ceil_bytes >> 20} MiB timed in this run (read + write bytes / device time)",
+                    "bytes_per_point_moved": moved,
+                    "moved_GBps": (moved * float(n) * batch / step_dev_s / 1e9) if moved else None,
+                    "frac_of_attainable": (moved * float(n) * batch / step_dev_s / 1e9 / ceil_gbs) if moved else None,
+                    "ceiling_for_this_traffic_frac_of_peak": (bytes_per_point / moved * ceil_gbs / HBM_PEAK_GBS) if moved else None,
+                    "note": "frac (of the 8 TB/s roofline, algorithmic bytes) is the figure of merit; this block says how much of the gap is the chip's copy ceiling "
+                            "and how much is traffic beyond the algorithmic bytes (the four-step intermediate crosses the fabric once in each direction)"}
+            except Exception as e:   # never lose the line over the side measurement
+                line["roofline"]["attainable"] = {"error": str(e)}
+            if per_kernel:
+                line["roofline"]["per_kernel"] = per_kernel
+                line["roofline"]["note"] = ("a launch in the roofline sense is the pass A + pass B pair that moves each point in and out once: "
+                                            "algorithmic 16 B/point over the pair; each pass alone moves 16 B/point through the fabric")
+            if world > 1:
+                line["cpu_baseline"] = None
+                line["cpu_baseline_note"] = "reported at N=1 only (rank 0 of a single-GPU run): see the n_gpus=1 line"
+            elif not args.no_cpu_baseline:
+                # the baseline the north_star names: the reference's Node.js CPU correctness path on the host cores; the C/pthreads
+                # port of the same algorithm is kept beside it.  Reported numbers, never a reason to lose the GPU line.
+                try:
+                    line["cpu_baseline"] = cpu_baseline_node(n)
+                except Exception as e:
+                    line["cpu_baseline"] = {"value": None, "unit": "GPoints/s", "cores": 0, "kind": "node", "sample": f"failed: {e}"}
+                try:
+                    line["cpu_baseline_port"] = cpu_baseline(n, seconds_target=6.0)
+                except Exception as e:
+                    line["cpu_baseline_port"] = {"value": None, "unit": "GPoints/s", "cores": 0, "kind": "port", "sample": f"failed: {e}"}
         print(json.dumps(line), flush=True)
 
     cmds.release()

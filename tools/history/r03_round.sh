@@ -3,7 +3,7 @@ cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
 tools/gpu_steps.sh \
   "copy_test|200|python3 -m pytest tests/test_gpu_parity.py -x -q -k 'copy_buffer'" \
-  "headline_full|400|python3 bench.py" \
+  "headline_full|400|python3 bench.py --full" \
   "cfg5_line|200|python3 bench.py --workload r2c_2p22_b1024 --no-cpu-baseline" > gpurun_out/r03_round_steps.log 2>&1
 grep -E "^=== .*exit" gpurun_out/r03_round_steps.log
 tail -2 gpurun_out/copy_test.log
