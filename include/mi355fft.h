@@ -113,8 +113,14 @@ typedef struct mi355fft_plan_desc {
   /* c2c only: createFftPlan({axes}) (plan.js:1307,1335-1339) — bit a set => axis a is transformed; 0 => all axes.  The
    * normalisation factor still uses prod(shape) over ALL axes, as the reference's does (plan.js:1334,1382). */
   uint32_t axes_mask;
-  uint32_t reserved2;
+  /* opts.precision (docs/API.md:50): MI355FFT_PRECISION_F32 (0, what every earlier caller passes) or
+   * MI355FFT_PRECISION_F16_STORAGE (1; c2c, r2c, c2r, dct*, dst*).  f16-storage: both sides of the plan hold IEEE binary16 —
+   * a complex element is (re, im) as two binary16 (4 bytes), a real element one binary16 (2 bytes); real sides cover
+   * count * 2 bytes rounded up to a multiple of 4.  Arithmetic runs in f32 and each output is rounded to nearest even once.
+   * Exec offsets of f16-storage plans are multiples of 4.  Custom strides and fftconv take f32 only. */
+  uint32_t precision;
 } mi355fft_plan_desc;
+enum { MI355FFT_PRECISION_F32 = 0, MI355FFT_PRECISION_F16_STORAGE = 1 };
 
 /* plan.exec(commandEncoder, {input, output?, temp?, inputOffsetBytes, outputOffsetBytes, kernel?})
  * (runtime/plans/c2c.js:3607-3612, runtime/plans/fftconv.js:1415-1429) */
@@ -125,7 +131,7 @@ typedef struct mi355fft_exec_args {
   mi355fft_buffer* output;         /* NULL => in place (c2c, in_place plans only) */
   mi355fft_buffer* temp;           /* optional caller workspace; NULL => plan-owned arena */
   mi355fft_buffer* kernel;         /* fftconv: kernel_count packed kernels of prod(kernel_shape) complex */
-  uint64_t input_offset_bytes;     /* multiples of 8 (plan.js:861-862) */
+  uint64_t input_offset_bytes;     /* multiples of 8 (plan.js:861-862); of 4 for f16-storage plans */
   uint64_t output_offset_bytes;
   uint64_t kernel_offset_bytes;
 } mi355fft_exec_args;

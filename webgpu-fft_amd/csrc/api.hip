@@ -363,7 +363,10 @@ MI_API int mi355fft_plan_exec(mi355fft_plan* plan, mi355fft_encoder* enc, const 
   if (!d.in_place && !args->output) return fail(MI355FFT_ERR_INVALID, "exec requires output when inPlace=false");
   if (d.in_place && args->output && (args->output != args->input || args->output_offset_bytes != args->input_offset_bytes))
     return fail(MI355FFT_ERR_INVALID, "inPlace=true requires output omitted or equal to input");
-  if (args->input_offset_bytes % 8 || args->output_offset_bytes % 8 || args->kernel_offset_bytes % 8)
+  if (d.precision == MI355FFT_PRECISION_F16_STORAGE) {   // binary16 elements: 4-byte complex, 2-byte real sides rounded up to 4 bytes
+    if (args->input_offset_bytes % 4 || args->output_offset_bytes % 4)
+      return fail(MI355FFT_ERR_INVALID, "inputOffsetBytes/outputOffsetBytes must be multiples of 4 for precision \"f16-storage\"");
+  } else if (args->input_offset_bytes % 8 || args->output_offset_bytes % 8 || args->kernel_offset_bytes % 8)
     return fail(MI355FFT_ERR_INVALID, "inputOffsetBytes/outputOffsetBytes must be multiples of 8");
   if (d.type == MI355FFT_FFTCONV && !args->kernel) return fail(MI355FFT_ERR_INVALID, "fftconv exec requires kernel");
   mi355fft_buffer* out = d.in_place ? args->input : args->output;

@@ -9,6 +9,7 @@
 //   void copy(void* dst, const void* src, size_t bytes);
 #pragma once
 #include <utility>
+#include "kern_f16.hpp"
 #include "kern_fftconv.hpp"
 #include "kern_generic.hpp"
 #include "kern_lines.hpp"
@@ -46,6 +47,7 @@ bool launch_lines_family(int id, const LineArgs& a, unsigned grid, L& l) {
       if constexpr (!(IC) && !(OC) && !(SI) && !(SO) && (TW) == 0 && C::NSTAGES >= 2) {   \
         if (a.real_mode == 1) {                                                          \
           if (a.mapped) l.launch(fft_lines_r2c_kernel<C, false, true>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a); \
+          else if (a.h16) l.launch(fft_lines_r2c_kernel<C, false, false, true>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a); \
           else l.launch(fft_lines_r2c_kernel<C>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a); \
           return true;                                                                   \
         }                                                                                \
@@ -61,7 +63,8 @@ bool launch_lines_family(int id, const LineArgs& a, unsigned grid, L& l) {
       }                                                                                  \
       if constexpr (!(IC) && !(OC) && (SI) && (SO) && (TW) == 0) {                        \
         if (a.real_mode == 2 && !a.mapped) {                                             \
-          l.launch(fft_lines_c2r_kernel<C>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a); \
+          if (a.h16) l.launch(fft_lines_c2r_kernel<C, false, false, true>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a); \
+          else l.launch(fft_lines_c2r_kernel<C>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a); \
           return true;                                                                   \
         }                                                                                \
         if constexpr (C::NSTAGES >= 2) {                                                 \
@@ -83,6 +86,13 @@ bool launch_lines_family(int id, const LineArgs& a, unsigned grid, L& l) {
         }                                                                                \
       }                                                                                  \
       if (a.mapped) return false;                                                        \
+      if (a.h16) {   /* f16-storage: the dense ROW instances only (plan.cpp wrap_f16_storage) */ \
+        if constexpr (!(IC) && !(OC) && (SI) == (SO) && (TW) == 0) {                     \
+          l.launch(fft_lines_kernel<C, true>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a); \
+          return true;                                                                   \
+        }                                                                                \
+        return false;                                                                    \
+      }                                                                                  \
       l.launch(fft_lines_kernel<C>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a); \
       return true;                                                                       \
       }                                                                                  \
@@ -424,6 +434,7 @@ bool dispatch_step(const Step& s, void* const ptr[5], L& l, LinesFn&& lines_fn, 
       a.fs_shift = (int)s.i[6]; a.fs_lo_mask = (unsigned)s.i[7]; a.fs_group = s.i[8] ? s.i[8] : 1; a.real_mode = (int)s.i[9];
       a.mapped = (int)s.i[10];
       if (a.mapped) { a.imap = s.imap; a.omap = s.omap; }
+      a.h16 = (int)s.i[11];
       a.scale = s.f[0];
       const LineKernelMeta& m = line_kernel_registry()[(size_t)s.variant];
       return lines_fn(family_of_line_kernel(m), s.variant, a, s.grid);
@@ -545,6 +556,12 @@ bool dispatch_step(const Step& s, void* const ptr[5], L& l, LinesFn&& lines_fn, 
       return true;
     case ST_COPY:
       if (ptr[0] != ptr[1]) l.copy(ptr[1], ptr[0], (size_t)s.i[0]);
+      return true;
+    case ST_F16_TO_F32:
+      l.launch(f16_to_f32_kernel, s.grid, 256u, 0u, (const _Float16*)ptr[0], (float*)ptr[1], (long long)s.i[0]);
+      return true;
+    case ST_F32_TO_F16:
+      l.launch(f32_to_f16_kernel, s.grid, 256u, 0u, (const float*)ptr[0], (_Float16*)ptr[1], (long long)s.i[0]);
       return true;
   }
   return false;

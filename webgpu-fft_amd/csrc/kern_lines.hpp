@@ -49,6 +49,28 @@ template <bool NT = false> MI_DEV void st_stream(cf* p, cf v) {
   else *p = v;
 }
 
+// f16-storage instances (H16 template parameter, plan.cpp wrap_f16_storage): the global sides hold a complex element as two
+// binary16 (re, im), 4 bytes; LDS and all arithmetic stay f32.  Loads widen exactly, stores round to nearest even.
+typedef _Float16 h2v __attribute__((ext_vector_type(2)));
+typedef _Float16 h4w __attribute__((ext_vector_type(4), aligned(4)));   // two adjacent complex elements
+template <bool H16> struct GlobalElem { typedef cf T; };
+template <> struct GlobalElem<true> { typedef h2v T; };
+template <bool NT = false> MI_DEV h2v ld_stream(const h2v* p) {
+  if constexpr (NT || MI355_NT_GLOBAL) return __builtin_nontemporal_load(p);
+  else return *p;
+}
+template <bool NT = false> MI_DEV void st_stream(h2v* p, h2v v) {
+  if constexpr (NT || MI355_NT_GLOBAL) __builtin_nontemporal_store(v, p);
+  else *p = v;
+}
+MI_DEV cf widen(cf v) { return v; }
+MI_DEV cf widen(h2v v) { cf r; r.x = (float)v.x; r.y = (float)v.y; return r; }
+template <bool H16> MI_DEV typename GlobalElem<H16>::T narrow(cf v) {
+  if constexpr (H16) { h2v r; r.x = (_Float16)v.x; r.y = (_Float16)v.y; return r; }
+  else return v;
+}
+MI_DEV h4w narrow2(cf a, cf b) { h4w r; r.x = (_Float16)a.x; r.y = (_Float16)a.y; r.z = (_Float16)b.x; r.w = (_Float16)b.y; return r; }
+
 // four-step twiddle e^{-2 pi i (line index in its group) * (element index) / Ntot}:
 //   TWID_FOURSTEP_OUT  multiplied into the last stage's outputs (LO table staged in LDS, HI from global)
 //   TWID_FOURSTEP_IN   multiplied into the first stage's inputs from per-thread registers that are computed
@@ -82,6 +104,7 @@ struct LineArgs {
   int v_in_lo, v_in_hi, v_out_lo, v_out_hi, v_zlo, v_zhi;   // VIEW instantiations of stage_read / stage_compute_write (kern_xcd.hpp fused kernels): rank-1 ranges of a four-step line
   int mapped;            // fft_lines_mapped_kernel: both sides go through imap / omap (in / out are the buffers' bases)
   SideMap imap, omap;
+  int h16;               // f16-storage: in / out hold binary16 elements (the H16 instances of the dense ROW kernels)
 };
 
 #ifndef MI355_NT_MAX_N
@@ -195,20 +218,21 @@ MI_DEV void fourstep_in_roots(cf (&fsw)[C::E], const LineArgs& a, long long tile
 
 // VIEW (column-mapped first stage of a fused four-step kernel): element idx * in_S + (column of the line) of the transform is read inside
 // [v_in_lo, v_in_hi) and is 0 elsewhere (rank-1 ioView.input / zeroPad.read)
-template <class C, int S, bool NT = false, bool VIEW = false>
+template <class C, int S, bool NT = false, bool VIEW = false, bool H16 = false>
 MI_DEV void stage_read(cf (&v)[C::E], const LineArgs& a, long long tile, int t, const cf* lds) {
   using I = StageInfo<C, S>;
+  using EL = typename GlobalElem<H16>::T;
   int line, u; thread_map<C, S>(t, line, u);
   if constexpr (I::FIRST) {
     const long long G0 = tile * C::T;
-    const cf* p;
+    const EL* p;
     long long live_lines;
     if constexpr (C::TWID == COL_RAGGED) {
       const long long o = tile / a.fs_group, j0 = (tile - o * a.fs_group) * C::T;   // group, first line of the tile inside it
-      p = a.in + o * a.in_outer_stride + j0;
+      p = reinterpret_cast<const EL*>(a.in) + o * a.in_outer_stride + j0;
       live_lines = a.in_S - j0;
     } else {
-      p = a.in + tile_base<C::IN_COL>(G0, a.in_S, a.in_outer_stride);
+      p = reinterpret_cast<const EL*>(a.in) + tile_base<C::IN_COL>(G0, a.in_S, a.in_outer_stride);
       // padding lines of the last tile re-read its last live line (loads stay in bounds, stores are masked)
       live_lines = a.num_lines - G0;
     }
@@ -220,15 +244,15 @@ MI_DEV void stage_read(cf (&v)[C::E], const LineArgs& a, long long tile, int t, 
     for (int b = 0; b < I::NB; ++b) {
 #pragma unroll
       for (int q = 0; q < I::R; ++q) {
-        const cf* pq = p + (unsigned)(b * C::TPL + q * (C::N / I::R)) * es;   // uniform
+        const EL* pq = p + (unsigned)(b * C::TPL + q * (C::N / I::R)) * es;   // uniform
         if constexpr (VIEW) {
           static_assert(C::IN_COL, "views ride the column-mapped pass A");
           const int i = (int)((unsigned)(u + b * C::TPL + q * (C::N / I::R)) * es + (unsigned)(G0 % a.in_S) + (unsigned)line);
           cf xv = {0.0f, 0.0f};
-          if (i >= a.v_in_lo && i < a.v_in_hi) xv = pq[voff];
+          if (i >= a.v_in_lo && i < a.v_in_hi) xv = widen(pq[voff]);
           v[b * I::R + q] = cswap_if<C::SWAP_IN>(xv);
         } else
-        v[b * I::R + q] = cswap_if<C::SWAP_IN>(ld_stream<NT>(pq + voff));
+        v[b * I::R + q] = cswap_if<C::SWAP_IN>(widen(ld_stream<NT>(pq + voff)));
       }
     }
   } else {
@@ -245,22 +269,23 @@ MI_DEV void stage_read(cf (&v)[C::E], const LineArgs& a, long long tile, int t, 
 // global memory — for kernels that post-process a whole line before it leaves the workgroup (kern_xcd_real.hpp)
 // MUL: the finished outputs are multiplied by the spectrum a.tw_lo[k] (conjugated when a.fs_shift != 0) on their way out — the
 // pointwise product of fftconv folded into the last stage's register store (fft_lines_mul_kernel)
-template <class C, int S, bool NT = false, bool KEEP_IN_LDS = false, bool MUL = false, bool VIEW = false>
+template <class C, int S, bool NT = false, bool KEEP_IN_LDS = false, bool MUL = false, bool VIEW = false, bool H16 = false>
 MI_DEV void stage_compute_write(cf (&v)[C::E], const LineArgs& a, long long tile, int t, cf* lds, const cf* tw_lds, const cf* lo_lds) {
   using I = StageInfo<C, S>;
+  using EL = typename GlobalElem<H16>::T;
   constexpr bool TO_GLOBAL = I::LAST && !KEEP_IN_LDS;
   int line, u; thread_map<C, S>(t, line, u);
-  cf* po = nullptr;
+  EL* po = nullptr;
   unsigned ls = 1, es = 1, gi = 0;
   bool live = true;
   if constexpr (TO_GLOBAL) {
     const long long G0 = tile * C::T;
     if constexpr (C::TWID == COL_RAGGED) {
       const long long o = tile / a.fs_group, j0 = (tile - o * a.fs_group) * C::T;
-      po = a.out + o * a.out_outer_stride + j0;
+      po = reinterpret_cast<EL*>(a.out) + o * a.out_outer_stride + j0;
       live = (long long)line < a.out_S - j0;
     } else {
-      po = a.out + tile_base<C::OUT_COL>(G0, a.out_S, a.out_outer_stride);
+      po = reinterpret_cast<EL*>(a.out) + tile_base<C::OUT_COL>(G0, a.out_S, a.out_outer_stride);
       live = (long long)line < a.num_lines - G0;
     }
     ls = C::OUT_COL ? 1u : (unsigned)a.out_outer_stride;
@@ -298,15 +323,15 @@ MI_DEV void stage_compute_write(cf (&v)[C::E], const LineArgs& a, long long tile
         if constexpr (MUL) r = cmul(r, lo_lds[b * I::R + q]);   // this thread's slice of the spectrum, held in registers by the caller
         if (a.scale != 1.0f) r = r * a.scale;
         // last stage: Ns_prev = N/R, so oidx = j + q*(N/R): the q term is uniform
-        cf* pq = po + (unsigned)(b * C::TPL + q * I::NSP) * es;
+        EL* pq = po + (unsigned)(b * C::TPL + q * I::NSP) * es;
         const unsigned voff = (unsigned)line * ls + (unsigned)u * es;
         if constexpr (VIEW) {   // transposed store of pass B: element k = oidx * out_S + (row of the line): inside [v_out_lo, v_out_hi) only, 0 outside [v_zlo, v_zhi)
           static_assert(C::OUT_COL, "views ride the transposed store of pass B");
           const int kk = (int)((unsigned)oidx * es + (unsigned)((tile * C::T) % a.out_S) + (unsigned)line);
           if (kk < a.v_zlo || kk >= a.v_zhi) r = cf{0.0f, 0.0f};
-          if (live && kk >= a.v_out_lo && kk < a.v_out_hi) pq[voff] = cswap_if<C::SWAP_OUT>(r);
+          if (live && kk >= a.v_out_lo && kk < a.v_out_hi) pq[voff] = narrow<H16>(cswap_if<C::SWAP_OUT>(r));
         } else
-        if (live) st_stream<NT>(pq + voff, cswap_if<C::SWAP_OUT>(r));
+        if (live) st_stream<NT>(pq + voff, narrow<H16>(cswap_if<C::SWAP_OUT>(r)));
       } else {
         lds[lds_index<C>(line, oidx)] = w[q];
       }
@@ -314,7 +339,8 @@ MI_DEV void stage_compute_write(cf (&v)[C::E], const LineArgs& a, long long tile
   }
 }
 
-template <class C>
+// H16: both sides binary16 (f16-storage plans whose whole route is this one dense launch)
+template <class C, bool H16 = false>
 __global__ void __launch_bounds__(C::THREADS) fft_lines_kernel(const LineArgs a) {
   MI_SMEM_DECL(smem);
   cf* lds = reinterpret_cast<cf*>(smem);
@@ -332,15 +358,15 @@ __global__ void __launch_bounds__(C::THREADS) fft_lines_kernel(const LineArgs a)
     __syncthreads();
     cf v[C::E], vn[C::E];
     long long tile = blockIdx.x;
-    if (tile < a.num_tiles) stage_read<C, 0, C::STREAM_NT>(v, a, tile, t, lds);
+    if (tile < a.num_tiles) stage_read<C, 0, C::STREAM_NT, false, H16>(v, a, tile, t, lds);
     for (; tile < a.num_tiles; tile += gridDim.x) {
       const long long next = tile + gridDim.x;
-      if (next < a.num_tiles) stage_read<C, 0, C::STREAM_NT>(vn, a, next, t, lds);      // in flight while this tile is computed and stored
+      if (next < a.num_tiles) stage_read<C, 0, C::STREAM_NT, false, H16>(vn, a, next, t, lds);      // in flight while this tile is computed and stored
       stage_compute_write<C, 0>(v, a, tile, t, lds, tw_lds, lo_lds);
       lines_sync<C>();
       stage_read<C, 1>(v, a, tile, t, lds);
       lines_sync<C>();
-      stage_compute_write<C, 1, C::STREAM_NT>(v, a, tile, t, lds, tw_lds, lo_lds);
+      stage_compute_write<C, 1, C::STREAM_NT, false, false, false, H16>(v, a, tile, t, lds, tw_lds, lo_lds);
 #pragma unroll
       for (int e = 0; e < C::E; ++e) v[e] = vn[e];
     }
@@ -364,24 +390,24 @@ __global__ void __launch_bounds__(C::THREADS) fft_lines_kernel(const LineArgs a)
   constexpr bool SNT = C::STREAM_NT;
   for (long long tile = blockIdx.x; tile < a.num_tiles; tile += gridDim.x) {
     cf v[C::E];
-    stage_read<C, 0, SNT>(v, a, tile, t, lds);
+    stage_read<C, 0, SNT, false, H16>(v, a, tile, t, lds);
     if constexpr (C::TWID == TWID_FOURSTEP_IN) {
       if (!fs_hoist) fourstep_in_roots<C>(fsw, a, tile, t);
 #pragma unroll
       for (int e = 0; e < C::E; ++e) v[e] = cmul(v[e], fsw[e]);
     }
-    stage_compute_write<C, 0, SNT>(v, a, tile, t, lds, tw_lds, lo_lds);     // (NT only matters where a stage stores to memory)
+    stage_compute_write<C, 0, SNT, false, false, false, H16>(v, a, tile, t, lds, tw_lds, lo_lds);     // (NT only matters where a stage stores to memory)
     if constexpr (C::NSTAGES >= 2) {
       lines_sync<C>();
       stage_read<C, 1>(v, a, tile, t, lds);
       lines_sync<C>();
-      stage_compute_write<C, 1, SNT>(v, a, tile, t, lds, tw_lds, lo_lds);
+      stage_compute_write<C, 1, SNT, false, false, false, H16>(v, a, tile, t, lds, tw_lds, lo_lds);
     }
     if constexpr (C::NSTAGES == 3) {
       lines_sync<C>();
       stage_read<C, 2>(v, a, tile, t, lds);
       lines_sync<C>();
-      stage_compute_write<C, 2, SNT>(v, a, tile, t, lds, tw_lds, lo_lds);
+      stage_compute_write<C, 2, SNT, false, false, false, H16>(v, a, tile, t, lds, tw_lds, lo_lds);
     }
   }
 }
@@ -523,10 +549,12 @@ __global__ void __launch_bounds__(C::THREADS) fft_lines_mapped_kernel(const Line
 #ifndef MI355_R2C_POST_BATCH
 #define MI355_R2C_POST_BATCH 1
 #endif
-template <class C, bool TRIG = false, bool MAPPED = false>
+// H16 (dense lines only): the real line holds binary16 (read as binary16 pairs), the packed bins leave as binary16 pairs
+template <class C, bool TRIG = false, bool MAPPED = false, bool H16 = false>
 __global__ void __launch_bounds__(C::THREADS, C::THREADS == 256 && C::T == 1 && !MAPPED ? 2 : 1) fft_lines_r2c_kernel(const LineArgs a) {   // (N = 2^14: two workgroups per CU, see fft_lines_c2r_kernel)
   static_assert(!C::IN_COL && !C::OUT_COL && !C::SWAP_IN && !C::SWAP_OUT && C::TWID == TWID_NONE && C::NSTAGES >= 2, "forward ROW configuration with an LDS line buffer");
   static_assert(!(TRIG && MAPPED), "the fused DCT-II takes dense lines");
+  static_assert(!H16 || (!TRIG && !MAPPED), "binary16 sides on the dense r2c lines only");
   MI_SMEM_DECL(smem);
   cf* lds = reinterpret_cast<cf*>(smem);
   cf* tw_lds = lds + C::DATA_ELEMS;
@@ -587,7 +615,7 @@ __global__ void __launch_bounds__(C::THREADS, C::THREADS == 256 && C::T == 1 && 
         }
       }
     } else {
-      stage_read<C, 0>(v, a, tile, t, lds);
+      stage_read<C, 0, false, false, H16>(v, a, tile, t, lds);
     }
     stage_compute_write<C, 0>(v, a, tile, t, lds, tw_lds, nullptr);
     __syncthreads();
@@ -607,7 +635,7 @@ __global__ void __launch_bounds__(C::THREADS, C::THREADS == 256 && C::T == 1 && 
     [[maybe_unused]] long long obase = 0;
     [[maybe_unused]] bool ozero = false, oline = false;
     if constexpr (MAPPED) oline = side_line(a.omap, G0 + t / C::TPL, a.num_lines, obase, ozero);
-    if constexpr (!TRIG && !MAPPED && MI355_R2C_POST_VEC && MI355_R2C_POST_ROOTS && H >= MI355_R2C_POST_ROOTS_H && H <= MI355_R2C_POST_ROOTS_HMAX && 1024 % (2 * C::TPL) == 0 && (H / 4) % C::TPL == 0) {
+    if constexpr (!TRIG && !MAPPED && !H16 && MI355_R2C_POST_VEC && MI355_R2C_POST_ROOTS && H >= MI355_R2C_POST_ROOTS_H && H <= MI355_R2C_POST_ROOTS_HMAX && 1024 % (2 * C::TPL) == 0 && (H / 4) % C::TPL == 0) {
       // r03: the form below with the loop's table loads taken out of it (as in the c2r twin's raw-copy head): lane ru of a line takes the
       // items j = ru + TPL i, i.e. bins k = 2 ru + 1 + 2 TPL i and k + 1; with the 1024-entry LO table that is 1024 / (2 TPL) LO roots per lane and
       // bin, and the HI root is the same for the whole line (k + 1 crosses into the next HI block on the line's last lane only).
@@ -672,19 +700,31 @@ __global__ void __launch_bounds__(C::THREADS, C::THREADS == 256 && C::T == 1 && 
       for (int p = t; p < live * PERV; p += C::THREADS) {
         const int line = p / PERV, j = p - line * PERV;
         cf* x = a.out + (G0 + line) * a.out_outer_stride;
+        [[maybe_unused]] h2v* xh = reinterpret_cast<h2v*>(a.out) + (G0 + line) * a.out_outer_stride;
         if (j == QP) {
           const cf z0 = lds[lds_index<C>(line, 0)];
+          if constexpr (H16) {
+            xh[0] = narrow<true>(cf{(z0.x + z0.y) * a.scale, 0.0f});
+            xh[H] = narrow<true>(cf{(z0.x - z0.y) * a.scale, 0.0f});
+          } else {
           x[0] = cf{(z0.x + z0.y) * a.scale, 0.0f};
           x[H] = cf{(z0.x - z0.y) * a.scale, 0.0f};
+          }
           continue;
         }
         const int k = 2 * j + 1;
         cf xk0, xm0, xk1, xm1;
         split(lds[lds_index<C>(line, k)], lds[lds_index<C>(line, H - k)], k, xk0, xm0);
         split(lds[lds_index<C>(line, k + 1)], lds[lds_index<C>(line, H - k - 1)], k + 1, xk1, xm1);
+        if constexpr (H16) {   // two bins: one 8-byte store (4-byte aligned: lines of H + 1 bins)
+          *reinterpret_cast<h4w*>(xh + k) = narrow2(xk0, xk1);
+          if (k + 1 == H / 2) xh[H - k] = narrow<true>(xm0);
+          else *reinterpret_cast<h4w*>(xh + (H - k - 1)) = narrow2(xm1, xm0);
+        } else {
         *reinterpret_cast<f4w*>(x + k) = f4w{xk0.x, xk0.y, xk1.x, xk1.y};
         if (k + 1 == H / 2) x[H - k] = xm0;                                   // X[H/2] is its own mirror: already stored
         else *reinterpret_cast<f4w*>(x + (H - k - 1)) = f4w{xm1.x, xm1.y, xm0.x, xm0.y};
+        }
       }
       __syncthreads();   // LDS is re-used by the next tile
       continue;
@@ -748,6 +788,11 @@ __global__ void __launch_bounds__(C::THREADS, C::THREADS == 256 && C::T == 1 && 
         put(k, xk);
         if (k == 0) put(H, xm);
         else if (km != k) put(km, xm);
+      } else if constexpr (H16) {
+        h2v* x = reinterpret_cast<h2v*>(a.out) + (G0 + line) * a.out_outer_stride;
+        x[k] = narrow<true>(xk);
+        if (k == 0) x[H] = narrow<true>(xm);
+        else if (km != k) x[km] = narrow<true>(xm);
       } else {
         cf* x = a.out + (G0 + line) * a.out_outer_stride;
         x[k] = xk;
@@ -879,9 +924,11 @@ __global__ void __launch_bounds__(C::THREADS) fft_lines_mul_kernel(const LineArg
 #ifndef MI355_LINES_C2R_MINW
 #define MI355_LINES_C2R_MINW 2
 #endif
-template <class C, bool TRIG = false, bool MAPPED = false>
+// H16 (dense lines only): the packed bins are binary16 pairs (widened as they are loaded), the real line leaves as binary16
+template <class C, bool TRIG = false, bool MAPPED = false, bool H16 = false>
 __global__ void __launch_bounds__(C::THREADS, C::THREADS == 256 && C::T == 1 ? MI355_LINES_C2R_MINW : 1) fft_lines_c2r_kernel(const LineArgs a) {
   static_assert(!C::IN_COL && !C::OUT_COL && C::SWAP_IN && C::SWAP_OUT && C::TWID == TWID_NONE, "inverse ROW configuration");
+  static_assert(!H16 || (!TRIG && !MAPPED), "binary16 sides on the dense c2r lines only");
   static_assert(!(TRIG || MAPPED) || C::NSTAGES >= 2, "the fused DCT-III and the mapped sides need the LDS line buffer");
   static_assert(!(TRIG && MAPPED), "the fused DCT-III takes dense lines");
   MI_SMEM_DECL(smem);
@@ -931,6 +978,7 @@ __global__ void __launch_bounds__(C::THREADS, C::THREADS == 256 && C::T == 1 ? M
           // runs at 263 (profiles/r03_c2r_raw_roots.log).
           cf* xl = lds + rl * C::PITCH;
           const cf* x = a.in + (G0 + (rl < live ? rl : live - 1)) * a.in_outer_stride;    // (a ragged last tile: the spare lines repeat the last one)
+          [[maybe_unused]] const h2v* x16 = reinterpret_cast<const h2v*>(a.in) + (G0 + (rl < live ? rl : live - 1)) * a.in_outer_stride;
           cf wl[RAW_WL], whs[RAW_NWH];       // (per tile: kept across the stages they would cost the stages their registers)
           const auto pre = [&](cf pk, cf m, int k, cf w) {
             if (k == 0) { pk.y = 0.0f; m.y = 0.0f; }
@@ -945,18 +993,30 @@ __global__ void __launch_bounds__(C::THREADS, C::THREADS == 256 && C::T == 1 ? M
             // N <= 8192: a lane loads BOTH bins of its pairs (k ascending, H - k descending: each a contiguous run across the lanes), all of
             // them and the roots up front, pre-splits in registers and writes Z[k], Z[H-k] into the slot: no pass over the slot, no barrier.
             // Same box (profiles/r03_c2r_direct.log): 2^12 576 -> 592, 2^13 555 -> 588; 2^14 498 -> 490, which keeps the in-slot pass
+            if constexpr (H16) {
+#pragma unroll
+              for (int i = 0; i < RAW_NK; ++i) { pks[i] = widen(x16[ru + i * C::TPL]); ms[i] = widen(x16[H - (ru + i * C::TPL)]); }
+              pmid = widen(x16[H / 2]);
+            } else {
 #pragma unroll
             for (int i = 0; i < RAW_NK; ++i) { pks[i] = x[ru + i * C::TPL]; ms[i] = x[H - (ru + i * C::TPL)]; }
             pmid = x[H / 2];
+            }
 #pragma unroll
             for (int c = 0; c < RAW_WL; ++c) wl[c] = a.tw_lo[ru + c * C::TPL];
 #pragma unroll
             for (int c = 0; c < RAW_NWH; ++c) whs[c] = a.tw_hi[c];
           } else {
-            cf raw[RAWN];
+            cf raw[RAWN], rawh;
+            if constexpr (H16) {
+#pragma unroll
+              for (int i = 0; i < RAWN; ++i) raw[i] = widen(x16[ru + i * C::TPL]);
+              rawh = widen(x16[H]);
+            } else {
 #pragma unroll
             for (int i = 0; i < RAWN; ++i) raw[i] = x[ru + i * C::TPL];
-            const cf rawh = x[H];
+            rawh = x[H];
+            }
 #pragma unroll
             for (int c = 0; c < RAW_WL; ++c) wl[c] = a.tw_lo[ru + c * C::TPL];
 #pragma unroll
@@ -1000,14 +1060,22 @@ __global__ void __launch_bounds__(C::THREADS, C::THREADS == 256 && C::T == 1 ? M
               if (p >= vend) break;
               const int l = p / PERV, j = p - l * PERV;
               const cf* x = a.in + (G0 + l) * a.in_outer_stride;
+              [[maybe_unused]] const h2v* x16 = reinterpret_cast<const h2v*>(a.in) + (G0 + l) * a.in_outer_stride;
               if (j == QP) {
-                const cf x0 = x[0], xh = x[H];
+                cf x0, xh;
+                if constexpr (H16) { x0 = widen(x16[0]); xh = widen(x16[H]); } else { x0 = x[0]; xh = x[H]; }
                 up[i] = f4w{x0.x, x0.y, xh.x, xh.y};
                 wh[i][0] = a.tw_hi[0]; wl[i][0] = a.tw_lo[0];
               } else {
                 const int k = 2 * j + 1;
+                if constexpr (H16) {   // two bins: one 8-byte load each way (4-byte aligned: lines of H + 1 bins)
+                  const h4w hu = *reinterpret_cast<const h4w*>(x16 + k), hd = *reinterpret_cast<const h4w*>(x16 + (H - k - 1));
+                  up[i] = f4w{(float)hu.x, (float)hu.y, (float)hu.z, (float)hu.w};
+                  dn[i] = f4w{(float)hd.x, (float)hd.y, (float)hd.z, (float)hd.w};
+                } else {
                 up[i] = *reinterpret_cast<const f4w*>(x + k);
                 dn[i] = *reinterpret_cast<const f4w*>(x + (H - k - 1));
+                }
 #pragma unroll
                 for (int c = 0; c < 2; ++c) { wh[i][c] = a.tw_hi[(unsigned)(k + c) >> a.fs_shift]; wl[i][c] = a.tw_lo[(unsigned)(k + c) & a.fs_lo_mask]; }
               }
@@ -1058,6 +1126,9 @@ __global__ void __launch_bounds__(C::THREADS, C::THREADS == 256 && C::T == 1 ? M
                 return r;
               };
               pk = bin(k); m = bin(H - k);
+            } else if constexpr (H16) {
+              const h2v* x = reinterpret_cast<const h2v*>(a.in) + (G0 + l) * a.in_outer_stride;
+              pk = widen(x[k]); m = widen(x[H - k]);
             } else {
               const cf* x = a.in + (G0 + l) * a.in_outer_stride;
               pk = x[k]; m = x[H - k];
@@ -1092,12 +1163,14 @@ __global__ void __launch_bounds__(C::THREADS, C::THREADS == 256 && C::T == 1 ? M
         __syncthreads();   // everyone has its inputs before stage 0 re-uses the buffer
       } else {
         const cf* x = a.in + (G0 + lclamp) * a.in_outer_stride;
+        [[maybe_unused]] const h2v* x16 = reinterpret_cast<const h2v*>(a.in) + (G0 + lclamp) * a.in_outer_stride;
 #pragma unroll
         for (int b = 0; b < I0::NB; ++b) {
 #pragma unroll
           for (int q = 0; q < I0::R; ++q) {
             const int k = u + b * C::TPL + q * (H / I0::R);
-            cf p = x[k], m = x[H - k];
+            cf p, m;
+            if constexpr (H16) { p = widen(x16[k]); m = widen(x16[H - k]); } else { p = x[k]; m = x[H - k]; }
             if (k == 0) { p.y = 0.0f; m.y = 0.0f; }
             const cf w = cmul(a.tw_hi[(unsigned)k >> a.fs_shift], a.tw_lo[(unsigned)k & a.fs_lo_mask]);
             const cf mc = {m.x, -m.y};
@@ -1108,18 +1181,18 @@ __global__ void __launch_bounds__(C::THREADS, C::THREADS == 256 && C::T == 1 ? M
         }
       }
     }
-    stage_compute_write<C, 0>(v, a, tile, t, lds, tw_lds, nullptr);
+    stage_compute_write<C, 0, false, false, false, false, H16>(v, a, tile, t, lds, tw_lds, nullptr);
     if constexpr (C::NSTAGES >= 2) {
       lines_sync<C>();
       stage_read<C, 1>(v, a, tile, t, lds);
       lines_sync<C>();
-      stage_compute_write<C, 1, false, (TRIG || MAPPED) && C::NSTAGES == 2>(v, a, tile, t, lds, tw_lds, nullptr);
+      stage_compute_write<C, 1, false, (TRIG || MAPPED) && C::NSTAGES == 2, false, false, H16>(v, a, tile, t, lds, tw_lds, nullptr);
     }
     if constexpr (C::NSTAGES == 3) {
       lines_sync<C>();
       stage_read<C, 2>(v, a, tile, t, lds);
       lines_sync<C>();
-      stage_compute_write<C, 2, false, TRIG || MAPPED>(v, a, tile, t, lds, tw_lds, nullptr);
+      stage_compute_write<C, 2, false, TRIG || MAPPED, false, false, H16>(v, a, tile, t, lds, tw_lds, nullptr);
     }
     if constexpr (MAPPED) {
       // the finished line sits in LDS as swapped pairs (x[2n+1], x[2n]); a thread stays on one line and walks it through omap

@@ -1145,6 +1145,9 @@ int validate_common(const mi355fft_plan_desc& d, std::string& err) {
   if (d.batch <= 0) { err = "batch must be positive int; got " + std::to_string(d.batch); return MI355FFT_ERR_INVALID; }
   if (d.normalize < 0 || d.normalize > 2) { err = "normalize must be one of \"none\", \"backward\", \"unitary\""; return MI355FFT_ERR_INVALID; }
   if (prodv(d.shape, d.rank) * d.batch > ((int64_t)1 << 40)) { err = "Unsupported: more than 2^40 points in one plan"; return MI355FFT_ERR_UNSUPPORTED; }
+  if (d.precision != MI355FFT_PRECISION_F32 && d.precision != MI355FFT_PRECISION_F16_STORAGE) {
+    err = "precision must be one of \"f32\", \"f16-storage\""; return MI355FFT_ERR_INVALID;
+  }
   for (const mi355fft_side_layout* l : {&d.input, &d.output})
     if (l->strided)
       for (int i = 0; i < d.rank; ++i)
@@ -1927,13 +1930,97 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
   return MI355FFT_OK;
 }
 
+// ---- precision "f16-storage" (reference src/kernels/f16_storage.js; runtime/plans/c2c.js:1036-1050, 3840-3861, 4163-4180) ----
+// The checks the reference makes before planning: custom strides (layout.strides, whdcn) and fftconv take f32 only.
+int validate_f16_storage(const mi355fft_plan_desc& d, std::string& err) {
+  if (d.type == MI355FFT_FFTCONV) { err = "fftconv supports precision:\"f32\" only in current implementation"; return MI355FFT_ERR_INVALID; }
+  if (d.input.strided || d.output.strided) {
+    if (d.type >= MI355FFT_DCT1) err = "custom strides for dct/dst currently support precision:\"f32\" only";
+    else err = std::string("custom strides currently support precision:\"f32\" only") + (d.type == MI355FFT_R2C ? " for r2c" : d.type == MI355FFT_C2R ? " for c2r" : "");
+    return MI355FFT_ERR_INVALID;
+  }
+  return MI355FFT_OK;
+}
+
+// The f32 plan is built as usual and then given binary16 sides.  Where that plan is one dense ROW line launch (c2c lines[N], r2c
+// lines-r2c[N], c2r lines-c2r[N]) the launch itself reads and writes binary16 (the H16 instances of kern_lines.hpp): 8 B per complex
+// point instead of 16, no staging.  Every other route runs unchanged on f32 staging regions behind the f32 plan's workspace:
+// binary16 -> f32 of the input in front, f32 -> binary16 of the output behind (and of the caller's output in front as well when
+// ioView.output keeps untouched elements, clearOutside: false).  Extents halve; real sides round up to 4 bytes.
+bool fuse_f16_storage(PlanIR& ir) {
+  if (ir.steps.size() != 1) return false;
+  Step& s = ir.steps[0];
+  if (s.kind != ST_LINES || s.i[10] != 0 || s.i[9] < 0 || s.i[9] > 2) return false;
+  if (!s.p[0].same(PtrRef(BUF_INPUT, 0)) || !s.p[1].same(PtrRef(BUF_OUTPUT, 0))) return false;
+  const LineKernelMeta& m = line_kernel_registry()[(size_t)s.variant];
+  if (m.in_col || m.out_col || m.twid != 0 || m.swap_in != m.swap_out) return false;
+  if (s.i[9] == 0 && (s.i[2] != 1 || s.i[4] != 1 || s.i[3] != m.N || s.i[5] != m.N)) return false;   // c2c: dense lines, no pitches
+  s.i[11] = 1;
+  ir.route += "f16 ";
+  return true;
+}
+
+void wrap_f16_storage(const mi355fft_plan_desc& d, PlanIR& ir) {
+  const uint64_t in32 = ir.in_bytes, out32 = ir.out_bytes;
+  ir.in_bytes = align_up(in32 / 2, 4);
+  ir.out_bytes = align_up(out32 / 2, 4);
+  if (fuse_f16_storage(ir)) return;
+  const auto grid = [](int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(((n + 7) / 8 + 255) / 256, Builder::MAX_BLOCKS)); };   // 8 scalars a lane
+  const uint64_t in_stage = align_up(ir.work_bytes, 256);
+  const uint64_t out_stage = d.in_place ? in_stage : align_up(in_stage + in32, 256);
+  ir.work_bytes = d.in_place ? align_up(in_stage + in32, 256) : align_up(out_stage + out32, 256);
+  for (Step& s : ir.steps)
+    for (PtrRef& p : s.p) {
+      if (p.buf == BUF_INPUT) p = PtrRef(BUF_WORK, (int64_t)in_stage + p.off);
+      else if (p.buf == BUF_OUTPUT) p = PtrRef(BUF_WORK, (int64_t)out_stage + p.off);
+    }
+  std::vector<Step> steps;
+  const auto convert = [&](StepKind kind, PtrRef src, PtrRef dst, uint64_t scalars) {
+    Step c;
+    c.kind = kind; c.p[0] = src; c.p[1] = dst; c.i[0] = (int64_t)scalars; c.grid = grid((int64_t)scalars);
+    steps.push_back(c);
+  };
+  convert(ST_F16_TO_F32, PtrRef(BUF_INPUT, 0), PtrRef(BUF_WORK, (int64_t)in_stage), in32 / 4);
+  const bool keep_out = d.io_output.enabled && !d.io_output.clear_outside;
+  if (keep_out) convert(ST_F16_TO_F32, PtrRef(BUF_OUTPUT, 0), PtrRef(BUF_WORK, (int64_t)out_stage), out32 / 4);
+  steps.insert(steps.end(), ir.steps.begin(), ir.steps.end());
+  convert(ST_F32_TO_F16, PtrRef(BUF_WORK, (int64_t)out_stage), PtrRef(d.in_place ? BUF_INPUT : BUF_OUTPUT, 0), out32 / 4);
+  ir.steps.swap(steps);
+  ir.route = std::string(keep_out ? "f16-in+out " : "f16-in ") + ir.route + "f16-out ";
+}
+
 }  // namespace
+
+int build_plan_f32(const mi355fft_plan_desc& desc, const PlannerOptions& opt, PlanIR& out, std::string& err);
 
 int build_plan(const mi355fft_plan_desc& desc, const PlannerOptions& opt, PlanIR& out, std::string& err) {
   out = PlanIR();
   out.desc = desc;
   int rc = validate_common(desc, err);
   if (rc) return rc;
+  const bool f16 = desc.precision == MI355FFT_PRECISION_F16_STORAGE;
+  if (f16 && (rc = validate_f16_storage(desc, err))) return rc;
+  // c2c N = 8192 under f16: the LDS ROW instance (LINE_ROW(8192, ...)) takes binary16 sides; line-reg has no such instance
+  if (f16 && desc.type == MI355FFT_C2C && opt.line32k >= 1) {
+    PlannerOptions o = opt;
+    o.line32k = 0;
+    PlanIR probe;
+    std::string e2;
+    if (build_plan_f32(desc, o, probe, e2) == MI355FFT_OK && probe.steps.size() == 1 && probe.steps[0].kind == ST_LINES) {
+      wrap_f16_storage(desc, probe);
+      if (probe.steps.size() == 1) { out = probe; return MI355FFT_OK; }
+    }
+  }
+  rc = build_plan_f32(desc, opt, out, err);
+  if (rc) return rc;
+  if (f16) wrap_f16_storage(desc, out);
+  return MI355FFT_OK;
+}
+
+int build_plan_f32(const mi355fft_plan_desc& desc, const PlannerOptions& opt, PlanIR& out, std::string& err) {
+  out = PlanIR();
+  out.desc = desc;
+  int rc;
   Builder b(out, opt);
   switch (desc.type) {
     case MI355FFT_C2C: rc = build_c2c(desc, b, err); break;

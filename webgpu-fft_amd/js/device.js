@@ -129,7 +129,7 @@ export class HipDevice {
     this.queue = new HipQueue(this);
     const info = native.deviceInfo(this._h);
     this.info = info;
-    this.features = new Set();      // no shader-f16 / subgroups: precision "f16-storage" is out of scope
+    this.features = new Set(["shader-f16"]);      // precision "f16-storage" plans (binary16 sides); no subgroups
     this.limits = Object.freeze({
       maxBufferSize: info.hbmTotal,
       maxStorageBufferBindingSize: info.hbmTotal,   // flat 64-bit device pointers: no binding windows

@@ -317,7 +317,7 @@ export function resolvePlanOptions(opts) {
   } else if (!isPlainObject(layout) || layout.interleavedComplex !== true) throw new Error(type + " requires layout.interleavedComplex=true");
   const precision = dflt(opts.precision, "f32");
   assertOneOf(precision, ["f32", "f16-storage"], "precision");
-  if (precision !== "f32") throw new Error('Unsupported: precision "f16-storage" is outside the MI355X hot path (f32 only)');
+  if (precision !== "f32" && type === "fftconv") throw new Error('fftconv supports precision:"f32" only in current implementation');
   // logical domains of the two sides: r2c writes / c2r reads the PACKED spectrum (r2c.js:72-123, c2r.js:168-220)
   const packedShape = [Math.floor(shape[0] / 2) + 1].concat(shape.slice(1));
   const inLogical = type === "c2r" ? packedShape : shape;
@@ -333,8 +333,9 @@ export function resolvePlanOptions(opts) {
     : { read: normalizeZeroPad(rank, inLogical, { read: (zpIn || {}).read }).read,
         write: normalizeZeroPad(rank, outLogical, { write: (zpIn || {}).write }).write };
   const inPlace = !!opts.inPlace;
-  const meta = { type, shape, rank, batch, inPlace, ioView, zeroPad };
-  const desc = { type: TYPE_CODE[type], shape, batch, inPlace: inPlace ? 1 : 0, direction: 0, normalize: 0 };
+  const meta = { type, shape, rank, batch, inPlace, ioView, zeroPad, precision };
+  // precision "f16-storage": binary16 sides, f32 arithmetic (include/mi355fft.h mi355fft_plan_desc.precision)
+  const desc = { type: TYPE_CODE[type], shape, batch, inPlace: inPlace ? 1 : 0, direction: 0, normalize: 0, precision: precision === "f32" ? 0 : 1 };
   if (ioView.input) desc.ioInput = ioView.input;
   if (ioView.output) desc.ioOutput = Object.assign({}, ioView.output, { clearOutside: ioView.output.clearOutside ? 1 : 0 });
   if (zeroPad.read) desc.zeroRead = zeroPad.read;
@@ -413,6 +414,10 @@ export function resolvePlanOptions(opts) {
   const inShape = ioView.input ? ioView.input.shape : (type === "c2r" ? packed : shape);
   const outShape = ioView.output ? ioView.output.shape : (type === "r2c" ? packed : shape);
   const sides = resolveLayoutSemantics(layout, rank, inShape, outShape);
+  if (precision !== "f32" && (sides.input || sides.output)) {     // c2c.js:612-613, r2c.js:118-119, c2r.js:215-216, dct_fft.js:163-164
+    if (trig) throw new Error('custom strides for dct/dst currently support precision:"f32" only');
+    throw new Error('custom strides currently support precision:"f32" only' + (type === "c2c" ? "" : " for " + type));
+  }
   desc.direction = DIRECTION_CODE[direction];
   desc.normalize = NORMALIZE_CODE[normalize];
   if (sides.input) desc.input = sides.input;

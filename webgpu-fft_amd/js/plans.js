@@ -37,6 +37,9 @@ export class Plan extends NativePlanBase {
   constructor(device, opts) {
     super(device);
     const { desc, meta } = resolvePlanOptions(opts);
+    if (meta.precision === "f16-storage" && !(device.features && device.features.has && device.features.has("shader-f16"))) {     // c2c.js:555-557
+      throw new Error('precision="f16-storage" requires device.features.has("shader-f16")');
+    }
     Object.assign(this, meta);
     // route metadata the reference exposes on its plans and its tests read (c2c.js:661-666, complete.suite.js:4790-4808)
     this._usesStridedInput = !!meta.inputLayout;

@@ -10,6 +10,7 @@ MAX_RANK = 8
 C2C, R2C, C2R, FFTCONV = 0, 1, 2, 3
 FORWARD, INVERSE = 0, 1
 NORM = {"none": 0, "backward": 1, "unitary": 2}
+PRECISION = {"f32": 0, "f16-storage": 1}
 TYPE = {"c2c": C2C, "r2c": R2C, "c2r": C2R, "fftconv": FFTCONV,
         "dct1": 4, "dct2": 5, "dct3": 6, "dct4": 7, "dst1": 8, "dst2": 9, "dst3": 10, "dst4": 11}
 DIRECTION = {"forward": FORWARD, "inverse": INVERSE}
@@ -63,7 +64,7 @@ class PlanDesc(ctypes.Structure):
         ("zero_read", ZeroRange),
         ("zero_write", ZeroRange),
         ("axes_mask", ctypes.c_uint32),
-        ("reserved2", ctypes.c_uint32),
+        ("precision", ctypes.c_uint32),
     ]
 
 
@@ -115,7 +116,7 @@ def _fill_range(dst, spec, rank):
 
 
 def make_desc(type, shape, batch=1, direction="forward", normalize="none", in_place=False, input_layout=None, output_layout=None,
-              conv=None, io_view=None, zero_pad=None, axes=None):
+              conv=None, io_view=None, zero_pad=None, axes=None, precision="f32"):
     """Build a PlanDesc from already-RESOLVED options (layout resolution lives in mi355fft.plans)."""
     d = PlanDesc()
     d.struct_size = ctypes.sizeof(PlanDesc)
@@ -150,6 +151,7 @@ def make_desc(type, shape, batch=1, direction="forward", normalize="none", in_pl
     if axes is not None:
         for a in axes:
             d.axes_mask |= 1 << int(a)
+    d.precision = PRECISION[precision] if isinstance(precision, str) else int(precision)
     return d
 
 

@@ -412,8 +412,8 @@ def resolve_plan_options(opts):
         raise ValueError(f"{typ} requires layout.interleavedComplex=true")
     precision = opts.get("precision", "f32")
     _assert_one_of(precision, ("f32", "f16-storage"), "precision")
-    if precision != "f32":
-        raise NotImplementedError('precision "f16-storage" is outside the MI355X hot path (f32 only)')
+    if precision != "f32" and typ == "fftconv":
+        raise ValueError('fftconv supports precision:"f32" only in current implementation')
     # logical domains of the two sides: r2c writes / c2r reads the PACKED spectrum (r2c.js:72-123, c2r.js:168-220)
     packed_shape = [shape[0] // 2 + 1] + shape[1:]
     in_logical = packed_shape if typ == "c2r" else shape
@@ -503,7 +503,11 @@ def resolve_plan_options(opts):
     in_shape = io_view["input"]["shape"] if io_view["input"] else (packed if typ == "c2r" else shape)
     out_shape = io_view["output"]["shape"] if io_view["output"] else (packed if typ == "r2c" else shape)
     inp, outl = resolve_layout_semantics(layout, rank, in_shape, out_shape)
-    out.update({"direction": direction, "input_layout": inp, "output_layout": outl})
+    if precision != "f32" and (inp or outl):       # c2c.js:612-613, r2c.js:118-119, c2r.js:215-216, dct_fft.js:163-164
+        if trig:
+            raise ValueError('custom strides for dct/dst currently support precision:"f32" only')
+        raise ValueError('custom strides currently support precision:"f32" only' + ("" if typ == "c2c" else f" for {typ}"))
+    out.update({"direction": direction, "input_layout": inp, "output_layout": outl, "precision": precision})
     return out
 
 
