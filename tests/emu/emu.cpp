@@ -26,7 +26,6 @@ static thread_local pthread_barrier_t* t_barrier = nullptr;
 static thread_local pthread_barrier_t* t_wave_barrier = nullptr;
 void sync_threads() { pthread_barrier_wait(t_barrier); }
 void sync_wave() { pthread_barrier_wait(t_wave_barrier); }
-void yield_thread() { std::this_thread::yield(); }
 }  // namespace emu
 
 namespace {
@@ -98,6 +97,13 @@ struct EmuLauncher {
   }
 };
 
+// records the launch shape of a fused-kernel dispatch case instead of launching (emu_check_xcd_registry)
+struct ShapeProbe {
+  unsigned block = 0, smem = 0;
+  template <class... P, class... A>
+  void launch_concurrent(void (*)(P...), unsigned, unsigned b, unsigned s, A&&...) { block = b; smem = s; }
+};
+
 }  // namespace
 
 extern "C" {
@@ -130,6 +136,22 @@ int emu_check_registry(char* msg, size_t msg_bytes) {
 #undef LINE_COL_RAGGED
 #undef CHECK
   if (cur != (int)reg.size()) { std::snprintf(msg, msg_bytes, "registry size %d != %zu", cur, reg.size()); ++bad; }
+  return bad;
+}
+
+// the fused registry's threads and LDS bytes (they decide co-residency: plan.cpp xcd_launch) must be what each instance's
+// dispatch case launches with
+int emu_check_xcd_registry(char* msg, size_t msg_bytes) {
+  using namespace mi355;
+  int bad = 0;
+  for (const XcdKernelMeta& m : xcd_kernel_registry()) {
+    ShapeProbe p;
+    if (!launch_xcd_fused(m.id, XcdFusedArgs{}, 1u, p) || (int)p.block != m.threads || (int)p.smem != m.lds_bytes) {
+      std::snprintf(msg, msg_bytes, "fused registry mismatch at id %d (%dx%d): launched %u threads, %u B of LDS; registry %d, %d", m.id, m.N1, m.N2,
+                    p.block, p.smem, m.threads, m.lds_bytes);
+      ++bad;
+    }
+  }
   return bad;
 }
 

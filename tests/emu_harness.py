@@ -25,6 +25,8 @@ def lib():
                                    ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]
         L.emu_check_registry.restype = ctypes.c_int
         L.emu_check_registry.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
+        L.emu_check_xcd_registry.restype = ctypes.c_int
+        L.emu_check_xcd_registry.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
         L.emu_fill_random.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64]
         L.emu_diff_sumsq.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_uint64, ctypes.POINTER(ctypes.c_double)]
         L.emu_plan_only.restype = ctypes.c_int

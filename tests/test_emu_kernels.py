@@ -22,6 +22,12 @@ def test_registry_matches_device_constants():
     assert emu.lib().emu_check_registry(msg, 256) == 0, msg.value
 
 
+def test_xcd_registry_matches_launch_shapes():
+    import ctypes
+    msg = ctypes.create_string_buffer(256)
+    assert emu.lib().emu_check_xcd_registry(msg, 256) == 0, msg.value
+
+
 @pytest.mark.parametrize("n", [2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096])
 @pytest.mark.parametrize("direction", ["forward", "inverse"])
 def test_c2c_row_lines(oracle, n, direction):

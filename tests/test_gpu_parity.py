@@ -123,7 +123,7 @@ def test_c2c_in_place_and_offsets(fft, dev, oracle):
     out.destroy()
 
 
-FUSED_LG = (15, 16, 17, 18, 19, 20, 21, 22)   # 15-17: solo mode; 21, 22 (r03): register-tile instances   # MI355_XCD_KERNEL_LIST / MI355_XCD_RT_KERNEL_LIST (plan.hpp)
+FUSED_LG = (15, 16, 17, 18, 19, 20, 21, 22)   # 15-17: solo mode; 21, 22 (r03): register-tile instances   # FUSED / RT lines of csrc/xcd_kernels.def
 
 
 @pytest.mark.parametrize("fused", [0, 1, 2, 3, 4])

@@ -145,183 +145,43 @@ template <class L> bool launch_fftconv_fused(int id, const FusedConvArgs& a, uns
   return false;
 }
 
-// XCD-fused kernels.  Instance ids follow the registry order of plan.cpp (c2c forward/inverse per entry, then r2c, then c2r).
+// XCD-fused kernels: instance ONLY of xcd_kernels.def (plan.hpp XCD_INSTANCES), one case per kind.
 // In the product build EVERY instance is compiled in its own translation unit (lines_xcd_one.hip with -DMI355_XCD_ID=k):
 // these kernels sit at the edge of the 256-VGPR budget and the register allocation of one and the same kernel changed with
 // the other kernels of its translation unit (e.g. 1024x2048 c2c: 247 VGPRs and no scratch alone, 256 VGPRs and 92 B of scratch
 // per lane in a unit with eleven siblings; r2c 1024x2048: 88 B against 264 B).
-#define MI_XCD_PLUS2(...) +2
-#define MI_XCD_PLUS1(...) +1
-constexpr int XCD_INSTANCE_COUNT = 0 MI355_XCD_KERNEL_LIST(MI_XCD_PLUS2) MI355_XCD_R2C_KERNEL_LIST(MI_XCD_PLUS1) MI355_XCD_C2R_KERNEL_LIST(MI_XCD_PLUS1)
-                                     MI355_XCD_2D_KERNEL_LIST(MI_XCD_PLUS2) MI355_XCD_RT_KERNEL_LIST(MI_XCD_PLUS2) + 1 + 2 + 1 + 2 + 1 + 1 + 1 + 2 + 2 MI355_XCD_VIEW_KERNEL_LIST(MI_XCD_PLUS2) + 2;   // (+ 2048 x 1024 on register tiles, forward and inverse)   // (+ the VIEW instances of the LDS-resident kernels) (+ the VIEW instances of the 32-line 1024 x 1024 kernel) (+ 1024 x 1024 on 16-line register tiles, two 256-thread workgroups per CU: forward, inverse) (+ the register-tile r2c and c2r 1024 x 2048) (+ the fftconv pipeline for 2^20 points) + the register-tile r2c 2048 x 2048 + the two-workgroups-per-CU 1024 x 1024 (forward, inverse) + the register-tile c2r 2048 x 2048 + the 32-line register-tile 1024 x 1024 (forward, inverse)
-#undef MI_XCD_PLUS2
-#undef MI_XCD_PLUS1
-
-// ONLY < 0: every instance (host emulation); ONLY = k: instance k alone is instantiated, the others fall through
 template <int ONLY, class L> bool launch_xcd_sel(int id, const XcdFusedArgs& a, unsigned grid, L& l);
 
 #if defined(MI355_XCD_DEFINE_INSTANCES) || defined(MI355_HOST_EMU)
-enum { MI_XCD_COUNTER_BASE = __COUNTER__ + 1 };
-#define MI_XCD_CASE(KERNEL, SWAP)                                                                  \
-  {                                                                                               \
-    constexpr int ME = __COUNTER__ - MI_XCD_COUNTER_BASE;                                         \
-    if constexpr (ONLY < 0 || ONLY == ME) {                                                       \
-      if (id == ME) {                                                                             \
-        using CA = LineCfg<N1_, A0_, A1_, A2_, TA_, true, true, SWAP, false, 0>;                   \
-        using CB = LineCfg<N2_, B0_, B1_, B2_, TB_, false, MI_XCD_B_OUT_COL, false, SWAP, 0>;      \
-        using F = XcdFusedCfg<CA, CB>;                                                            \
-        l.launch_concurrent(KERNEL<CA, CB>, grid, (unsigned)F::THREADS, (unsigned)F::LDS_BYTES, a); \
-        return true;                                                                              \
-      }                                                                                           \
-    }                                                                                             \
-  }
-#define MI_XCD_PARAMS(N1, A0, A1, A2, TA, N2, B0, B1, B2, TB) \
-  constexpr int N1_ = N1, A0_ = A0, A1_ = A1, A2_ = A2, TA_ = TA, N2_ = N2, B0_ = B0, B1_ = B1, B2_ = B2, TB_ = TB;
 template <int ONLY, class L> bool launch_xcd_sel(int id, const XcdFusedArgs& a, unsigned grid, L& l) {
-#define MI_XCD_B_OUT_COL true
-#define X(...) { MI_XCD_PARAMS(__VA_ARGS__) MI_XCD_CASE(fft_xcd_fused_kernel, false) MI_XCD_CASE(fft_xcd_fused_kernel, true) }
-  MI355_XCD_KERNEL_LIST(X)
-#undef X
-#define X(...) { MI_XCD_PARAMS(__VA_ARGS__) MI_XCD_CASE(fft_xcd_r2c_kernel, false) }
-  MI355_XCD_R2C_KERNEL_LIST(X)
-#undef X
-#define X(...) { MI_XCD_PARAMS(__VA_ARGS__) MI_XCD_CASE(fft_xcd_c2r_kernel, false) }
-  MI355_XCD_C2R_KERNEL_LIST(X)
-#undef X
-#undef MI_XCD_B_OUT_COL
-#define MI_XCD_B_OUT_COL false      /* 2-D: the second pass is a ROW kernel, natural order out */
-#define X(...) { MI_XCD_PARAMS(__VA_ARGS__) MI_XCD_CASE(fft_xcd_fused_kernel, false) MI_XCD_CASE(fft_xcd_fused_kernel, true) }
-  MI355_XCD_2D_KERNEL_LIST(X)
-#undef X
-#undef MI_XCD_B_OUT_COL
-  // register-tile instances (kern_regtile.hpp): forward, then inverse, per entry
-#define MI_XCD_RT_CASE(N1, INV)                                                                                   \
-  {                                                                                                               \
-    constexpr int ME = __COUNTER__ - MI_XCD_COUNTER_BASE;                                                         \
-    if constexpr (ONLY < 0 || ONLY == ME) {                                                                       \
-      if (id == ME) {                                                                                             \
-        using F = XcdRtCfg<N1, INV>;                                                                              \
-        l.launch_concurrent(fft_xcd_rt_kernel<N1, INV>, grid, (unsigned)F::THREADS, (unsigned)F::LDS_BYTES, a);   \
-        return true;                                                                                              \
-      }                                                                                                           \
-    }                                                                                                             \
+  constexpr XcdInstance k = XCD_INSTANCES[ONLY];
+  if (id != ONLY) return false;
+  if constexpr (k.kind <= XK_VIEW) {   // LDS-resident passes; 2-D: pass B is a ROW kernel, natural order out
+    using CA = LineCfg<k.N1, k.ra[0], k.ra[1], k.ra[2], k.ta, true, true, k.inverse, false, 0>;
+    using CB = LineCfg<k.N2, k.rb[0], k.rb[1], k.rb[2], k.tb, false, k.kind != XK_TWO_D, false, k.inverse, 0>;
+    using F = XcdFusedCfg<CA, CB>;
+    if constexpr (k.kind == XK_R2C) l.launch_concurrent(fft_xcd_r2c_kernel<CA, CB>, grid, (unsigned)F::THREADS, (unsigned)F::LDS_BYTES, a);
+    else if constexpr (k.kind == XK_C2R) l.launch_concurrent(fft_xcd_c2r_kernel<CA, CB>, grid, (unsigned)F::THREADS, (unsigned)F::LDS_BYTES, a);
+    else l.launch_concurrent(fft_xcd_fused_kernel<CA, CB, k.kind == XK_VIEW>, grid, (unsigned)F::THREADS, (unsigned)F::LDS_BYTES, a);
+  } else if constexpr (k.kind == XK_RT) {
+    using F = XcdRtCfg<k.N1, k.inverse>;
+    l.launch_concurrent(fft_xcd_rt_kernel<k.N1, k.inverse>, grid, (unsigned)F::THREADS, (unsigned)F::LDS_BYTES, a);
+  } else if constexpr (k.kind == XK_RT_R2C || k.kind == XK_RT_C2R) {
+    using F = XcdRtR2cCfgN<k.N1>;
+    if constexpr (k.kind == XK_RT_R2C) l.launch_concurrent(fft_xcd_rt_r2c_kernel<k.N1>, grid, (unsigned)F::THREADS, (unsigned)F::LDS_BYTES, a);
+    else l.launch_concurrent(fft_xcd_rt_c2r_kernel<k.N1>, grid, (unsigned)F::THREADS, (unsigned)F::LDS_BYTES, a);
+  } else if constexpr (k.kind == XK_HX) {
+    l.launch_concurrent(fft_xcd_hx_kernel<k.inverse>, grid, (unsigned)HxCfg::THREADS, (unsigned)HxCfg::LDS_BYTES, a);
+  } else if constexpr (k.kind == XK_CONV) {
+    using F = Rt1kCfgT<k.tb>;
+    l.launch_concurrent(fft_xcd_conv1m_kernel<k.N1>, grid, (unsigned)F::THREADS, (unsigned)F::LDS_BYTES, a);
+  } else {   // XK_RT1K, XK_RT1K_16, XK_RT1K_VIEW, XK_RT1K_2048: Tb-line register tiles along the 1024-point rows
+    using F = Rt1kCfgT<k.tb>;
+    constexpr unsigned smem = F::LDS_BYTES + (k.N1 == 2048 ? RtCfg::TW2_ELEMS * 8 : 0);   // (2048-point columns: their stage-2 roots too)
+    l.launch_concurrent(fft_xcd_rt1k_kernel<k.inverse, k.tb, k.kind == XK_RT1K_VIEW, k.N1>, grid, (unsigned)F::THREADS, smem, a);
   }
-#define X(N1) MI_XCD_RT_CASE(N1, false) MI_XCD_RT_CASE(N1, true)
-  MI355_XCD_RT_KERNEL_LIST(X)
-#undef X
-#undef MI_XCD_RT_CASE
-  {
-    constexpr int ME = __COUNTER__ - MI_XCD_COUNTER_BASE;
-    if constexpr (ONLY < 0 || ONLY == ME) {
-      if (id == ME) { l.launch_concurrent(fft_xcd_rt_r2c_kernel<2048>, grid, (unsigned)XcdRtR2cCfg::THREADS, (unsigned)XcdRtR2cCfg::LDS_BYTES, a); return true; }
-    }
-  }
-  {
-    constexpr int ME = __COUNTER__ - MI_XCD_COUNTER_BASE;
-    if constexpr (ONLY < 0 || ONLY == ME) {
-      if (id == ME) { l.launch_concurrent(fft_xcd_hx_kernel<false>, grid, (unsigned)HxCfg::THREADS, (unsigned)HxCfg::LDS_BYTES, a); return true; }
-    }
-  }
-  {
-    constexpr int ME = __COUNTER__ - MI_XCD_COUNTER_BASE;
-    if constexpr (ONLY < 0 || ONLY == ME) {
-      if (id == ME) { l.launch_concurrent(fft_xcd_hx_kernel<true>, grid, (unsigned)HxCfg::THREADS, (unsigned)HxCfg::LDS_BYTES, a); return true; }
-    }
-  }
-  {
-    constexpr int ME = __COUNTER__ - MI_XCD_COUNTER_BASE;
-    if constexpr (ONLY < 0 || ONLY == ME) {
-      if (id == ME) { l.launch_concurrent(fft_xcd_rt_c2r_kernel<2048>, grid, (unsigned)XcdRtR2cCfg::THREADS, (unsigned)XcdRtR2cCfg::LDS_BYTES, a); return true; }
-    }
-  }
-  {
-    constexpr int ME = __COUNTER__ - MI_XCD_COUNTER_BASE;
-    if constexpr (ONLY < 0 || ONLY == ME) {
-      if (id == ME) { l.launch_concurrent(fft_xcd_rt1k_kernel<false>, grid, (unsigned)Rt1kCfg::THREADS, (unsigned)Rt1kCfg::LDS_BYTES, a); return true; }
-    }
-  }
-  {
-    constexpr int ME = __COUNTER__ - MI_XCD_COUNTER_BASE;
-    if constexpr (ONLY < 0 || ONLY == ME) {
-      if (id == ME) { l.launch_concurrent(fft_xcd_rt1k_kernel<true>, grid, (unsigned)Rt1kCfg::THREADS, (unsigned)Rt1kCfg::LDS_BYTES, a); return true; }
-    }
-  }
-  {
-    constexpr int ME = __COUNTER__ - MI_XCD_COUNTER_BASE;
-    if constexpr (ONLY < 0 || ONLY == ME) {
-      if (id == ME) { l.launch_concurrent(fft_xcd_conv1m_kernel<1024>, grid, (unsigned)Rt1kCfg::THREADS, (unsigned)Rt1kCfg::LDS_BYTES, a); return true; }
-    }
-  }
-  {
-    constexpr int ME = __COUNTER__ - MI_XCD_COUNTER_BASE;
-    if constexpr (ONLY < 0 || ONLY == ME) {
-      if (id == ME) { l.launch_concurrent(fft_xcd_rt_r2c_kernel<1024>, grid, (unsigned)XcdRtR2cCfgN<1024>::THREADS, (unsigned)XcdRtR2cCfgN<1024>::LDS_BYTES, a); return true; }
-    }
-  }
-  {
-    constexpr int ME = __COUNTER__ - MI_XCD_COUNTER_BASE;
-    if constexpr (ONLY < 0 || ONLY == ME) {
-      if (id == ME) { l.launch_concurrent(fft_xcd_rt_c2r_kernel<1024>, grid, (unsigned)XcdRtR2cCfgN<1024>::THREADS, (unsigned)XcdRtR2cCfgN<1024>::LDS_BYTES, a); return true; }
-    }
-  }
-  {
-    constexpr int ME = __COUNTER__ - MI_XCD_COUNTER_BASE;
-    if constexpr (ONLY < 0 || ONLY == ME) {
-      if (id == ME) { l.launch_concurrent(fft_xcd_rt1k_kernel<false, 16>, grid, (unsigned)Rt1kCfgT<16>::THREADS, (unsigned)Rt1kCfgT<16>::LDS_BYTES, a); return true; }
-    }
-  }
-  {
-    constexpr int ME = __COUNTER__ - MI_XCD_COUNTER_BASE;
-    if constexpr (ONLY < 0 || ONLY == ME) {
-      if (id == ME) { l.launch_concurrent(fft_xcd_rt1k_kernel<true, 16>, grid, (unsigned)Rt1kCfgT<16>::THREADS, (unsigned)Rt1kCfgT<16>::LDS_BYTES, a); return true; }
-    }
-  }
-  {
-    constexpr int ME = __COUNTER__ - MI_XCD_COUNTER_BASE;
-    if constexpr (ONLY < 0 || ONLY == ME) {
-      if (id == ME) { l.launch_concurrent(fft_xcd_rt1k_kernel<false, 32, true>, grid, (unsigned)Rt1kCfg::THREADS, (unsigned)Rt1kCfg::LDS_BYTES, a); return true; }
-    }
-  }
-  {
-    constexpr int ME = __COUNTER__ - MI_XCD_COUNTER_BASE;
-    if constexpr (ONLY < 0 || ONLY == ME) {
-      if (id == ME) { l.launch_concurrent(fft_xcd_rt1k_kernel<true, 32, true>, grid, (unsigned)Rt1kCfg::THREADS, (unsigned)Rt1kCfg::LDS_BYTES, a); return true; }
-    }
-  }
-#define MI_XCD_CASE_VIEW(SWAP)                                                                         \
-  {                                                                                                   \
-    constexpr int ME = __COUNTER__ - MI_XCD_COUNTER_BASE;                                             \
-    if constexpr (ONLY < 0 || ONLY == ME) {                                                           \
-      if (id == ME) {                                                                                 \
-        using CA = LineCfg<N1_, A0_, A1_, A2_, TA_, true, true, SWAP, false, 0>;                       \
-        using CB = LineCfg<N2_, B0_, B1_, B2_, TB_, false, true, false, SWAP, 0>;                      \
-        using F = XcdFusedCfg<CA, CB>;                                                                \
-        l.launch_concurrent(fft_xcd_fused_kernel<CA, CB, true>, grid, (unsigned)F::THREADS, (unsigned)F::LDS_BYTES, a); \
-        return true;                                                                                  \
-      }                                                                                               \
-    }                                                                                                 \
-  }
-#define X(...) { MI_XCD_PARAMS(__VA_ARGS__) MI_XCD_CASE_VIEW(false) MI_XCD_CASE_VIEW(true) }
-  MI355_XCD_VIEW_KERNEL_LIST(X)
-#undef X
-#undef MI_XCD_CASE_VIEW
-  {
-    constexpr int ME = __COUNTER__ - MI_XCD_COUNTER_BASE;
-    if constexpr (ONLY < 0 || ONLY == ME) {
-      if (id == ME) { l.launch_concurrent(fft_xcd_rt1k_kernel<false, 32, false, 2048>, grid, 512u, (unsigned)(Rt1kCfg::LDS_BYTES + RtCfg::TW2_ELEMS * 8), a); return true; }
-    }
-  }
-  {
-    constexpr int ME = __COUNTER__ - MI_XCD_COUNTER_BASE;
-    if constexpr (ONLY < 0 || ONLY == ME) {
-      if (id == ME) { l.launch_concurrent(fft_xcd_rt1k_kernel<true, 32, false, 2048>, grid, 512u, (unsigned)(Rt1kCfg::LDS_BYTES + RtCfg::TW2_ELEMS * 8), a); return true; }
-    }
-  }
-  static_assert(__COUNTER__ - MI_XCD_COUNTER_BASE == XCD_INSTANCE_COUNT, "instance ids out of step with the lists");
-  return false;
+  return true;
 }
-#undef MI_XCD_CASE
-#undef MI_XCD_PARAMS
 #endif
 
 template <class L, int... Is>
@@ -329,11 +189,7 @@ bool launch_xcd_fold(int id, const XcdFusedArgs& a, unsigned grid, L& l, std::in
   return ((id == Is && launch_xcd_sel<Is, L>(id, a, grid, l)) || ...);
 }
 template <class L> bool launch_xcd_fused(int id, const XcdFusedArgs& a, unsigned grid, L& l) {
-#ifdef MI355_HOST_EMU
-  return launch_xcd_sel<-1, L>(id, a, grid, l);
-#else
   return launch_xcd_fold(id, a, grid, l, std::make_integer_sequence<int, XCD_INSTANCE_COUNT>{});
-#endif
 }
 
 // XCD-resident kernel (kern_xcd_res.hpp): variant bit 0 = inverse, bit 1 = data-movement skeleton.  Own translation unit

@@ -443,9 +443,6 @@ __global__ void __launch_bounds__(RtCfg::THREADS) fft_xcd_rt_r2c_kernel(const Xc
     }
   }
 }
-struct XcdRtR2cCfg {
-  static constexpr int THREADS = RtCfg::THREADS, LDS_BYTES = (RtCfg::HALF_ELEMS + RtCfg::TW2_ELEMS) * 8 + 64;
-};
 template <int N1_> struct XcdRtR2cCfgN { static constexpr int THREADS = RtCfg::THREADS, LDS_BYTES = XcdRtCfg<N1_, false>::LDS_BYTES; };
 
 // ---- c2r: the Hermitian four-step of kern_xcd_real.hpp on register tiles, N = 2048 x 2048 real samples -----------------------

@@ -62,7 +62,7 @@ template <class T> MI_DEV T* sgpr_base(T* p) {
   asm volatile("" : "+s"(a));
   return (T*)(__attribute__((address_space(1))) T*)a;
 }
-#define MI_LDS_ATOMIC_ADD_U32(p, v) __hip_atomic_fetch_add((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
+#define MI_LDS_FETCH_ADD_U32(p, v) __hip_atomic_fetch_add((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
 // device-scope (sc1) 8-byte load: served by the XCD's L2, never by this CU's L1
 MI_DEV cf ld_sc1(const cf* p) {
   const unsigned long long v = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -77,7 +77,7 @@ MI_DEV cf ld_sc1(const cf* p) {
 #define MI_COMPILER_ACQUIRE() __atomic_thread_fence(__ATOMIC_ACQUIRE)
 template <class T> MI_DEV T* sgpr_base(T* p) { return p; }
 #define MI_WAVE_ONLY_SYNC() emu::sync_wave()
-#define MI_LDS_ATOMIC_ADD_U32(p, v) __atomic_fetch_add((p), (v), __ATOMIC_SEQ_CST)
+#define MI_LDS_FETCH_ADD_U32(p, v) __atomic_fetch_add((p), (v), __ATOMIC_SEQ_CST)
 MI_DEV cf ld_sc1(const cf* p) { __atomic_thread_fence(__ATOMIC_SEQ_CST); return *p; }
 #endif
 
@@ -125,7 +125,7 @@ MI_DEV void res_signal(unsigned* counter, unsigned* s_meet, int lane) {
   MI_WAIT_VMEM();
   MI_WAVE_ONLY_SYNC();   // every lane of the wave is here (lock-step on the GPU; the emulation's lanes are free-running threads)
   if (lane == 0) {
-    const unsigned old = MI_LDS_ATOMIC_ADD_U32(s_meet, 1u);
+    const unsigned old = MI_LDS_FETCH_ADD_U32(s_meet, 1u);
     if (old & 1u) MI_ATOMIC_ADD_U32(counter, 1u);
   }
 }

@@ -6,6 +6,6 @@
 #error "compile with -DMI355_XCD_ID=<instance id>"
 #endif
 namespace mi355 {
-static_assert(MI355_XCD_ID >= 0 && MI355_XCD_ID < XCD_INSTANCE_COUNT, "no such XCD kernel instance: update XCD_IDS in the Makefile");
+static_assert(MI355_XCD_ID >= 0 && MI355_XCD_ID < XCD_INSTANCE_COUNT, "no such XCD kernel instance (xcd_kernels.def)");
 template bool launch_xcd_sel<MI355_XCD_ID, HipLauncher>(int, const XcdFusedArgs&, unsigned, HipLauncher&);
 }

@@ -87,83 +87,39 @@ const std::vector<ConvKernelMeta>& conv_kernel_registry() {
   return reg;
 }
 
-#define MI_RT_COMMA(n) n,
+namespace {
+// launch shape of an XCD-fused instance: host copies of the Cfg constants its case in dispatch.hpp launches with (kern_xcd.hpp
+// XcdFusedCfg, kern_regtile.hpp), checked against them by tests/emu (emu_check_xcd_registry)
+XcdKernelMeta xcd_meta(int id, const XcdInstance& k) {
+  XcdKernelMeta m{k, id, 0, 0};
+  constexpr int RT_HALF = 16 * 32 * 32, RT_TW2 = 31 * 64, TW1_1K = 31 * 32;   // RtCfg::HALF_ELEMS, RtCfg::TW2_ELEMS, Rt1kCfgT::TW1_ELEMS
+  if (k.kind <= XK_VIEW) {   // XcdFusedCfg: the larger of the two passes' tiles + their stage tables (one copy if the passes are the same)
+    const LineKernelMeta ma = make_meta(0, k.N1, k.ra[0], k.ra[1], k.ra[2], k.ta, true, true, k.inverse, false, 0);
+    const LineKernelMeta mb = make_meta(0, k.N2, k.rb[0], k.rb[1], k.rb[2], k.tb, false, k.kind != XK_TWO_D, false, k.inverse, 0);
+    const int da = ma.lds_bytes - ma.tw_elems * 8, db = mb.lds_bytes - mb.tw_elems * 8;
+    const bool shared = k.N1 == k.N2 && k.ra[0] == k.rb[0] && k.ra[1] == k.rb[1] && k.ra[2] == k.rb[2];
+    m.threads = ma.threads;
+    m.lds_bytes = std::max(da, db) + (ma.tw_elems + (shared ? 0 : mb.tw_elems)) * 8 + 64;
+  } else if (k.kind == XK_RT || k.kind == XK_RT_R2C || k.kind == XK_RT_C2R) {   // XcdRtCfg: max(pass A's LDS tile, one exchange half) + tables
+    const bool a_rt = k.N1 == 2048;   // (2048-point pass A on register tiles too: no LDS tile, no line table)
+    const LineKernelMeta ma = make_meta(0, a_rt ? 1024 : k.N1, 32, (a_rt ? 1024 : k.N1) / 32, 1, 16, true, true, k.inverse, false, 0);
+    m.threads = 512;
+    m.lds_bytes = std::max(a_rt ? 0 : ma.lds_bytes - ma.tw_elems * 8, RT_HALF * 8) + (a_rt ? 0 : ma.tw_elems * 8) + RT_TW2 * 8 + 64;
+  } else if (k.kind == XK_HX) {   // HxCfg: 16-line tiles, 512 threads
+    m.threads = 512;
+    m.lds_bytes = (16 * 32 * 16 + TW1_1K) * 8 + 64;
+  } else {   // Rt1kCfgT<Tb>: Tb-line tiles, 16 Tb threads; 2048 x 1024 adds the stage-2 roots of its 2048-point columns
+    m.threads = 16 * k.tb;
+    m.lds_bytes = (k.tb * 32 * 16 + TW1_1K + (k.N1 == 2048 ? RT_TW2 : 0)) * 8 + 64;
+  }
+  return m;
+}
+}  // namespace
+
 const std::vector<XcdKernelMeta>& xcd_kernel_registry() {
   static const std::vector<XcdKernelMeta> reg = [] {
     std::vector<XcdKernelMeta> r;
-    int id = 0;
-#define XCD_META(N1, A0, A1, A2, TA, N2, B0, B1, B2, TB, INV, REAL)                                       \
-  {                                                                                                       \
-    const LineKernelMeta ma = make_meta(0, N1, A0, A1, A2, TA, true, true, INV, false, 0);                \
-    const LineKernelMeta mb = make_meta(0, N2, B0, B1, B2, TB, false, (REAL) != 3, false, INV, 0);        \
-    XcdKernelMeta m{id++, N1, N2, {A0, A1, A2}, {B0, B1, B2}, TA, TB, INV, ma.threads, 0, REAL, 0};       \
-    const int da = ma.lds_bytes - ma.tw_elems * 8, db = mb.lds_bytes - mb.tw_elems * 8;                   \
-    const bool shared = N1 == N2 && A0 == B0 && A1 == B1 && A2 == B2;                                     \
-    m.lds_bytes = (da > db ? da : db) + (ma.tw_elems + (shared ? 0 : mb.tw_elems)) * 8 + 64;              \
-    r.push_back(m);                                                                                       \
-  }
-#define X(N1, A0, A1, A2, TA, N2, B0, B1, B2, TB)                                                          \
-  XCD_META(N1, A0, A1, A2, TA, N2, B0, B1, B2, TB, false, 0)                                          \
-  XCD_META(N1, A0, A1, A2, TA, N2, B0, B1, B2, TB, true, 0)
-    MI355_XCD_KERNEL_LIST(X)
-#undef X
-#define X(N1, A0, A1, A2, TA, N2, B0, B1, B2, TB) XCD_META(N1, A0, A1, A2, TA, N2, B0, B1, B2, TB, false, 1)
-    MI355_XCD_R2C_KERNEL_LIST(X)
-#undef X
-#define X(N1, A0, A1, A2, TA, N2, B0, B1, B2, TB) XCD_META(N1, A0, A1, A2, TA, N2, B0, B1, B2, TB, false, 2)
-    MI355_XCD_C2R_KERNEL_LIST(X)
-#undef X
-#define X(N1, A0, A1, A2, TA, N2, B0, B1, B2, TB)                                                          \
-  XCD_META(N1, A0, A1, A2, TA, N2, B0, B1, B2, TB, false, 3)                                              \
-  XCD_META(N1, A0, A1, A2, TA, N2, B0, B1, B2, TB, true, 3)
-    MI355_XCD_2D_KERNEL_LIST(X)
-#undef X
-#undef XCD_META
-    // register-tile instances (kern_regtile.hpp XcdRtCfg): 512 threads; LDS = max(pass A's LDS tile, one exchange half) + tables
-    for (int n1 : {MI355_XCD_RT_KERNEL_LIST(MI_RT_COMMA)}) for (int inv = 0; inv < 2; ++inv) {
-      const bool a_rt = n1 == 2048;
-      const LineKernelMeta ma = make_meta(0, a_rt ? 1024 : n1, 32, (a_rt ? 1024 : n1) / 32, 1, 16, true, true, inv != 0, false, 0);
-      XcdKernelMeta m{id++, n1, 2048, {32, a_rt ? 64 : n1 / 32, 1}, {64, 32, 1}, 16, 16, inv != 0, 512, 0, 0, 1};
-      const int data_a = a_rt ? 0 : ma.lds_bytes - ma.tw_elems * 8, tw_a = a_rt ? 0 : ma.tw_elems * 8;
-      m.lds_bytes = std::max(data_a, 16 * 32 * 32 * 8) + tw_a + 31 * 64 * 8 + 64;
-      r.push_back(m);
-    }
-    { XcdKernelMeta m{id++, 2048, 2048, {64, 32, 1}, {64, 32, 1}, 16, 16, false, 512, (16 * 32 * 32 + 31 * 64) * 8 + 64, 1, 1}; r.push_back(m); }   // r2c 2048 x 2048 (fft_xcd_rt_r2c_kernel)
-    for (int inv = 0; inv < 2; ++inv) {   // 1024 x 1024 with two workgroups per CU (fft_xcd_hx_kernel): rt = 2
-      XcdKernelMeta m{id++, 1024, 1024, {32, 32, 1}, {32, 32, 1}, 16, 16, inv != 0, 512, (16 * 32 * 16 + 31 * 32) * 8 + 64, 0, 2}; r.push_back(m);
-    }
-    { XcdKernelMeta m{id++, 2048, 2048, {64, 32, 1}, {64, 32, 1}, 16, 16, false, 512, (16 * 32 * 32 + 31 * 64) * 8 + 64, 2, 1}; r.push_back(m); }   // c2r 2048 x 2048 (fft_xcd_rt_c2r_kernel)
-    for (int inv = 0; inv < 2; ++inv) {   // 1024 x 1024 on 32-line register tiles (fft_xcd_rt1k_kernel): rt = 3
-      XcdKernelMeta m{id++, 1024, 1024, {32, 32, 1}, {32, 32, 1}, 32, 32, inv != 0, 512, (32 * 32 * 16 + 31 * 32) * 8 + 64, 0, 3}; r.push_back(m);
-    }
-    { XcdKernelMeta m{id++, 1024, 1024, {32, 32, 1}, {32, 32, 1}, 32, 32, false, 512, (32 * 32 * 16 + 31 * 32) * 8 + 64, 4, 3}; r.push_back(m); }   // real = 4: fftconv pipeline for 2^20 points (fft_xcd_conv1m_kernel)
-    { const LineKernelMeta ma = make_meta(0, 1024, 32, 32, 1, 16, true, true, false, false, 0);   // r2c 1024 x 2048: LDS-resident pass A + register-tile pass B (fft_xcd_rt_r2c_kernel<1024>)
-      XcdKernelMeta m{id++, 1024, 2048, {32, 32, 1}, {64, 32, 1}, 16, 16, false, 512, 0, 1, 1};
-      m.lds_bytes = std::max(ma.lds_bytes - ma.tw_elems * 8, 16 * 32 * 32 * 8) + ma.tw_elems * 8 + 31 * 64 * 8 + 64; r.push_back(m); }
-    { const LineKernelMeta ma = make_meta(0, 1024, 32, 32, 1, 16, true, true, false, false, 0);   // c2r 1024 x 2048 (fft_xcd_rt_c2r_kernel<1024>)
-      XcdKernelMeta m{id++, 1024, 2048, {32, 32, 1}, {64, 32, 1}, 16, 16, false, 512, 0, 2, 1};
-      m.lds_bytes = std::max(ma.lds_bytes - ma.tw_elems * 8, 16 * 32 * 32 * 8) + ma.tw_elems * 8 + 31 * 64 * 8 + 64; r.push_back(m); }
-    for (int inv = 0; inv < 2; ++inv) {   // 1024 x 1024 on 16-line register tiles, 256 threads, two workgroups per CU (fft_xcd_rt1k_kernel<.., 16>): rt = 5
-      XcdKernelMeta m{id++, 1024, 1024, {32, 32, 1}, {32, 32, 1}, 16, 16, inv != 0, 256, (16 * 32 * 16 + 31 * 32) * 8 + 64, 0, 5}; r.push_back(m);
-    }
-    for (int inv = 0; inv < 2; ++inv) {   // VIEW instances of the 32-line 1024 x 1024 kernel (rank-1 ioView / zeroPad as load / store predicates): rt = 6
-      XcdKernelMeta m{id++, 1024, 1024, {32, 32, 1}, {32, 32, 1}, 32, 32, inv != 0, 512, (32 * 32 * 16 + 31 * 32) * 8 + 64, 0, 6}; r.push_back(m);
-    }
-#define X(N1, A0, A1, A2, TA, N2, B0, B1, B2, TB)                                                          \
-  for (int inv = 0; inv < 2; ++inv) {   /* VIEW instances of the LDS-resident fused kernel: rt = 6 */     \
-    const LineKernelMeta ma = make_meta(0, N1, A0, A1, A2, TA, true, true, inv != 0, false, 0);           \
-    const LineKernelMeta mb = make_meta(0, N2, B0, B1, B2, TB, false, true, false, inv != 0, 0);          \
-    XcdKernelMeta m{id++, N1, N2, {A0, A1, A2}, {B0, B1, B2}, TA, TB, inv != 0, ma.threads, 0, 0, 6};     \
-    const int da = ma.lds_bytes - ma.tw_elems * 8, db = mb.lds_bytes - mb.tw_elems * 8;                   \
-    const bool shared = N1 == N2 && A0 == B0 && A1 == B1 && A2 == B2;                                     \
-    m.lds_bytes = (da > db ? da : db) + (ma.tw_elems + (shared ? 0 : mb.tw_elems)) * 8 + 64;              \
-    r.push_back(m);                                                                                       \
-  }
-    MI355_XCD_VIEW_KERNEL_LIST(X)
-#undef X
-    for (int inv = 0; inv < 2; ++inv) {   // 2^21 as 2048 x 1024: 16-line register tiles down the columns, 32-line register tiles along the rows (fft_xcd_rt1k_kernel<.., 2048>): rt = 7
-      XcdKernelMeta m{id++, 2048, 1024, {64, 32, 1}, {32, 32, 1}, 16, 32, inv != 0, 512, (32 * 32 * 16 + 31 * 32 + 31 * 64) * 8 + 64, 0, 7}; r.push_back(m);
-    }
+    for (const XcdInstance& k : XCD_INSTANCES) r.push_back(xcd_meta((int)r.size(), k));
     return r;
   }();
   return reg;
@@ -354,48 +310,99 @@ struct Builder {
   // c2r 2^20 289 -> 300.  So: one slot per group, and as many groups per XCD (a power of two, at most 16) as keep all slots of the chip
   // within the 256 MiB Infinity Cache.  The 2048-point register-tile instances keep two slots (their single group per XCD measured
   // the same either way).  MI355FFT_XCD_SPLIT / MI355FFT_XCD_SLOTS override.
-  void xcd_groups(uint64_t slot_bytes, bool two_slot_default, int64_t& split, int64_t& slots) const {
+  void xcd_groups(const XcdKernelMeta& xm, uint64_t slot_bytes, int64_t& split, int64_t& slots) const {
+    const bool two_slot_default = xm.kind == XK_RT;
     slots = opt.xcd_slots > 0 ? opt.xcd_slots : (two_slot_default ? 2 : 1);
     if (opt.xcd_split > 0) { split = opt.xcd_split; return; }
+    // 2048 x 2048 real transforms: two groups per XCD with one slot each (8 x 2 x 16.8 MB, a little over the Infinity Cache) measured
+    // ahead of one group with two slots on three of four boxes (r2c 288 vs 279, 282 vs 270, 269 vs 264, 232 vs 238: profiles/r03_regtile_ab.log)
+    if ((xm.kind == XK_RT_R2C || xm.kind == XK_RT_C2R) && xm.N1 == 2048 && opt.xcd_slots <= 0) { split = 2; return; }
+    // fftconv pipeline, groups per XCD x data lines per round (two slots per line, W and W2), same box, GPoints/s (profiles/r03_fftconv_pipeline_ab.log):
+    // 2 x 1 101-104 (8 x 2 x 2 x 8 MiB = the Infinity Cache), 1 x 2 95-97, 2 x 2 92-96, 1 x 1 87-89, 4 x 1 68; three launches 70-73
+    if (xm.kind == XK_CONV) { split = 2; return; }
     split = 16;
     while (split > 1 && (uint64_t)(8 * slots * split) * slot_bytes > ((uint64_t)(two_slot_default ? 320 : 256) << 20)) split >>= 1;
+  }
+
+  // One XCD-fused launch (kern_xcd.hpp, kern_xcd_real.hpp, kern_regtile.hpp): grouping, workspace, control block and tables.
+  static constexpr int XCC_IDS = 16;                     // workspace slot sets: one per XCC id a workgroup can read (4 bits)
+  static constexpr uint64_t XCD_CTL_BYTES = 40960;       // control block of a shared-mode launch (kern_xcd.hpp XcdCtl)
+  static constexpr int64_t XCD_CTL_ZERO_FLOATS = 9216;   // the part of it the ST_ZERO before every such launch clears (all of XcdCtl)
+  struct XcdLaunch {
+    bool solo;
+    int64_t grid, split = 1, slots = 1;
+    PtrRef wslots, ctl, ta, tb, lo, hi;   // tables: pass A's and pass B's stage roots, the four-step roots as HI[m >> shift] * LO[m & mask]
+    int shift = 0;
+  };
+  // Solo: every workgroup walks whole transforms alone (no registration, no cross-workgroup barrier, so no co-residency requirement
+  // and as many workgroups per CU as fit), one slot of `slot_elems` points each, all of them within the Infinity Cache.  Shared: the
+  // groups of an XCD share each transform; `split` groups of `slots` slots per XCC id, every workgroup co-resident — one per CU, two
+  // where 256 threads and <= 80 KB of LDS leave room.
+  XcdLaunch xcd_launch(const XcdKernelMeta& xm, bool solo, int64_t slot_elems, int64_t transforms) {
+    XcdLaunch x{solo, opt.compute_units};
+    if (solo) {
+      const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>((160 * 1024) / xm.lds_bytes, 2048 / xm.threads), 4));
+      x.grid = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>((int64_t)opt.compute_units * per_cu, ((int64_t)opt.solo_cap_mb << 20) / (slot_elems * 8)), transforms));
+      x.wslots = alloc_work((uint64_t)x.grid * slot_elems * 8);
+      x.ctl = alloc_work(256);
+    } else {
+      xcd_groups(xm, (uint64_t)slot_elems * 8, x.split, x.slots);
+      x.wslots = alloc_work((uint64_t)(XCC_IDS * x.slots * x.split) * slot_elems * 8);
+      x.ctl = alloc_work(XCD_CTL_BYTES);
+      if (opt.xcd_fused != 2 && ((xm.threads <= 256 && xm.lds_bytes <= 80 * 1024) || xm.kind == XK_HX)) x.grid *= 2;
+    }
+    return x;
+  }
+  // four-step roots e^{-2 pi i m/N}: 2^shift LO roots (shift = 10 from 2^20 up, half of log2 N below), HI of N >> shift
+  void xcd_roots(XcdLaunch& x, int64_t N) {
+    x.shift = N >= (1 << 20) ? 10 : lg2(N) / 2;
+    std::vector<float2h> lo((size_t)1 << x.shift), hi((size_t)std::max<int64_t>(1, N >> x.shift));
+    for (size_t l = 0; l < lo.size(); ++l) lo[l] = root_of_unity((int64_t)l, N);
+    for (size_t h = 0; h < hi.size(); ++h) hi[h] = root_of_unity((int64_t)h << x.shift, N);
+    x.lo = add_table(lo);
+    x.hi = add_table(hi);
+  }
+  // the ST_ZERO of the control block (shared mode) and the launch with the fields every fused emitter fills (dispatch.hpp
+  // ST_XCD_FUSED); the caller adds the scale, pitches other than N (i[9] in, i[10] out) and its own fields
+  Step& push_xcd(StepKind kind, int variant, const XcdLaunch& x, PtrRef src, PtrRef dst, int64_t transforms, int64_t N) {
+    if (!x.solo) { Step& z = push(ST_ZERO); z.p[0] = x.ctl; z.i[0] = XCD_CTL_ZERO_FLOATS; z.grid = 1; }
+    Step& st = push(kind);
+    st.variant = variant;
+    st.p[0] = src; st.p[1] = dst; st.p[2] = x.wslots; st.p[3] = x.ctl; st.p[4] = PtrRef(BUF_TABLE, 0);
+    st.i[0] = transforms; st.i[1] = N; st.i[2] = x.shift; st.i[3] = ((int64_t)1 << x.shift) - 1;
+    st.i[4] = x.ta.off; st.i[5] = x.tb.off; st.i[6] = x.lo.off; st.i[7] = x.hi.off; st.i[8] = x.split; st.i[9] = N; st.i[10] = N;
+    st.i[11] = x.slots; st.i[12] = x.solo ? 1 : 0; st.i[13] = opt.xcd_spin_limit;
+    st.grid = (unsigned)x.grid;
+    return st;
+  }
+  // route names of the 1-D c2c kinds in shared mode (bench.py and the tests match on them)
+  static const char* xcd_c2c_route(XcdKind k) {
+    switch (k) {
+      case XK_RT: return "xcd-fused-rt";
+      case XK_HX: return "xcd-fused-2wg";
+      case XK_RT1K: case XK_RT1K_2048: return "xcd-fused-rt32";
+      case XK_RT1K_16: return "xcd-fused-rt16x2";
+      default: return "xcd-fused";
+    }
   }
 
   // 2-D c2c planes [N1][N0] (axis 0 = N0 fastest) through the fused kernel's TWO_D instances; false if none applies
   bool emit_xcd_2d(PtrRef src, PtrRef dst, int64_t N0, int64_t N1, int64_t planes, bool inverse, float scale) {
     if (opt.force_generic || opt.xcd_fused != 1 || opt.only_pass || !opt.xcd_2d) return false;
     const XcdKernelMeta* xm = nullptr;
-    for (const auto& m : xcd_kernel_registry()) if (m.real == 3 && m.N1 == N1 && m.N2 == N0 && m.inverse == inverse) xm = &m;
+    for (const auto& m : xcd_kernel_registry()) if (m.kind == XK_TWO_D && m.N1 == N1 && m.N2 == N0 && m.inverse == inverse) xm = &m;
     if (!xm) return false;
     const int64_t N = N0 * N1;
     const LineKernelMeta ma = make_meta(0, xm->N1, xm->ra[0], xm->ra[1], xm->ra[2], xm->ta, true, true, false, false, 0);
     const LineKernelMeta mb = make_meta(0, xm->N2, xm->rb[0], xm->rb[1], xm->rb[2], xm->tb, false, false, false, false, 0);
     const bool solo = (uint64_t)N * 8 <= ((uint64_t)opt.solo_max_kb_2d << 10);
     if (!solo && !opt.xcd_shared) return false;
-    int64_t split = 1, grid = opt.compute_units, slots = 1;
-    PtrRef wslots, ctl;
-    if (solo) {
-      const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>((160 * 1024) / xm->lds_bytes, 2048 / xm->threads), 4));
-      grid = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>((int64_t)opt.compute_units * per_cu, ((int64_t)opt.solo_cap_mb << 20) / (N * 8)), planes));
-      slots = 1;
-      wslots = alloc_work((uint64_t)grid * N * 8);
-      ctl = alloc_work(256);
-    } else {
-      xcd_groups((uint64_t)N * 8, false, split, slots);
-      wslots = alloc_work((uint64_t)(16 * slots * split) * N * 8);
-      ctl = alloc_work(40960);
-      if (xm->threads <= 256 && xm->lds_bytes <= 80 * 1024) grid *= 2;
-    }
-    std::vector<float2h> one(1, float2h{1, 0});
-    const PtrRef ta = line_tables(ma), tb = line_tables(mb), tone = add_table(one);
-    if (!solo) { Step& z = push(ST_ZERO); z.p[0] = ctl; z.i[0] = 9216; z.grid = 1; }
-    Step& st = push(ST_XCD_FUSED);
-    st.variant = xm->id;
-    st.p[0] = src; st.p[1] = dst; st.p[2] = wslots; st.p[3] = ctl; st.p[4] = PtrRef(BUF_TABLE, 0);
-    st.i[0] = planes; st.i[1] = N; st.i[2] = 0; st.i[3] = 0; st.i[9] = N; st.i[10] = N;
-    st.i[4] = ta.off; st.i[5] = tb.off; st.i[6] = tone.off; st.i[7] = tone.off; st.i[8] = split; st.i[11] = slots; st.i[12] = solo ? 1 : 0; st.i[13] = opt.xcd_spin_limit;
+    XcdLaunch x = xcd_launch(*xm, solo, N, planes);
+    x.ta = line_tables(ma);
+    x.tb = line_tables(mb);
+    x.lo = x.hi = add_table(std::vector<float2h>(1, float2h{1, 0}));   // no four-step roots (shift 0)
+    Step& st = push_xcd(ST_XCD_FUSED, xm->id, x, src, dst, planes, N);
     st.f[0] = scale;
-    st.grid = (unsigned)grid;
     ir.route += std::string(solo ? "xcd-2d-solo[" : "xcd-2d[") + std::to_string(N0) + "x" + std::to_string(N1) + "] ";
     return true;
   }
@@ -405,48 +412,26 @@ struct Builder {
     if (opt.force_generic || !opt.xcd_fused || !opt.xcd_r2c || opt.only_pass || N < 4096 || (N & (N - 1))) return false;
     const int lgf = lg2(N);
     const int64_t F1 = (int64_t)1 << (lgf / 2), F2 = N / F1;
+    const XcdKind kind = c2r ? XK_C2R : XK_R2C, kind_rt = c2r ? XK_RT_C2R : XK_RT_R2C;
     const XcdKernelMeta* xm = nullptr;
     for (const auto& m : xcd_kernel_registry())
-      if (m.real == (c2r ? 2 : 1) && m.N1 == F1 && m.N2 == F2 && (!m.rt || (opt.xcd_rt && opt.xcd_shared))) xm = &m;
+      if ((m.kind == kind || (m.kind == kind_rt && opt.xcd_rt && opt.xcd_shared)) && m.N1 == F1 && m.N2 == F2) xm = &m;
     if (!xm || (N <= 8192 && opt.xcd_fused != 2)) return false;
-    const LineKernelMeta ma = make_meta(0, xm->rt ? 1024 : xm->N1, xm->rt ? 32 : xm->ra[0], xm->ra[1], xm->ra[2], xm->ta, true, true, false, false, 0);
-    const LineKernelMeta mb = make_meta(0, xm->rt ? 1024 : xm->N2, xm->rt ? 32 : xm->rb[0], xm->rb[1], xm->rb[2], xm->tb, false, true, false, false, 0);
-    const int64_t wsize = c2r ? (xm->rt ? (F1 / 2) * F2 : F1 * (F2 / 2 + 16)) : (F1 / 2 + 1) * F2;   // r2c: rows 0..N1/2; c2r: columns 0..N2/2 (+ padding; register tiles: N1/2 packed full rows)
+    const bool rt = xm->kind == kind_rt;
+    const LineKernelMeta ma = make_meta(0, rt ? 1024 : xm->N1, rt ? 32 : xm->ra[0], xm->ra[1], xm->ra[2], xm->ta, true, true, false, false, 0);
+    const LineKernelMeta mb = make_meta(0, rt ? 1024 : xm->N2, rt ? 32 : xm->rb[0], xm->rb[1], xm->rb[2], xm->tb, false, true, false, false, 0);
+    const int64_t wsize = c2r ? (rt ? (F1 / 2) * F2 : F1 * (F2 / 2 + 16)) : (F1 / 2 + 1) * F2;   // r2c: rows 0..N1/2; c2r: columns 0..N2/2 (+ padding; register tiles: N1/2 packed full rows)
     // small transforms: one workgroup per transform (solo mode, see emit_axis); the real line is N*4 bytes
     const bool solo = (uint64_t)N * 4 <= ((uint64_t)opt.solo_max_kb << 10) / (c2r ? 1 : 2) && opt.xcd_fused != 2;
     if (!solo && !opt.xcd_shared) return false;
-    int64_t split = 1, grid = opt.compute_units, slots = 1;
-    PtrRef wslots, ctl;
-    if (solo) {
-      const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>((160 * 1024) / xm->lds_bytes, 2048 / xm->threads), 4));
-      grid = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>((int64_t)opt.compute_units * per_cu, ((int64_t)opt.solo_cap_mb << 20) / (wsize * 8)), lines));
-      slots = 1;
-      wslots = alloc_work((uint64_t)grid * wsize * 8);
-      ctl = alloc_work(256);
-    } else {
-      xcd_groups((uint64_t)wsize * 8, false, split, slots);
-      // 2048 x 2048 real transforms: two groups per XCD with one slot each (8 x 2 x 16.8 MB, a little over the Infinity Cache) measured
-      // ahead of one group with two slots on three of four boxes (r2c 288 vs 279, 282 vs 270, 269 vs 264, 232 vs 238: profiles/r03_regtile_ab.log)
-      if (xm->rt == 1 && xm->N1 == 2048 && opt.xcd_split <= 0 && opt.xcd_slots <= 0) { split = 2; slots = 1; }
-      wslots = alloc_work((uint64_t)(16 * slots * split) * wsize * 8);
-      ctl = alloc_work(40960);
-    }
-    const int shift = N >= (1 << 20) ? 10 : lgf / 2;                // LO table of 2^shift roots, HI of N >> shift
-    std::vector<float2h> lo((size_t)1 << shift), hi((size_t)std::max<int64_t>(1, N >> shift));
-    for (size_t l = 0; l < lo.size(); ++l) lo[l] = root_of_unity((int64_t)l, N);
-    for (size_t h = 0; h < hi.size(); ++h) hi[h] = root_of_unity((int64_t)h << shift, N);
-    const PtrRef tb = xm->rt ? regtile_table() : line_tables(mb), ta = (xm->rt && xm->N1 == 2048) ? tb : line_tables(ma), tlo = add_table(lo), thi = add_table(hi);
-    if (!solo) { Step& z = push(ST_ZERO); z.p[0] = ctl; z.i[0] = 9216; z.grid = 1; }
-    Step& st = push(ST_XCD_FUSED);
-    st.variant = xm->id;
-    st.p[0] = src; st.p[1] = dst; st.p[2] = wslots; st.p[3] = ctl; st.p[4] = PtrRef(BUF_TABLE, 0);
-    st.i[0] = lines; st.i[1] = N; st.i[2] = shift; st.i[3] = ((int64_t)1 << shift) - 1;
+    XcdLaunch x = xcd_launch(*xm, solo, wsize, lines);
+    x.tb = rt ? regtile_table() : line_tables(mb);
+    x.ta = rt && xm->N1 == 2048 ? x.tb : line_tables(ma);
+    xcd_roots(x, N);
+    Step& st = push_xcd(ST_XCD_FUSED, xm->id, x, src, dst, lines, N);
     st.i[9] = c2r ? N / 2 + 1 : N / 2; st.i[10] = c2r ? N / 2 : N / 2 + 1;        // pitches in complex elements
-    st.i[4] = ta.off; st.i[5] = tb.off; st.i[6] = tlo.off; st.i[7] = thi.off; st.i[8] = split; st.i[11] = slots; st.i[12] = solo ? 1 : 0; st.i[13] = opt.xcd_spin_limit;
     st.f[0] = scale;
-    if (!solo && opt.xcd_fused != 2 && xm->threads <= 256 && xm->lds_bytes <= 80 * 1024) grid *= 2;   // as emit_axis: two co-resident workgroups per CU
-    st.grid = (unsigned)grid;
-    ir.route += std::string(c2r ? (solo ? "xcd-c2r-solo[N=" : xm->rt ? "xcd-c2r-rt[N=" : "xcd-c2r[N=") : (solo ? "xcd-r2c-solo[N=" : xm->rt ? "xcd-r2c-rt[N=" : "xcd-r2c[N=")) + std::to_string(xm->N1) + "x" + std::to_string(xm->N2) + "] ";
+    ir.route += std::string(c2r ? "xcd-c2r" : "xcd-r2c") + (solo ? "-solo" : rt ? "-rt" : "") + "[N=" + std::to_string(xm->N1) + "x" + std::to_string(xm->N2) + "] ";
     return true;
   }
 
@@ -543,27 +528,19 @@ struct Builder {
   bool emit_xcd_view(PtrRef in, PtrRef out, int64_t N, int64_t lines, bool inverse, float scale, const SideMap& im, const SideMap& om) {
     if (opt.force_generic || opt.xcd_fused != 1 || !opt.xcd_shared || !opt.fuse_views || opt.only_pass) return false;
     const XcdKernelMeta* xm = nullptr;
-    for (const auto& m : xcd_kernel_registry()) if (m.rt == 6 && (int64_t)m.N1 * m.N2 == N && m.inverse == inverse) xm = &m;
+    for (const auto& m : xcd_kernel_registry())
+      if ((m.kind == XK_VIEW || m.kind == XK_RT1K_VIEW) && (int64_t)m.N1 * m.N2 == N && m.inverse == inverse) xm = &m;
     if (!xm) return false;
-    int64_t split = 1, slots = 1;
-    xcd_groups((uint64_t)N * 8, false, split, slots);
-    const PtrRef wslots = alloc_work((uint64_t)(16 * slots * split) * N * 8), ctl = alloc_work(40960);
-    const int shift = N >= (1 << 20) ? 10 : lg2(N) / 2;                // LO table of 2^shift roots, HI of N >> shift (as emit_axis)
-    std::vector<float2h> lo((size_t)1 << shift), hi((size_t)(N >> shift));
-    for (size_t l = 0; l < lo.size(); ++l) lo[l] = root_of_unity((int64_t)l, N);
-    for (size_t h = 0; h < hi.size(); ++h) hi[h] = root_of_unity((int64_t)h << shift, N);
+    XcdLaunch x = xcd_launch(*xm, false, N, lines);
     const LineKernelMeta ml = make_meta(0, xm->N1, xm->ra[0], xm->ra[1], xm->ra[2], xm->ta, true, true, false, false, 0);
     const LineKernelMeta mr = make_meta(0, xm->N2, xm->rb[0], xm->rb[1], xm->rb[2], xm->tb, false, true, false, false, 0);
-    const PtrRef ta = line_tables(ml), tb = line_tables(mr), tlo = add_table(lo), thi = add_table(hi);
-    { Step& z = push(ST_ZERO); z.p[0] = ctl; z.i[0] = 9216; z.grid = 1; }
-    Step& st = push(ST_XCD_FUSED);
-    st.variant = xm->id;
-    st.p[0] = in.plus(im.offset * 8); st.p[1] = out.plus(om.offset * 8); st.p[2] = wslots; st.p[3] = ctl; st.p[4] = PtrRef(BUF_TABLE, 0);
-    st.i[0] = lines; st.i[1] = N; st.i[2] = shift; st.i[3] = ((int64_t)1 << shift) - 1; st.i[9] = im.batch_stride; st.i[10] = om.batch_stride;
-    st.i[4] = ta.off; st.i[5] = tb.off; st.i[6] = tlo.off; st.i[7] = thi.off; st.i[8] = split; st.i[11] = slots; st.i[12] = 0; st.i[13] = opt.xcd_spin_limit;
+    x.ta = line_tables(ml);
+    x.tb = line_tables(mr);
+    xcd_roots(x, N);
+    Step& st = push_xcd(ST_XCD_FUSED, xm->id, x, in.plus(im.offset * 8), out.plus(om.offset * 8), lines, N);
+    st.i[9] = im.batch_stride; st.i[10] = om.batch_stride;
     st.f[0] = scale;
     st.imap = im; st.omap = om;
-    st.grid = (unsigned)(opt.compute_units * ((xm->threads <= 256 && xm->lds_bytes <= 80 * 1024) ? 2 : 1));
     ir.route += "xcd-fused-view[N=" + std::to_string(xm->N1) + "x" + std::to_string(xm->N2) + "] ";
     return true;
   }
@@ -702,22 +679,14 @@ struct Builder {
     if (!opt.force_generic && S == 1 && N == (1 << 20) && opt.xcd_res && opt.xcd_shared && !opt.only_pass && opt.compute_units % 32 == 0) {
       // XCD-resident route (kern_xcd_res.hpp): the transform stays in the registers and LDS of one XCD's 32 workgroups between
       // its passes; hand-offs go through a 4 MiB L2-resident exchange buffer per XCD.  One workgroup per CU, all co-resident.
-      const int shift = 10;
-      std::vector<float2h> lo((size_t)1 << shift), hi((size_t)(N >> shift));
-      for (size_t l = 0; l < lo.size(); ++l) lo[l] = root_of_unity((int64_t)l, N);
-      for (size_t h = 0; h < hi.size(); ++h) hi[h] = root_of_unity((int64_t)h << shift, N);
-      const LineKernelMeta mt = make_meta(0, 1024, 32, 32, 1, 16, true, true, false, false, 0);
-      const PtrRef ta = line_tables(mt), tlo = add_table(lo), thi = add_table(hi);
-      const PtrRef wslots = alloc_work((uint64_t)16 * 4 * (1 << 20));   // 4 channels of 1 MiB per XCC id (16 ids)
-      const PtrRef ctl = alloc_work(40960);
-      { Step& z = push(ST_ZERO); z.p[0] = ctl; z.i[0] = 9216; z.grid = 1; }
-      Step& st = push(ST_XCD_RES);
-      st.variant = (inverse ? 1 : 0) + (opt.xcd_res == 2 || opt.xcd_res == 4 ? 2 : 0) + (opt.xcd_res >= 3 && !inverse ? 4 : 0);   // 3: stamps, 4: stamps on the skeleton
-      st.p[0] = src; st.p[1] = dst; st.p[2] = wslots; st.p[3] = ctl; st.p[4] = PtrRef(BUF_TABLE, 0);
-      st.i[0] = lines; st.i[1] = N; st.i[2] = shift; st.i[3] = ((int64_t)1 << shift) - 1; st.i[9] = N; st.i[10] = N;
-      st.i[4] = ta.off; st.i[5] = ta.off; st.i[6] = tlo.off; st.i[7] = thi.off; st.i[8] = opt.xcd_res_depth; st.i[11] = 1; st.i[12] = 0; st.i[13] = opt.xcd_spin_limit;
+      XcdLaunch x{false, opt.compute_units, opt.xcd_res_depth, 1};
+      x.wslots = alloc_work((uint64_t)XCC_IDS * 4 * (1 << 20));   // 4 channels of 1 MiB per XCC id
+      x.ctl = alloc_work(XCD_CTL_BYTES);
+      x.ta = x.tb = line_tables(make_meta(0, 1024, 32, 32, 1, 16, true, true, false, false, 0));
+      xcd_roots(x, N);
+      const int variant = (inverse ? 1 : 0) + (opt.xcd_res == 2 || opt.xcd_res == 4 ? 2 : 0) + (opt.xcd_res >= 3 && !inverse ? 4 : 0);   // 3: stamps, 4: stamps on the skeleton
+      Step& st = push_xcd(ST_XCD_RES, variant, x, src, dst, lines, N);
       st.f[0] = scale;
-      st.grid = (unsigned)opt.compute_units;
       ir.route += "xcd-resident[N=1024x1024,depth=" + std::to_string(opt.xcd_res_depth) + (opt.xcd_res == 2 || opt.xcd_res == 4 ? ",skeleton" : "") + (opt.xcd_res >= 3 ? ",stamps" : "") + "] ";
       return MI355FFT_OK;
     }
@@ -725,57 +694,45 @@ struct Builder {
       // XCD-fused route: both passes in one persistent launch, one transform per XCD at a time (kern_xcd.hpp)
       const int lgf = lg2(N);
       const int64_t F1 = (int64_t)1 << (lgf / 2), F2 = N / F1;
+      // the LDS-resident kernel, or a register-tile form where the options select it and shared mode is allowed (the VIEW instances
+      // serve emit_xcd_view, 2048 x 1024 the 2^21 choice below)
+      const auto usable = [&](XcdKind k) {
+        switch (k) {
+          case XK_FUSED: return true;
+          case XK_RT: return opt.xcd_rt != 0 && opt.xcd_shared;
+          case XK_HX: return opt.xcd_hx == 1 && opt.xcd_shared;
+          case XK_RT1K: return opt.xcd_hx == 2 && opt.xcd_shared;
+          case XK_RT1K_16: return opt.xcd_hx == 3 && opt.xcd_shared;
+          default: return false;
+        }
+      };
       const XcdKernelMeta* xm = nullptr;
-      for (const auto& m : xcd_kernel_registry())
-        if (!m.real && m.N1 == F1 && m.N2 == F2 && m.inverse == inverse && (!m.rt || ((m.rt == 2 ? opt.xcd_hx == 1 : m.rt == 3 ? opt.xcd_hx == 2 : m.rt == 5 ? opt.xcd_hx == 3 : m.rt == 6 || m.rt == 7 ? false : opt.xcd_rt != 0) && opt.xcd_shared))) xm = &m;
+      for (const auto& m : xcd_kernel_registry()) if (usable(m.kind) && m.N1 == F1 && m.N2 == F2 && m.inverse == inverse) xm = &m;
       // c2c 2^21: with two groups per XCD and one slot each the LDS-resident 1024 x 2048 instance (8-line tiles taken in pairs) runs at 177
       // GPoints/s, ahead of both register-tile forms — 2048 x 1024 (16-line tiles down the columns, 32-line tiles along the rows;
       // MI355FFT_XCD_RT=3) 172, 1024 x 2048 (MI355FFT_XCD_RT=2) 162: profiles/r03_regtile_ab.log.  So the register tiles serve 2^22 only.
       if (N == ((int64_t)1 << 21) && opt.xcd_rt != 2) {
         xm = nullptr;
         for (const auto& m : xcd_kernel_registry())
-          if (!m.real && m.inverse == inverse && ((opt.xcd_rt == 3 && opt.xcd_shared) ? m.rt == 7 : (!m.rt && m.N1 == F1 && m.N2 == F2))) xm = &m;
+          if (m.inverse == inverse && ((opt.xcd_rt == 3 && opt.xcd_shared) ? m.kind == XK_RT1K_2048 : (m.kind == XK_FUSED && m.N1 == F1 && m.N2 == F2))) xm = &m;
       }
       if (xm && (N > 4096 || opt.xcd_fused == 2) &&
           (opt.xcd_shared || ((uint64_t)N * 8 <= ((uint64_t)opt.solo_max_kb << 10) && opt.xcd_fused != 2))) {
-        const bool a_rt = xm->rt == 1 && xm->N1 == 2048;   // register-tile passes take their stage-2 table instead of a line kernel's
+        const bool rt = xm->kind == XK_RT, a_rt = rt && xm->N1 == 2048;   // register-tile passes take their stage-2 table instead of a line kernel's
         const LineKernelMeta ma = make_meta(0, a_rt ? 1024 : xm->N1, xm->ra[0], a_rt ? 32 : xm->ra[1], xm->ra[2], xm->ta, true, true, false, false, 0);
-        const LineKernelMeta mb = make_meta(0, xm->rt == 1 ? 1024 : xm->N2, xm->rt == 1 ? 32 : xm->rb[0], xm->rb[1], xm->rb[2], xm->tb, false, true, false, false, 0);
-        // transforms of at most 1 MiB: every workgroup walks whole transforms alone ("solo": no registration, no cross-
-        // workgroup barrier, so no co-residency requirement and as many workgroups per CU as fit); larger ones are shared by
-        // the groups of an XCD
+        const LineKernelMeta mb = make_meta(0, rt ? 1024 : xm->N2, rt ? 32 : xm->rb[0], xm->rb[1], xm->rb[2], xm->tb, false, true, false, false, 0);
+        // transforms of at most 1 MiB run in solo mode (xcd_launch); larger ones are shared by the groups of an XCD
         const bool solo = (uint64_t)N * 8 <= ((uint64_t)opt.solo_max_kb << 10) && opt.xcd_fused != 2;
-        int64_t split = 1, grid = opt.compute_units, slots = 1;
-        PtrRef wslots, ctl;
-        if (solo) {
-          const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>((160 * 1024) / xm->lds_bytes, 2048 / xm->threads), 4));
-          grid = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>((int64_t)opt.compute_units * per_cu, ((int64_t)opt.solo_cap_mb << 20) / (N * 8)), lines));
-          slots = 1;
-          wslots = alloc_work((uint64_t)grid * N * 8);          // one slot per workgroup, all of them within the Infinity Cache
-          ctl = alloc_work(256);
-        } else {
-          xcd_groups((uint64_t)N * 8, xm->rt == 1, split, slots);
-          wslots = alloc_work((uint64_t)(16 * slots * split) * N * 8);   // slots per group x `split` groups per XCC id (16 ids)
-          ctl = alloc_work(40960);
-        }
-        const int shift = N >= (1 << 20) ? 10 : lgf / 2;                // LO table of 2^shift roots, HI of N >> shift
-        std::vector<float2h> lo((size_t)1 << shift), hi((size_t)std::max<int64_t>(1, N >> shift));
-        for (size_t l = 0; l < lo.size(); ++l) lo[l] = root_of_unity((int64_t)l, N);
-        for (size_t h = 0; h < hi.size(); ++h) hi[h] = root_of_unity((int64_t)h << shift, N);
-        const PtrRef tb = xm->rt == 1 ? regtile_table() : line_tables(mb), ta = a_rt ? tb : xm->rt == 7 ? regtile_table() : line_tables(ma), tlo = add_table(lo), thi = add_table(hi);
-        if (!solo) { Step& z = push(ST_ZERO); z.p[0] = ctl; z.i[0] = 9216; z.grid = 1; }
-        Step& st = push(ST_XCD_FUSED);
-        st.variant = xm->id;
-        st.p[0] = src; st.p[1] = dst; st.p[2] = wslots; st.p[3] = ctl; st.p[4] = PtrRef(BUF_TABLE, 0);
-        st.i[0] = lines; st.i[1] = N; st.i[2] = shift; st.i[3] = ((int64_t)1 << shift) - 1;
-        st.i[9] = lane_in_pitch ? lane_in_pitch : N; st.i[10] = lane_out_pitch ? lane_out_pitch : N;
+        XcdLaunch x = xcd_launch(*xm, solo, N, lines);
+        x.tb = rt ? regtile_table() : line_tables(mb);
+        x.ta = a_rt ? x.tb : xm->kind == XK_RT1K_2048 ? regtile_table() : line_tables(ma);
+        xcd_roots(x, N);
+        Step& st = push_xcd(ST_XCD_FUSED, xm->id, x, src, dst, lines, N);
+        if (lane_in_pitch) st.i[9] = lane_in_pitch;
+        if (lane_out_pitch) st.i[10] = lane_out_pitch;
         if (lane_in_pitch || lane_out_pitch) lane_used = true;
-        st.i[4] = ta.off; st.i[5] = tb.off; st.i[6] = tlo.off; st.i[7] = thi.off; st.i[8] = split; st.i[11] = slots; st.i[12] = solo ? 1 : 0; st.i[13] = opt.xcd_spin_limit;
         st.f[0] = scale;
-        // shared mode: every workgroup must be co-resident — one per CU, two where 256 threads and <= 80 KB of LDS leave room
-        if (!solo && opt.xcd_fused != 2 && ((xm->threads <= 256 && xm->lds_bytes <= 80 * 1024) || xm->rt == 2)) grid *= 2;
-        st.grid = (unsigned)grid;
-        ir.route += std::string(solo ? "xcd-solo[N=" : xm->rt == 2 ? "xcd-fused-2wg[N=" : xm->rt == 3 ? "xcd-fused-rt32[N=" : xm->rt == 5 ? "xcd-fused-rt16x2[N=" : xm->rt == 7 ? "xcd-fused-rt32[N=" : xm->rt ? "xcd-fused-rt[N=" : "xcd-fused[N=") + std::to_string(xm->N1) + "x" + std::to_string(xm->N2) + "] ";
+        ir.route += std::string(solo ? "xcd-solo" : xcd_c2c_route(xm->kind)) + "[N=" + std::to_string(xm->N1) + "x" + std::to_string(xm->N2) + "] ";
         return MI355FFT_OK;
       }
     }
@@ -1795,30 +1752,17 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
   if (b.opt.conv_pipeline && !b.opt.force_generic && b.opt.xcd_fused == 1 && b.opt.xcd_shared && !b.opt.only_pass && rank == 1 && fN == ((int64_t)1 << 20) &&
       d.conv_boundary == MI355FFT_CIRCULAR && !zpad && !d.input.strided && !d.output.strided) {
     const XcdKernelMeta* xm = nullptr;
-    for (const auto& m : xcd_kernel_registry()) if (m.real == 4) xm = &m;
+    for (const auto& m : xcd_kernel_registry()) if (m.kind == XK_CONV) xm = &m;
     if (xm) {
-      // groups per XCD x data lines per round (two slots per line, W and W2), same box, GPoints/s (profiles/r03_fftconv_pipeline_ab.log):
-      // 2 x 1 101-104 (8 x 2 x 2 x 8 MiB = the Infinity Cache), 1 x 2 95-97, 2 x 2 92-96, 1 x 1 87-89, 4 x 1 68; three launches 70-73
-      const int64_t split = b.opt.xcd_split > 0 ? b.opt.xcd_split : 2;
-      const int64_t L = b.opt.xcd_slots > 0 ? b.opt.xcd_slots : 1;
-      const PtrRef wslots = b.alloc_work((uint64_t)(16 * 2 * L * split) * fN * 8), ctl = b.alloc_work(40960);
-      std::vector<float2h> lo(1024), hi((size_t)(fN >> 10));
-      for (int64_t l = 0; l < 1024; ++l) lo[(size_t)l] = root_of_unity(l, fN);
-      for (int64_t h = 0; h < (fN >> 10); ++h) hi[(size_t)h] = root_of_unity(h << 10, fN);
-      const LineKernelMeta ml = make_meta(0, 1024, 32, 32, 1, 32, true, true, false, false, 0);
-      const PtrRef ta = b.line_tables(ml), tlo = b.add_table(lo), thi = b.add_table(hi);
-      { Step& z = b.push(ST_ZERO); z.p[0] = ctl; z.i[0] = 9216; z.grid = 1; }
-      Step& st = b.push(ST_XCD_FUSED);
-      st.variant = xm->id;
-      st.p[0] = in; st.p[1] = out; st.p[2] = wslots; st.p[3] = ctl; st.p[4] = PtrRef(BUF_TABLE, 0);
-      st.i[0] = B; st.i[1] = fN; st.i[2] = 10; st.i[3] = 1023; st.i[9] = fN;
+      Builder::XcdLaunch x = b.xcd_launch(*xm, false, 2 * fN, B);   // two slots per data line in a round (W and W2): Builder::xcd_groups
+      x.ta = x.tb = b.line_tables(make_meta(0, 1024, 32, 32, 1, 32, true, true, false, false, 0));
+      b.xcd_roots(x, fN);
+      Step& st = b.push_xcd(ST_XCD_FUSED, xm->id, x, in, out, B, fN);
       const bool kmajor = d.conv_output_layout == MI355FFT_KERNEL_MAJOR;
       st.i[10] = kmajor ? oN : K * oN;        // between data lines
       st.i[17] = kmajor ? B * oN : oN;        // between the kernels of one data line
-      st.i[4] = ta.off; st.i[5] = ta.off; st.i[6] = tlo.off; st.i[7] = thi.off; st.i[8] = split; st.i[11] = L; st.i[12] = 0; st.i[13] = b.opt.xcd_spin_limit;
-      st.i[14] = kf.off - wslots.off; st.i[15] = K; st.i[16] = d.conv_mode == MI355FFT_CORRELATION ? 1 : 0;
+      st.i[14] = kf.off - x.wslots.off; st.i[15] = K; st.i[16] = d.conv_mode == MI355FFT_CORRELATION ? 1 : 0;
       st.f[0] = (float)(1.0 / (double)fN);
-      st.grid = (unsigned)b.opt.compute_units;
       b.ir.route += "fftconv-pipeline[N=1024x1024,K=" + std::to_string(K) + "] ";
       return MI355FFT_OK;
     }

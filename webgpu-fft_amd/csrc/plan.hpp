@@ -54,48 +54,19 @@ struct ConvKernelMeta { int id, N, R0, R1, TL; };
 struct MixedCtMeta { int id, N, T, threads, lds_bytes; std::vector<int> radices; };
 const std::vector<MixedCtMeta>& mixedct_registry();
 
-// XCD-fused four-step kernels (kern_xcd.hpp): X(N1, R0a, R1a, R2a, Ta, N2, R0b, R1b, R2b, Tb); the tile widths are chosen so
-// that both passes use the same workgroup size; each is built forward and inverse.  (64 x 64 exists for the CPU
-// emulation tests.)  N = 2^15, 2^16, 2^17 (solo mode: one workgroup per transform), 2^18, 2^19, 2^20, 2^21 (the c2c half of
-// r2c/c2r N = 2^22).  2^22 = 2048 x 2048 (8-wide tiles on both
-// passes, 104 B of scratch) was built and measured slower than the two-launch route (104 vs 112 GPoints/s): not instantiated.
-#define MI355_XCD_KERNEL_LIST(X) \
-  X(64, 8, 8, 1, 16, 64, 8, 8, 1, 16) X(128, 16, 8, 1, 32, 256, 16, 16, 1, 16) X(256, 16, 16, 1, 16, 256, 16, 16, 1, 16) \
-  X(256, 16, 16, 1, 16, 512, 32, 16, 1, 16) X(512, 32, 16, 1, 16, 512, 32, 16, 1, 16) X(512, 32, 16, 1, 32, 1024, 32, 32, 1, 16) \
-  X(1024, 32, 32, 1, 16, 1024, 32, 32, 1, 16) X(1024, 32, 32, 1, 16, 2048, 32, 32, 2, 8)
-// (2^22 = 2048 x 2048 on LDS-resident 8-line tiles, re-measured in r03 with the one-slot grouping: 89-105 vs 159 GPoints/s for the register tiles: profiles/r03_regtile_ab.log)
-// (2^20 with 1024 threads and 16-point register stages — 16 waves per CU instead of 8, 128 VGPRs, 56 B of scratch — measured
-// 165-176 vs 186 GPoints/s: profiles/r02_xcd_2p21_orientation.log; not instantiated)
-// (2^21 as 2048 x 1024 — 64-byte segments on the input side instead of the output side — measured 138 vs 167 GPoints/s for
-// 1024 x 2048 and 189 vs 219 on config 5: profiles/r02_xcd_2p21_orientation.log; not instantiated)
-// r2c and c2r variants (kern_xcd_real.hpp), same parameters: a real line of N1*N2 points; r2c forward, c2r inverse.  2^12 (test instance), 2^15 .. 2^17 (solo mode), 2^18 .. 2^21.
-// (2^22 = 2048 x 2048 with 8-wide tiles on both passes was built and measured slower than the half-length route over the
-// fused c2c kernel — 153-163 vs 183 G real points/s — and is not instantiated.)
-#define MI355_XCD_R2C_KERNEL_LIST(X) \
-  X(64, 8, 8, 1, 16, 64, 8, 8, 1, 16) X(128, 16, 8, 1, 32, 256, 16, 16, 1, 16) X(256, 16, 16, 1, 16, 256, 16, 16, 1, 16) \
-  X(256, 16, 16, 1, 16, 512, 32, 16, 1, 16) X(512, 32, 16, 1, 16, 512, 32, 16, 1, 16) X(512, 32, 16, 1, 32, 1024, 32, 32, 1, 16) \
-  X(1024, 32, 32, 1, 16, 1024, 32, 32, 1, 16) X(1024, 32, 32, 1, 16, 2048, 32, 32, 2, 8)
-// c2r: 2^21 (1024 x 2048, 396 B of scratch per lane) measured 140 vs 215 G real points/s for the half-length route: not instantiated
-#define MI355_XCD_C2R_KERNEL_LIST(X) \
-  X(64, 8, 8, 1, 16, 64, 8, 8, 1, 16) X(128, 16, 8, 1, 32, 256, 16, 16, 1, 16) X(256, 16, 16, 1, 16, 256, 16, 16, 1, 16) \
-  X(256, 16, 16, 1, 16, 512, 32, 16, 1, 16) X(512, 32, 16, 1, 16, 512, 32, 16, 1, 16) X(512, 32, 16, 1, 32, 1024, 32, 32, 1, 16) \
-  X(1024, 32, 32, 1, 16, 1024, 32, 32, 1, 16)
-// 2-D c2c of an [N1][N0] array (axis 0 = N0 fastest): X(N1, radices, Ta, N0, radices, Tb) — columns of N1 (pass A), barrier,
-// rows of N0 with a ROW kernel (natural order out, no four-step roots); forward and inverse.  Tile widths chosen so that both
-// passes use the same workgroup size (256 threads for the 256/512 planes, 512 with a 1024 side)
-#define MI355_XCD_2D_KERNEL_LIST(X) \
-  X(256, 16, 16, 1, 16, 256, 16, 16, 1, 16) X(512, 32, 16, 1, 16, 512, 32, 16, 1, 16) X(1024, 32, 32, 1, 16, 1024, 32, 32, 1, 16) \
-  X(256, 16, 16, 1, 16, 512, 32, 16, 1, 16) X(512, 32, 16, 1, 16, 256, 16, 16, 1, 16) \
-  X(1024, 32, 32, 1, 16, 512, 32, 16, 1, 32) X(512, 32, 16, 1, 32, 1024, 32, 32, 1, 16)
-// register-tile instances (kern_regtile.hpp, r03): X(N1) — N = N1 x 2048 with the 2048-point side(s) on 16-line tiles held in
-// registers (128-byte segments where the LDS-resident 8-line tiles above move 64-byte ones); forward and inverse.  Listed AFTER
-// the LDS-resident instances of the same size so that a registry walk finds them last (PlannerOptions::xcd_rt).
-#define MI355_XCD_RT_KERNEL_LIST(X) X(1024) X(2048)
-// VIEW instantiations of the LDS-resident fused kernel (rank-1 ioView / zeroPad ranges as load / store predicates): 2^17, 2^18, 2^19, 2^21, forward and inverse
-// (2^20 has its own in kern_regtile.hpp).  Same parameters as MI355_XCD_KERNEL_LIST.
-#define MI355_XCD_VIEW_KERNEL_LIST(X) \
-  X(256, 16, 16, 1, 16, 512, 32, 16, 1, 16) X(512, 32, 16, 1, 16, 512, 32, 16, 1, 16) X(512, 32, 16, 1, 32, 1024, 32, 32, 1, 16) X(1024, 32, 32, 1, 16, 2048, 32, 32, 2, 8)
-struct XcdKernelMeta { int id, N1, N2, ra[3], rb[3], ta, tb; bool inverse; int threads, lds_bytes; int real; int rt; };   // real: 0 c2c, 1 r2c, 2 c2r, 3 two-dimensional c2c, 4 fftconv pipeline; rt: 1 register-tile instance (2048-point sides), 2 the two-workgroups-per-CU 1024 x 1024
+// XCD-fused four-step kernels: one entry per instance id, in id order (xcd_kernels.def, where the kinds are described)
+enum XcdKind : int {
+  XK_FUSED, XK_R2C, XK_C2R, XK_TWO_D, XK_VIEW,                 // LDS-resident passes (kern_xcd.hpp, kern_xcd_real.hpp)
+  XK_RT, XK_RT_R2C, XK_RT_C2R, XK_HX, XK_RT1K, XK_RT1K_16, XK_RT1K_VIEW, XK_RT1K_2048, XK_CONV   // register tiles (kern_regtile.hpp)
+};
+struct XcdInstance { XcdKind kind; int N1, ra[3], ta, N2, rb[3], tb; bool inverse; };
+constexpr XcdInstance XCD_INSTANCES[] = {
+#define XCD_KERNEL(KIND, N1, A0, A1, A2, TA, N2, B0, B1, B2, TB, INV) {XK_##KIND, N1, {A0, A1, A2}, TA, N2, {B0, B1, B2}, TB, INV},
+#include "xcd_kernels.def"
+#undef XCD_KERNEL
+};
+constexpr int XCD_INSTANCE_COUNT = (int)(sizeof XCD_INSTANCES / sizeof XCD_INSTANCES[0]);
+struct XcdKernelMeta : XcdInstance { int id, threads, lds_bytes; };   // + the launch shape (plan.cpp xcd_kernel_registry)
 const std::vector<XcdKernelMeta>& xcd_kernel_registry();
 const std::vector<ConvKernelMeta>& conv_kernel_registry();
 

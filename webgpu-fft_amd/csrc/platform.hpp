@@ -30,9 +30,11 @@
 #define MI_ACQUIRE_AGENT() do { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); } while (0)
 #define MI_SLEEP() __builtin_amdgcn_s_sleep(1)
 #else
+#include <chrono>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <thread>
 namespace emu {
 struct dim3_t { unsigned x = 1, y = 1, z = 1; };
 extern thread_local dim3_t t_threadIdx, t_blockIdx, t_blockDim, t_gridDim;
@@ -40,7 +42,6 @@ extern thread_local char* t_smem;
 extern unsigned g_xcds;   // emulated XCD count: block b reports XCC id b % g_xcds
 void sync_threads();
 void sync_wave();    // the 64 emulated threads of one wave (kern_xcd_res.hpp: waves of a workgroup wait on different counters)
-void yield_thread();
 }  // namespace emu
 #define __global__
 #define __device__
@@ -63,7 +64,9 @@ void yield_thread();
 #define MI_ATOMIC_OR_U32(p, v) __atomic_fetch_or((p), (v), __ATOMIC_SEQ_CST)
 #define MI_WAIT_VMEM() do { } while (0)
 #define MI_ACQUIRE_AGENT() __atomic_thread_fence(__ATOMIC_SEQ_CST)
-#define MI_SLEEP() emu::yield_thread()   /* bounded spins must outlast thread start-up of the other emulated blocks */
+// a poll of a bounded wait sleeps: the emulated blocks are thousands of host threads, and spin_limit bare yields could run out
+// while the other blocks are still starting or computing on a loaded host (a wait that gives up on correct code)
+#define MI_SLEEP() std::this_thread::sleep_for(std::chrono::microseconds(10))
 #define MI_WAVE_SYNC() emu::sync_threads() /* emulated waves are not lock-step: use the block barrier */
 #endif
 
