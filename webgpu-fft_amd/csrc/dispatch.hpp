@@ -175,6 +175,9 @@ template <int ONLY, class L> bool launch_xcd_sel(int id, const XcdFusedArgs& a, 
   } else if constexpr (k.kind == XK_CONV) {
     using F = Rt1kCfgT<k.tb>;
     l.launch_concurrent(fft_xcd_conv1m_kernel<k.N1>, grid, (unsigned)F::THREADS, (unsigned)F::LDS_BYTES, a);
+  } else if constexpr (k.kind == XK_CONV_VIEW) {
+    using F = Rt1kCfgT<k.tb>;
+    l.launch_concurrent(fft_xcd_conv1m_kernel<k.N1, true>, grid, (unsigned)F::THREADS, (unsigned)F::LDS_BYTES, a);
   } else {   // XK_RT1K, XK_RT1K_16, XK_RT1K_VIEW, XK_RT1K_2048: Tb-line register tiles along the 1024-point rows
     using F = Rt1kCfgT<k.tb>;
     constexpr unsigned smem = F::LDS_BYTES + (k.N1 == 2048 ? RtCfg::TW2_ELEMS * 8 : 0);   // (2048-point columns: their stage-2 roots too)
@@ -279,6 +282,7 @@ bool dispatch_step(const Step& s, void* const ptr[5], L& l, LinesFn&& lines_fn, 
       a.mul = a.conv_k ? (const cf*)((const char*)ptr[2] + s.i[14]) : nullptr;   // the kernel spectra sit in the same workspace arena as the slots
       a.v_in_lo = (int)s.imap.lo[0]; a.v_in_hi = (int)s.imap.hi[0]; a.v_out_lo = (int)s.omap.lo[0]; a.v_out_hi = (int)s.omap.hi[0];
       a.v_zlo = (int)s.omap.zlo[0]; a.v_zhi = (int)s.omap.zhi[0];   // (VIEW instances only; the planner fills the two maps)
+      a.v_split = (int)s.i[18]; a.v_shift = (int)s.i[19];              // (CONV_VIEW only)
       if (s.kind == ST_XCD_RES) return launch_xcd_res(s.variant, a, s.grid, l);
       return xcd_fn(s.variant, a, s.grid);
     }

@@ -931,7 +931,12 @@ __global__ void __launch_bounds__(Rt1kCfgT<T>::THREADS, 2) fft_xcd_rt1k_kernel(c
 // = 56 B/point for one kernel where forward, pointwise and inverse launches move 88 (and 40 instead of 56 for every further kernel).
 // Inverse passes run the forward arithmetic on re/im-swapped data (radix.hpp): the product is swapped before M_k's second half, the
 // result swapped back at C_k's store.  Group barriers: A | M_k, M_k | C_k, and C_k | M_k+1 when another kernel follows (W2 is reused).
-template <int N1_>
+// VIEW (the linear modes and zeroPad of a line of up to 2^20 points): the zero-padded embed of the data is a predicate of
+// phase A's loads (element i of the padded line is read inside [v_in_lo, v_in_hi) and is 0 elsewhere; in_pitch is the data's own length),
+// crop and zeroPad.write are predicates of phase C's stores.  Padded index kk belongs to logical index m = kk (kk < v_split) or kk - v_shift
+// (kk >= v_split + v_shift; correlation's negative lags at the top of the padded domain) and to none in between; y[m] is stored inside
+// [v_out_lo, v_out_hi), as 0 outside [v_zlo, v_zhi).  `out` carries the offset -v_out_lo.  Phase M and the barriers are the same code.
+template <int N1_, bool VIEW = false>
 __global__ void __launch_bounds__(Rt1kCfg::THREADS) fft_xcd_conv1m_kernel(const XcdFusedArgs f) {
   static_assert(N1_ == 1024, "1024 x 1024");
   MI_SMEM_DECL(smem);
@@ -944,10 +949,12 @@ __global__ void __launch_bounds__(Rt1kCfg::THREADS) fft_xcd_conv1m_kernel(const 
   const unsigned gslot = s_words[0], rank = s_words[1], gsize = s_words[2], gidx = s_words[4], groups = s_words[5];
   constexpr unsigned N1 = 1024, N2 = 1024, NT = 32;
   cf* const Wg = f.wslots + (size_t)(2u * (f.slots ? f.slots : 1u) * gslot) * (size_t)f.N;     // per group and line of a round: W and W2
-  const int cl = t & 31, h = t >> 5;        // column-side map
-  const int rl = t >> 4, hh = t & 15;       // row-side map
+  // column-side map cl = t & 31, h = t >> 5; row-side map rl = t >> 4, hh = t & 15: formed per tile (see `fresh`)
   const bool first = MI_UNIFORM_U32((unsigned)t >> 8) == 0u;   // 16-row tiles of phase M: consumers ku = t div 16 < 16 are served in the first exchange half
   const auto root = [&](unsigned m) { return cmul(f.tw_hi[m >> f.fs_shift], f.tw_lo[m & f.fs_lo_mask]); };
+  // VIEW: a lane index as a value defined where it is used.  The exchange's LDS addresses derive from it, so they are formed per tile: hoisted out of
+  // the line loop (the other instance: 88 bytes of scratch per lane) they do not fit in the registers next to the predicates.
+  const auto fresh = [&](int v) { if constexpr (VIEW) MI_OPAQUE_LANE_INT(v); return v; };
   const auto stage1 = [&](cf (&w)[32], int j2) {
     int ti = j2; MI_OPAQUE_LANE_INT(ti);
 #pragma unroll
@@ -955,7 +962,7 @@ __global__ void __launch_bounds__(Rt1kCfg::THREADS) fft_xcd_conv1m_kernel(const 
     fft_radix<32>(w);
   };
   // rows k1 = 32 tile + rl of a workspace slot, times the four-step roots e^{-2 pi i k1 n2/N}: this thread's elements n2 = 2hh (+1) + 32 q
-  const auto load_rows = [&](cf (&va)[32], cf (&vb)[32], const cf* S, unsigned tile) {
+  const auto load_rows = [&](cf (&va)[32], cf (&vb)[32], const cf* S, unsigned tile, int rl, int hh) {
     const unsigned k1 = tile * 32u + (unsigned)rl;
     const cf* p = S + (size_t)(tile * 32u) * N2;
     const unsigned lo = (unsigned)rl * N2 + 2u * (unsigned)hh;
@@ -976,6 +983,18 @@ __global__ void __launch_bounds__(Rt1kCfg::THREADS) fft_xcd_conv1m_kernel(const 
       }
     }
   };
+  // VIEW: the store predicates of phase C on the padded index, from the logical ranges (uniform; all zero otherwise).  The zeroPad.write range
+  // maps to ONE padded range: what lies between its two images belongs to no logical index and is never stored.
+  unsigned vs1 = 0, vn1 = 0, vs2 = 0, vn2 = 0, vz_lo = 0, vz_n = 0, vshift = 0;
+  if constexpr (VIEW) {
+    const int sp = f.v_split, sh = f.v_shift, lo = f.v_out_lo, hi = f.v_out_hi;
+    const int e1 = hi < sp ? hi : sp, b2 = lo > sp ? lo : sp;
+    const int zl = f.v_zlo < sp ? f.v_zlo : f.v_zlo + sh, zh = f.v_zhi <= sp ? f.v_zhi : f.v_zhi + sh;
+    vs1 = (unsigned)lo; vn1 = e1 > lo ? (unsigned)(e1 - lo) : 0u;
+    vs2 = (unsigned)(b2 + sh); vn2 = hi > b2 ? (unsigned)(hi - b2) : 0u;
+    vz_lo = (unsigned)zl; vz_n = zh > zl ? (unsigned)(zh - zl) : 0u;
+    vshift = (unsigned)sh;
+  }
   unsigned bar = 0;                                  // barriers passed so far (the counter is monotonic)
   const auto group_barrier = [&]() -> bool {
     xcd_arrive(&f.ctl->bar[gslot][0]);
@@ -992,14 +1011,29 @@ __global__ void __launch_bounds__(Rt1kCfg::THREADS) fft_xcd_conv1m_kernel(const 
       const unsigned ll = tt / NT, tile = tt - ll * NT;
       const cf* const x = f.in + (tr0 + ll) * f.in_pitch;
       cf* const W = Wg + (size_t)(2u * ll) * (size_t)f.N;
+      const int ta = fresh(t), cl = ta & 31, h = ta >> 5;
       cf va[32], vb[32], w[32];
       {
         const cf* p = x + tile * 32u;
         const unsigned voff = (unsigned)h * N2 + (unsigned)cl;
+        if constexpr (VIEW) {
+          // element (32 q (+16) + h) N2 + 32 tile + cl of the line: one lane value, the row term is a constant of the unrolled loop.
+          // A row group wholly outside the range issues its load with no lane enabled: nothing is fetched.
+          const unsigned rel = voff + tile * 32u - (unsigned)f.v_in_lo, span = (unsigned)(f.v_in_hi - f.v_in_lo);
 #pragma unroll
-        for (int q = 0; q < 32; ++q) {
-          va[q] = ld_stream<MI355_RT1K_NT_IN != 0>(sgpr_base(p + (unsigned)(32 * q) * N2) + voff);
-          vb[q] = ld_stream<MI355_RT1K_NT_IN != 0>(sgpr_base(p + (unsigned)(32 * q + 16) * N2) + voff);
+          for (int q = 0; q < 32; ++q) {
+            const cf* const pa = sgpr_base(p + (unsigned)(32 * q) * N2) + voff;
+            const cf* const pb = sgpr_base(p + (unsigned)(32 * q + 16) * N2) + voff;
+            va[q] = cf{0.0f, 0.0f}; vb[q] = cf{0.0f, 0.0f};
+            if (rel + (unsigned)(32 * q) * N2 < span) va[q] = ld_stream<MI355_RT1K_NT_IN != 0>(pa);
+            if (rel + (unsigned)(32 * q + 16) * N2 < span) vb[q] = ld_stream<MI355_RT1K_NT_IN != 0>(pb);
+          }
+        } else {
+#pragma unroll
+          for (int q = 0; q < 32; ++q) {
+            va[q] = ld_stream<MI355_RT1K_NT_IN != 0>(sgpr_base(p + (unsigned)(32 * q) * N2) + voff);
+            vb[q] = ld_stream<MI355_RT1K_NT_IN != 0>(sgpr_base(p + (unsigned)(32 * q + 16) * N2) + voff);
+          }
         }
       }
       fft_radix<32>(va);
@@ -1027,8 +1061,9 @@ __global__ void __launch_bounds__(Rt1kCfg::THREADS) fft_xcd_conv1m_kernel(const 
         const unsigned ll = tt / (2 * NT), tile = tt - ll * (2 * NT);
         const cf* const W = Wg + (size_t)(2u * ll) * (size_t)f.N;
         cf* const W2 = Wg + (size_t)(2u * ll + 1u) * (size_t)f.N;
-        const int ml = t >> 5, mu = t & 31;          // row-side map of a 16-row tile: row ml, elements n2 = mu + 32 q
-        const int kl = t & 15, ku = t >> 4;          // column-side map: row k1 = 16 tile + kl, butterfly ku
+        const int tm = fresh(t);
+        const int ml = tm >> 5, mu = tm & 31;        // row-side map of a 16-row tile: row ml, elements n2 = mu + 32 q
+        const int kl = tm & 15, ku = tm >> 4;        // column-side map: row k1 = 16 tile + kl, butterfly ku
         cf v[32], w[32];
         {
           const unsigned k1 = tile * 16u + (unsigned)ml;
@@ -1073,8 +1108,9 @@ __global__ void __launch_bounds__(Rt1kCfg::THREADS) fft_xcd_conv1m_kernel(const 
         const unsigned ll = tt / NT, tile = tt - ll * NT;
         cf* const y = f.out + (tr0 + ll) * f.out_pitch + (long long)kk * f.out_kernel_pitch;
         const cf* const W2 = Wg + (size_t)(2u * ll + 1u) * (size_t)f.N;
+        const int tc = fresh(t), cl = tc & 31, h = tc >> 5, rl = tc >> 4, hh = tc & 15;
         cf va[32], vb[32], w[32];
-        load_rows(va, vb, W2, tile);
+        load_rows(va, vb, W2, tile, rl, hh);
         fft_radix<32>(va);
         fft_radix<32>(vb);
         cf* const po = y + tile * 32u;
@@ -1083,9 +1119,25 @@ __global__ void __launch_bounds__(Rt1kCfg::THREADS) fft_xcd_conv1m_kernel(const 
 #pragma unroll
           for (int q = 0; q < 32; ++q) st_stream<MI355_RT1K_NT_OUT != 0>(sgpr_base(po + ((unsigned)(32 * q) + off) * N1) + so, (ww[q] * f.scale).yx);
         };
-        rt1k_exchange(va, vb, w, xb, rl, 2 * hh, 2 * hh + 1, cl, h, [&] { stage1(w, h); store(w, 0u); });
+        // VIEW: padded index ko = (32 q + off + h) N1 + 32 tile + cl.  The stored padded ranges are [vs1, vs1 + vn1) (m = ko) and [vs2, vs2 + vn2)
+        // (m = ko - shift): every base is taken `shift` elements low and the lanes of the first range add it back, so the lane offsets stay
+        // unsigned.  (always_inline: inlined late, the closure stays in private memory and its uniform fields come back in vector registers.)
+        const auto store_view = [&](cf (&ww)[32], unsigned off) __attribute__((always_inline)) {
+          const unsigned kb = so + tile * 32u;
+#pragma unroll
+          for (int q = 0; q < 32; ++q) {
+            const unsigned ko = kb + ((unsigned)(32 * q) + off) * N1;
+            cf r = (ww[q] * f.scale).yx;
+            if (ko - vz_lo >= vz_n) r = cf{0.0f, 0.0f};
+            const bool upper = ko - vs2 < vn2;
+            cf* const pe = sgpr_base(po + ((unsigned)(32 * q) + off) * N1 - vshift) + (upper ? so : so + vshift);
+            if (ko - vs1 < vn1 || upper) st_stream<MI355_RT1K_NT_OUT != 0>(pe, r);
+          }
+        };
+        const auto put = [&](cf (&ww)[32], unsigned off) __attribute__((always_inline)) { if constexpr (VIEW) store_view(ww, off); else store(ww, off); };
+        rt1k_exchange(va, vb, w, xb, rl, 2 * hh, 2 * hh + 1, cl, h, [&] { stage1(w, h); put(w, 0u); });
         stage1(w, h + 16);
-        store(w, 16u);
+        put(w, 16u);
         __syncthreads();
       }
       // W2 is rewritten by M_k+1 (a further kernel, which passes no other barrier first); the next data line's M_0 comes after its A | M barrier

@@ -82,6 +82,9 @@ struct XcdFusedArgs {
   // semantics of plan.hpp): element i of a line is read inside [v_in_lo, v_in_hi) and is 0 elsewhere; element k is stored inside
   // [v_out_lo, v_out_hi) only, as 0 outside [v_zlo, v_zhi).  `in` / `out` already carry the maps' offsets.
   int v_in_lo, v_in_hi, v_out_lo, v_out_hi, v_zlo, v_zhi;
+  // CONV_VIEW only (fftconv on a padded FFT domain): padded index k is logical index k below v_split, k - v_shift from v_split + v_shift on and
+  // none in between; the v_out_* / v_z* ranges above are logical
+  int v_split, v_shift;
 };
 
 // roots for one PASS_B tile, generated per tile: anchors by exact table lookup every 8th element, the 7 in between by

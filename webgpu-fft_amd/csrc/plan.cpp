@@ -155,6 +155,7 @@ PlannerOptions planner_options_from_env() {
   if (const char* s = std::getenv("MI355FFT_XCD_RT")) o.xcd_rt = std::atoi(s);
   if (const char* s = std::getenv("MI355FFT_XCD_HX")) o.xcd_hx = std::atoi(s);
   if (const char* s = std::getenv("MI355FFT_CONV_PIPELINE")) o.conv_pipeline = std::atoi(s);
+  if (const char* s = std::getenv("MI355FFT_CONV_PAD")) o.conv_pad = std::atoi(s);
   if (const char* s = std::getenv("MI355FFT_SOLO_MAX_KB")) { const int v = std::atoi(s); if (v >= 0) o.solo_max_kb = v; }
   if (const char* s = std::getenv("MI355FFT_SOLO_CAP_MB")) { const int v = std::atoi(s); if (v >= 1) o.solo_cap_mb = v; }
   if (const char* s = std::getenv("MI355FFT_XCD_SLOTS")) { const int v = std::atoi(s); if (v >= 0 && v <= 2) o.xcd_slots = v; }
@@ -319,7 +320,7 @@ struct Builder {
     if ((xm.kind == XK_RT_R2C || xm.kind == XK_RT_C2R) && xm.N1 == 2048 && opt.xcd_slots <= 0) { split = 2; return; }
     // fftconv pipeline, groups per XCD x data lines per round (two slots per line, W and W2), same box, GPoints/s (profiles/r03_fftconv_pipeline_ab.log):
     // 2 x 1 101-104 (8 x 2 x 2 x 8 MiB = the Infinity Cache), 1 x 2 95-97, 2 x 2 92-96, 1 x 1 87-89, 4 x 1 68; three launches 70-73
-    if (xm.kind == XK_CONV) { split = 2; return; }
+    if (xm.kind == XK_CONV || xm.kind == XK_CONV_VIEW) { split = 2; return; }
     split = 16;
     while (split > 1 && (uint64_t)(8 * slots * split) * slot_bytes > ((uint64_t)(two_slot_default ? 320 : 256) << 20)) split >>= 1;
   }
@@ -1677,6 +1678,23 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
   // transform before the crop (fftconv.js:386,542,565)
   if (int rv = validate_views(d, err, fs, fs)) return rv;
   const bool zpad = d.zero_read.enabled || d.zero_write.enabled;
+  // Long rank-1 linear modes: the result is cropped out of the FFT domain, so any domain of at least shape + kernelShape - 1 points gives
+  // the same values; the next power of two keeps the transforms off the Bluestein / mixed-radix routes.  Everything the caller states
+  // (zeroPad ranges, output shape and offset) stays on the logical domain [0, lfN).  Padded index k is logical index k below `split`
+  // and k - padD from split + padD on; the padD indices in between belong to no logical index.  Convolution: split = lfN (the padding
+  // is the tail).  Correlation conjugates the kernel spectra, so its kernelShape - 1 negative lags wrap to the TOP of the domain:
+  // split = shape.  pad_lo / pad_hi carry the start / the end of a logical range onto the padded domain.
+  const int64_t lfN = fs[0];
+  int64_t padD = 0;
+  if (b.opt.conv_pad && rank == 1 && d.conv_boundary != MI355FFT_CIRCULAR && lfN > 16384 && lfN <= ((int64_t)1 << 22) && !is_pow2(lfN)) {
+    int64_t P = 32768;
+    while (P < lfN) P <<= 1;
+    padD = P - lfN; fs[0] = P;
+    b.ir.route += "pad[" + std::to_string(lfN) + "->" + std::to_string(P) + "] ";
+  }
+  const int64_t split = d.conv_mode == MI355FFT_CORRELATION ? d.shape[0] : lfN;
+  const auto pad_lo = [&](int64_t m) { return m < split ? m : m + padD; };
+  const auto pad_hi = [&](int64_t e) { return e <= split ? e : e + padD; };
   const int64_t inN = prodv(d.shape, rank), kN = prodv(ks, rank), fN = prodv(fs, rank), oN = prodv(os, rank);
   PtrRef in(BUF_INPUT, 0), out(BUF_OUTPUT, 0), kern(BUF_KERNEL, 0);
   b.ir.kernel_bytes = (uint64_t)K * kN * 8;
@@ -1749,21 +1767,36 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
   if (rc) return rc;
   // 1b. 2^20-point circular lines, dense on both sides: forward transform, K products and K inverse transforms in ONE persistent launch
   // whose spectrum tiles never leave the registers (kern_regtile.hpp fft_xcd_conv1m_kernel): 56 + 40 (K - 1) B/point instead of 88 + 56 (K - 1)
+  // The linear modes (a padded or exact 2^20-point domain) and zeroPad take the kernel's VIEW form: the embed of the data is a predicate of its
+  // first loads, crop and zeroPad.write are predicates of its last stores (A reads 8 shape, C writes 8 os bytes per line and kernel)
   if (b.opt.conv_pipeline && !b.opt.force_generic && b.opt.xcd_fused == 1 && b.opt.xcd_shared && !b.opt.only_pass && rank == 1 && fN == ((int64_t)1 << 20) &&
-      d.conv_boundary == MI355FFT_CIRCULAR && !zpad && !d.input.strided && !d.output.strided) {
+      !d.input.strided && !d.output.strided) {
+    const bool view = d.conv_boundary != MI355FFT_CIRCULAR || zpad;
     const XcdKernelMeta* xm = nullptr;
-    for (const auto& m : xcd_kernel_registry()) if (m.kind == XK_CONV) xm = &m;
+    for (const auto& m : xcd_kernel_registry()) if (m.kind == (view ? XK_CONV_VIEW : XK_CONV)) xm = &m;
     if (xm) {
       Builder::XcdLaunch x = b.xcd_launch(*xm, false, 2 * fN, B);   // two slots per data line in a round (W and W2): Builder::xcd_groups
       x.ta = x.tb = b.line_tables(make_meta(0, 1024, 32, 32, 1, 32, true, true, false, false, 0));
       b.xcd_roots(x, fN);
-      Step& st = b.push_xcd(ST_XCD_FUSED, xm->id, x, in, out, B, fN);
+      Step& st = b.push_xcd(ST_XCD_FUSED, xm->id, x, in, view ? out.plus(-ooff[0] * 8) : out, B, fN);
       const bool kmajor = d.conv_output_layout == MI355FFT_KERNEL_MAJOR;
       st.i[10] = kmajor ? oN : K * oN;        // between data lines
       st.i[17] = kmajor ? B * oN : oN;        // between the kernels of one data line
       st.i[14] = kf.off - x.wslots.off; st.i[15] = K; st.i[16] = d.conv_mode == MI355FFT_CORRELATION ? 1 : 0;
       st.f[0] = (float)(1.0 / (double)fN);
-      b.ir.route += "fftconv-pipeline[N=1024x1024,K=" + std::to_string(K) + "] ";
+      if (view) {
+        st.i[9] = inN;                        // the data lines keep their own length: nothing is embedded
+        int64_t lo = 0, hi = d.shape[0];
+        if (d.zero_read.enabled) { lo = std::max(lo, d.zero_read.start[0]); hi = std::min(hi, d.zero_read.end[0]); }
+        if (hi < lo) hi = lo;
+        st.imap = st.omap = Builder::dense_map(fs, rank);
+        st.imap.lo[0] = (int)lo; st.imap.hi[0] = (int)hi;
+        st.omap.lo[0] = (int)ooff[0]; st.omap.hi[0] = (int)(ooff[0] + os[0]);      // logical, as the zeroPad.write range
+        st.omap.zlo[0] = d.zero_write.enabled ? (int)d.zero_write.start[0] : 0;
+        st.omap.zhi[0] = d.zero_write.enabled ? (int)d.zero_write.end[0] : (int)lfN;
+        st.i[18] = split; st.i[19] = padD;
+        b.ir.route += "fftconv-pipeline-view[N=1024x1024,K=" + std::to_string(K) + "] ";
+      } else b.ir.route += "fftconv-pipeline[N=1024x1024,K=" + std::to_string(K) + "] ";
       return MI355FFT_OK;
     }
   }
@@ -1810,7 +1843,21 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
   const float inv_n = (float)(1.0 / (double)fN);
   const bool direct_out = !embed && !d.output.strided;   // the inverse FFT can land in the output itself
   const bool side_out = embed || d.output.strided || d.zero_write.enabled || d.conv_output_layout != MI355FFT_KERNEL_MAJOR;
-  const bool fuse_out = side_out && map_inv;
+  const bool fuse_out = side_out && map_inv && padD == 0;
+  // padded domain: the zeroPad.write range as ONE padded range (what lies between its two images is never extracted), the crop from
+  // its padded offset — in two pieces where it holds both positive and negative lags of a correlation
+  mi355fft_zero_range zw = d.zero_write;
+  int64_t poff[8];
+  for (int i = 0; i < rank; ++i) poff[i] = ooff[i];
+  if (padD) { zw.start[0] = pad_lo(zw.start[0]); zw.end[0] = pad_hi(zw.end[0]); poff[0] = pad_lo(ooff[0]); }
+  const bool straddle = padD > 0 && ooff[0] < split && ooff[0] + os[0] > split;
+  const auto extract = [&](mi355fft_side_layout lay, int64_t extra) {
+    if (!straddle) { b.emit_strided(false, out, y, lay, os, rank, B, fs, poff, fN, extra); return; }
+    const int64_t n1 = split - ooff[0], n2 = os[0] - n1, o2 = split + padD;
+    if (lay.batch_stride_elements <= 0) lay.batch_stride_elements = oN;
+    b.emit_strided(false, out, y, lay, &n1, 1, B, fs, ooff, fN, extra);
+    b.emit_strided(false, out, y, lay, &n2, 1, B, fs, &o2, fN, extra + n1 * lay.strides[0]);
+  };
   for (int64_t k = 0; k < K; ++k) {
     if (mul_m) {
       Step& st = b.push(ST_LINES);
@@ -1855,10 +1902,10 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
     }
     rc = b.emit_nd(y, y, fs, rank, B, true, inv_n, err);
     if (rc) return rc;
-    if (d.zero_write.enabled) emit_zero_outside(b, y, d.zero_write, fs, rank, B);
+    if (d.zero_write.enabled) emit_zero_outside(b, y, zw, fs, rank, B);
     if (d.output.strided) {
       // lane of kernel k: outputOffset + k*kernelStride + b*batchStride (fftconv.js:868-871)
-      b.emit_strided(false, out, y, d.output, os, rank, B, fs, ooff, fN, k * kstride);
+      extract(d.output, k * kstride);
     } else {
       mi355fft_side_layout ol{};
       ol.strided = 1;
@@ -1866,7 +1913,7 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
       for (int i = 0; i < rank; ++i) { ol.strides[i] = st; st *= os[i]; }
       if (d.conv_output_layout == MI355FFT_KERNEL_MAJOR) { ol.offset_elements = k * B * oN; ol.batch_stride_elements = oN; }
       else { ol.offset_elements = k * oN; ol.batch_stride_elements = K * oN; }
-      b.emit_strided(false, out, y, ol, os, rank, B, fs, ooff, fN, 0);
+      extract(ol, 0);
     }
   }
   if (d.zero_write.enabled && !fuse_out) b.ir.route += "zero-write ";

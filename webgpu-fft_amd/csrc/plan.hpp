@@ -57,7 +57,7 @@ const std::vector<MixedCtMeta>& mixedct_registry();
 // XCD-fused four-step kernels: one entry per instance id, in id order (xcd_kernels.def, where the kinds are described)
 enum XcdKind : int {
   XK_FUSED, XK_R2C, XK_C2R, XK_TWO_D, XK_VIEW,                 // LDS-resident passes (kern_xcd.hpp, kern_xcd_real.hpp)
-  XK_RT, XK_RT_R2C, XK_RT_C2R, XK_HX, XK_RT1K, XK_RT1K_16, XK_RT1K_VIEW, XK_RT1K_2048, XK_CONV   // register tiles (kern_regtile.hpp)
+  XK_RT, XK_RT_R2C, XK_RT_C2R, XK_HX, XK_RT1K, XK_RT1K_16, XK_RT1K_VIEW, XK_RT1K_2048, XK_CONV, XK_CONV_VIEW   // register tiles (kern_regtile.hpp)
 };
 struct XcdInstance { XcdKind kind; int N1, ra[3], ta, N2, rb[3], tb; bool inverse; };
 constexpr XcdInstance XCD_INSTANCES[] = {
@@ -154,7 +154,9 @@ struct PlannerOptions {
   int mixed_lds_kb = 0;                // experiments: LDS per workgroup of the mixed-radix line kernel (0 = per-length rule)
   int mixed_threads = 256;
   int64_t conv_fused_max_points = (int64_t)1 << 20;   // fftconv-fused (one launch, latency route) up to this many points B*N*K; above: forward-mul + inverse line launches
-  int conv_pipeline = 1;               // fftconv of 2^20-point circular dense lines: forward, products and inverses in one persistent launch (kern_regtile.hpp fft_xcd_conv1m_kernel)
+  int conv_pipeline = 1;               // fftconv on a 2^20-point FFT domain, dense sides: forward, products and inverses in one persistent launch (kern_regtile.hpp fft_xcd_conv1m_kernel;
+                                       // the linear modes and zeroPad through its VIEW form); 0: the composed route
+  int conv_pad = 1;                    // fftconv, rank 1, linear modes with 16384 < shape + kernelShape - 1 <= 2^22: transform on the next power of two (0: the exact length)
   int conv_lines = 1;                  // fftconv: kernel-spectrum product fused behind the forward line FFT (1-D, power-of-two FFT length <= max_line)
   int trig_fused = 1;                  // dct2 / dst2 of dense lines (half length a line-kernel size): permutation + real FFT + phase in one launch
   int trig_real = 1;                   // dct2/dst2/dct3/dst3 along a dense even axis through a real FFT of length N (kern_trig.hpp)
