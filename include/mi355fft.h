@@ -41,7 +41,12 @@ typedef struct mi355fft_commands mi355fft_commands; /* replaces GPUCommandBuffer
 enum { MI355FFT_C2C = 0, MI355FFT_R2C = 1, MI355FFT_C2R = 2, MI355FFT_FFTCONV = 3,
        /* real-to-real transforms over real f32 buffers (runtime/plans/dct_fft.js; create_plan.js:15) */
        MI355FFT_DCT1 = 4, MI355FFT_DCT2 = 5, MI355FFT_DCT3 = 6, MI355FFT_DCT4 = 7,
-       MI355FFT_DST1 = 8, MI355FFT_DST2 = 9, MI355FFT_DST3 = 10, MI355FFT_DST4 = 11 };
+       MI355FFT_DST1 = 8, MI355FFT_DST2 = 9, MI355FFT_DST3 = 10, MI355FFT_DST4 = 11,
+       /* fftconv over real f32 data (host option: type "fftconv" with layout.interleavedComplex false).  Same descriptor fields as
+        * MI355FFT_FFTCONV; input, kernel buffer (kernelCount packed kernels of prod(kernelShape) f32) and output hold f32 reals, the
+        * side layouts and conv_output_kernel_stride_elements count f32 elements, exec offsets follow the real side of r2c plans.  The values are
+        * the real parts of what the complex plan returns for the same data with zero imaginary parts. */
+       MI355FFT_FFTCONV_REAL = 12 };
 /* opts.direction: forward = exp(-i...), inverse = exp(+i...) (kernels/stockham_stage.js:35) */
 enum { MI355FFT_FORWARD = 0, MI355FFT_INVERSE = 1 };
 /* opts.normalize (runtime/common.js:35-40): none -> 1, backward -> 1/N on inverse only, unitary -> 1/sqrt(N) */
@@ -96,7 +101,7 @@ typedef struct mi355fft_plan_desc {
   int64_t batch;                   /* >= 1 */
   mi355fft_side_layout input;
   mi355fft_side_layout output;
-  /* type == MI355FFT_FFTCONV only */
+  /* type == MI355FFT_FFTCONV and MI355FFT_FFTCONV_REAL only */
   int32_t conv_mode;
   int32_t conv_boundary;
   int32_t conv_kernel_count;       /* fftConv.kernelCount, >= 1 */

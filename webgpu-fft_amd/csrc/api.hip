@@ -368,7 +368,7 @@ MI_API int mi355fft_plan_exec(mi355fft_plan* plan, mi355fft_encoder* enc, const 
       return fail(MI355FFT_ERR_INVALID, "inputOffsetBytes/outputOffsetBytes must be multiples of 4 for precision \"f16-storage\"");
   } else if (args->input_offset_bytes % 8 || args->output_offset_bytes % 8 || args->kernel_offset_bytes % 8)
     return fail(MI355FFT_ERR_INVALID, "inputOffsetBytes/outputOffsetBytes must be multiples of 8");
-  if (d.type == MI355FFT_FFTCONV && !args->kernel) return fail(MI355FFT_ERR_INVALID, "fftconv exec requires kernel");
+  if ((d.type == MI355FFT_FFTCONV || d.type == MI355FFT_FFTCONV_REAL) && !args->kernel) return fail(MI355FFT_ERR_INVALID, "fftconv exec requires kernel");
   mi355fft_buffer* out = d.in_place ? args->input : args->output;
   const uint64_t out_off = d.in_place ? args->input_offset_bytes : args->output_offset_bytes;
   if (!d.in_place && d.type != MI355FFT_C2C && args->output->ptr == args->input->ptr)
@@ -379,7 +379,7 @@ MI_API int mi355fft_plan_exec(mi355fft_plan* plan, mi355fft_encoder* enc, const 
   if (out_off + plan->ir.out_bytes > out->bytes)
     return fail(MI355FFT_ERR_INVALID, "output buffer/view too small: need %llu bytes at offset %llu, have %llu", (unsigned long long)plan->ir.out_bytes,
                 (unsigned long long)out_off, (unsigned long long)out->bytes);
-  if (d.type == MI355FFT_FFTCONV && args->kernel_offset_bytes + plan->ir.kernel_bytes > args->kernel->bytes)
+  if ((d.type == MI355FFT_FFTCONV || d.type == MI355FFT_FFTCONV_REAL) && args->kernel_offset_bytes + plan->ir.kernel_bytes > args->kernel->bytes)
     return fail(MI355FFT_ERR_INVALID, "kernel buffer too small: need %llu bytes, have %llu", (unsigned long long)plan->ir.kernel_bytes,
                 (unsigned long long)args->kernel->bytes);
   // workspace: caller's temp when it is big enough and does not alias input/output, else the plan's arena

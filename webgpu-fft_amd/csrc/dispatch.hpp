@@ -29,6 +29,19 @@ namespace mi355 {
 enum : int { FAM_ROW_SMALL = 0, FAM_ROW_1K = 1, FAM_ROW_BIG = 2, FAM_PASS_A = 3, FAM_PASS_B = 4, FAM_COUNT = 5 };
 constexpr int row_family(int N) { return N <= 256 ? FAM_ROW_SMALL : (N <= 1024 ? FAM_ROW_1K : FAM_ROW_BIG); }
 
+// real fftconv line kernel (kern_lines.hpp fft_lines_rconv_kernel) on a forward ROW configuration.  Its instances are built in a
+// translation unit of their own (lines_rconv.hip) in the product build: kernels compiled together change each other's register
+// allocation, and the family units' device code stays what it was
+template <class C, class L> bool launch_lines_rconv(const LineArgs& a, unsigned grid, L& l);
+#if defined(MI355_RCONV_DEFINE_INSTANCES) || defined(MI355_HOST_EMU)
+template <class C, class L> bool launch_lines_rconv(const LineArgs& a, unsigned grid, L& l) {
+  if constexpr (!C::IN_COL && !C::OUT_COL && !C::SWAP_IN && !C::SWAP_OUT && C::TWID == TWID_NONE && C::NSTAGES >= 2) {
+    l.launch(fft_lines_rconv_kernel<C>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a);
+    return true;
+  } else return false;
+}
+#endif
+
 template <int FAMILY, class L>
 bool launch_lines_family(int id, const LineArgs& a, unsigned grid, L& l) {
   int cur = 0;
@@ -55,6 +68,7 @@ bool launch_lines_family(int id, const LineArgs& a, unsigned grid, L& l) {
           l.launch(fft_lines_r2c_kernel<C, true>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a); \
           return true;                                                                   \
         }                                                                                \
+        if (a.real_mode == 9) return launch_lines_rconv<C>(a, grid, l);                   \
         if (a.real_mode == 4) {                                                          \
           if (a.mapped) l.launch(fft_lines_mul_kernel<C, true>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a); \
           else l.launch(fft_lines_mul_kernel<C>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a); \
@@ -296,6 +310,9 @@ bool dispatch_step(const Step& s, void* const ptr[5], L& l, LinesFn&& lines_fn, 
       if (a.mapped) { a.imap = s.imap; a.omap = s.omap; }
       a.h16 = (int)s.i[11];
       a.scale = s.f[0];
+      if (a.real_mode == 9) {   // real fftconv line: p[4] (tw_hi) is the packed kernel spectrum; the HI roots sit directly behind the 1024 LO roots (one table)
+        a.v_out_lo = (int)s.i[12]; a.v_in_lo = (int)s.i[13]; a.v_in_hi = (int)s.i[14];
+      }
       const LineKernelMeta& m = line_kernel_registry()[(size_t)s.variant];
       return lines_fn(family_of_line_kernel(m), s.variant, a, s.grid);
     }

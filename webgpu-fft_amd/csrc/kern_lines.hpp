@@ -100,6 +100,8 @@ struct LineArgs {
   int fs_shift;
   unsigned fs_lo_mask;
   int real_mode;         // 4: fft_lines_mul_kernel (tw_lo = kernel spectrum, fs_shift != 0: conjugate it);  1: fft_lines_r2c_kernel (real line read as complex pairs, split fused behind the last stage); 2: fft_lines_c2r_kernel
+                         // 9: fft_lines_rconv_kernel (real fftconv line: r2c, product, c2r in one launch; tw_hi = the packed kernel spectrum, H + 1 bins, and the HI roots sit behind the
+                         //    1024 LO roots at tw_lo + 1024; v_in_lo = split, v_in_hi = padD of the padded-domain index map, v_out_lo != 0: conjugate the spectrum)
   long long fs_group;    // TWID_FOURSTEP_IN: lines per group (line index inside the group = G % fs_group); COL_RAGGED: tiles per group
   int v_in_lo, v_in_hi, v_out_lo, v_out_hi, v_zlo, v_zhi;   // VIEW instantiations of stage_read / stage_compute_write (kern_xcd.hpp fused kernels): rank-1 ranges of a four-step line
   int mapped;            // fft_lines_mapped_kernel: both sides go through imap / omap (in / out are the buffers' bases)
@@ -879,6 +881,203 @@ __global__ void __launch_bounds__(C::THREADS) fft_lines_mul_kernel(const LineArg
       lines_sync<C>();
       stage_compute_write<C, 2, false, false, true>(v, a, tile, t, lds, tw_lds, hk);
     }
+  }
+}
+
+// Real fftconv line (type MI355FFT_FFTCONV_REAL, route lines-rconv): r2c, product with one packed kernel spectrum and c2r of real lines
+// of P = 2H points without leaving LDS — 4 B read and 4 B written per real point and kernel where the composed route (r2c launch,
+// pointwise pass over the packed bins, c2r launch) moves about 20.  C is the forward ROW configuration of the half length H; the
+// inverse stages run on the same configuration through the re/im swap (IFFT z = swap FFT swap z).
+//   load    : the r2c MAPPED head — z[n] = x[2n] + i x[2n+1] through a.imap, zeros outside its [lo, hi) (embed + zeroPad.read)
+//   forward : the ROW stages, finished half-length spectrum Z kept in its LDS slot
+//   pairs   : one lane per pair (k, H-k), in the slot: split (X[k] = E + wO, X[H-k] = conj(E - wO)), product with G[k], G[H-k]
+//             (a.tw_hi, conjugated when correlating; the imaginary parts of bins 0 and H are ignored as in c2r), pre-split of the
+//             inverse (Z'[k] = E' + iO', Z'[H-k] = conj E' + i conj O'); roots w = e^{-2 pi i k/P} = HI[k >> 10] LO[k & 1023] (a.tw_lo: 1024 LO
+//             factors, the HI factors behind them) serve both.  A pair belongs to one lane, which reads all pairs of a batch before it
+//             rewrites any (as the c2r RAW head does).  Spectrum and roots are the same for every tile but are loaded per tile (cache
+//             hits): kept in registers across the stages they cost the stages theirs (16384-point lines: 395 registers spilled)
+//   inverse : the same stages on the swapped slot, finished line kept in LDS as swapped pairs (x[2n+1], x[2n])
+//   store   : sweep through a.omap: padded index k is logical index m = k below `split` and k - padD from split + padD on (the padD
+//             indices between belong to no logical index: plan.cpp build_fftconv); stored at m inside the crop [lo, hi), as 0
+//             outside the zeroPad.write range [zlo, zhi); scale 1/P in a.scale
+template <class C>
+__global__ void __launch_bounds__(C::THREADS, C::THREADS == 256 && C::T == 1 ? 2 : 1) fft_lines_rconv_kernel(const LineArgs a) {   // (one-line 256-thread workgroups: two to a CU, as the r2c / c2r kernels)
+  static_assert(!C::IN_COL && !C::OUT_COL && !C::SWAP_IN && !C::SWAP_OUT && C::TWID == TWID_NONE && C::NSTAGES >= 2, "forward ROW configuration with an LDS line buffer");
+  MI_SMEM_DECL(smem);
+  cf* lds = reinterpret_cast<cf*>(smem);
+  cf* tw_lds = lds + C::DATA_ELEMS;
+  const int t = threadIdx.x;
+  if constexpr (C::TW_LDS_ELEMS > 0) {
+    for (int i = t; i < C::TW_LDS_ELEMS; i += C::THREADS) tw_lds[i] = a.tw[i];
+    __syncthreads();
+  }
+  constexpr int H = C::N;
+  constexpr int NP = (H / 2) / C::TPL;          // pairs per lane (k = pu + TPL i < H/2); lane 0 of a line takes the self-mirrored bin H/2 too
+  constexpr int PB = NP > 4 ? 4 : NP;           // pairs per batch: six complex registers each
+  static_assert((H / 2) % C::TPL == 0 && NP % PB == 0, "the pairs of a line are dealt out in whole strides");
+  using I0 = StageInfo<C, 0>;
+  const int pl = t / C::TPL, pu = t % C::TPL;   // pair step and store sweep: a thread stays on one line
+  const int split = a.v_in_lo, padD = a.v_in_hi;
+  const bool conj = a.v_out_lo != 0;
+  const float* xin = reinterpret_cast<const float*>(a.in);
+  float* y = reinterpret_cast<float*>(a.out);
+  for (long long tile = blockIdx.x; tile < a.num_tiles; tile += gridDim.x) {
+    cf v[C::E];
+    {
+      const SideMap& im = a.imap;
+      int line, u; thread_map<C, 0>(t, line, u);
+      long long base = 0; bool zero;
+      const bool ok = side_line(im, tile * C::T + line, a.num_lines, base, zero);
+      const long long sa = im.stride[im.ax];
+      const int lo = im.lo[im.ax], hi = im.hi[im.ax];
+      // unit stride and an even base: z[n] is one 8-byte load wherever both of its samples lie inside [lo, hi).  Whatever is left (a
+      // sample pair cut by lo or hi, strided lanes, odd bases) is fetched by the lanes that need it in a rolled loop that parks the
+      // values in the lane's own LDS slots: unrolled beside the first sweep, its two 4-byte loads per element and their addresses cost
+      // every instance 60-90 registers
+#ifndef MI355_HOST_EMU
+      // one line per workgroup: its base is the same in every lane; saying so keeps it in scalar registers and the loads on 32-bit lane offsets
+      if constexpr (C::T == 1) base = (long long)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(base >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)base));
+#endif
+      const bool pairs = ok && sa == 1 && (base & 1) == 0;
+      const cf* xp = reinterpret_cast<const cf*>(xin + base);
+      bool rest = false;
+#pragma unroll
+      for (int b = 0; b < I0::NB; ++b) {
+#pragma unroll
+        for (int q = 0; q < I0::R; ++q) {
+          const int n = u + b * C::TPL + q * (H / I0::R), j = 2 * n;     // z[n] = x[2n] + i x[2n+1]
+          cf x = {0.0f, 0.0f};
+          if (pairs && j >= lo && j + 1 < hi) x = xp[n];
+          else rest = rest || (ok && j + 1 >= lo && j < hi);
+          v[b * I0::R + q] = x;
+        }
+      }
+      if (rest) {
+        const bool whole = !pairs;      // every element of this lane's
+#pragma unroll 4
+        for (int e = 0; e < C::E; ++e) {
+          const int n = u + (e / I0::R) * C::TPL + (e % I0::R) * (H / I0::R), j = 2 * n;
+          cf x = {0.0f, 0.0f};
+          if (whole || j < lo || j + 1 >= hi) {
+            if (j >= lo && j < hi) x.x = xin[base + (long long)j * sa];
+            if (j + 1 >= lo && j + 1 < hi) x.y = xin[base + (long long)(j + 1) * sa];
+          }
+          lds[lds_index<C>(line, n)] = x;
+        }
+#pragma unroll
+        for (int b = 0; b < I0::NB; ++b) {
+#pragma unroll
+          for (int q = 0; q < I0::R; ++q) {
+            const int n = u + b * C::TPL + q * (H / I0::R), j = 2 * n;
+            if (whole || j < lo || j + 1 >= hi) v[b * I0::R + q] = lds[lds_index<C>(line, n)];
+          }
+        }
+      }
+    }
+    __syncthreads();      // (the parked values are read before stage 0 of another lane overwrites the slots)
+    stage_compute_write<C, 0>(v, a, tile, t, lds, tw_lds, nullptr);
+    __syncthreads();
+    stage_read<C, 1>(v, a, tile, t, lds);
+    __syncthreads();
+    stage_compute_write<C, 1, false, true>(v, a, tile, t, lds, tw_lds, nullptr);
+    if constexpr (C::NSTAGES == 3) {
+      __syncthreads();
+      stage_read<C, 2>(v, a, tile, t, lds);
+      __syncthreads();
+      stage_compute_write<C, 2, false, true>(v, a, tile, t, lds, tw_lds, nullptr);
+    }
+    __syncthreads();
+    {
+      // split, product and pre-split of one pair; zk = Z[k], zm = Z[H-k]
+      const auto pair = [&](cf zk, cf zm, cf g0, cf g1, cf w, int k) {
+        const cf zmc = {zm.x, -zm.y};
+        const cf e = (zk + zmc) * 0.5f;
+        const cf wo = cmul(w, mul_neg_i((zk - zmc) * 0.5f));
+        const cf xk = e + wo;
+        cf xm = e - wo;
+        xm.y = -xm.y;
+        if (conj) { g0.y = -g0.y; g1.y = -g1.y; }
+        if (k == 0) { g0.y = 0.0f; g1.y = 0.0f; }           // bins 0 and H are real
+        const cf yk = cmul(xk, g0), ym = cmul(xm, g1);
+        const cf mc = {ym.x, -ym.y};
+        const cf e2 = yk + mc;
+        const cf o2 = cmul_conj(yk - mc, w);
+        lds[lds_index<C>(pl, k)] = e2 + mul_pos_i(o2);
+        if (k != 0 && H - k != k) { const cf ec = {e2.x, -e2.y}, oc = {o2.x, -o2.y}; lds[lds_index<C>(pl, H - k)] = ec + mul_pos_i(oc); }
+      };
+      int toff = 0;
+#ifndef MI355_HOST_EMU
+      asm volatile("" : "+s"(toff));     // opaque zero, per tile: the loads below stay in the tile loop
+#endif
+      const cf* mul = a.tw_hi + toff;
+      const cf* lo = a.tw_lo + toff;
+      const cf* hi = lo + 1024;
+#pragma unroll 1
+      for (int i0 = 0; i0 < NP; i0 += PB) {
+        cf g0[PB], g1[PB], wh[PB], wl[PB], zk[PB], zm[PB];
+#pragma unroll
+        for (int i = 0; i < PB; ++i) {
+          const int k = pu + (i0 + i) * C::TPL;
+          g0[i] = mul[k]; g1[i] = mul[H - k];
+          wh[i] = hi[(unsigned)k >> a.fs_shift]; wl[i] = lo[(unsigned)k & a.fs_lo_mask];
+        }
+#pragma unroll
+        for (int i = 0; i < PB; ++i) {
+          const int k = pu + (i0 + i) * C::TPL;
+          zk[i] = lds[lds_index<C>(pl, k)]; zm[i] = lds[lds_index<C>(pl, k == 0 ? 0 : H - k)];
+        }
+#pragma unroll
+        for (int i = 0; i < PB; ++i) pair(zk[i], zm[i], g0[i], g1[i], cmul(wh[i], wl[i]), pu + (i0 + i) * C::TPL);
+      }
+      if (pu == 0) {
+        const cf zh = lds[lds_index<C>(pl, H / 2)], gh = mul[H / 2];
+        pair(zh, zh, gh, gh, cmul(hi[(unsigned)(H / 2) >> a.fs_shift], lo[(unsigned)(H / 2) & a.fs_lo_mask]), H / 2);
+      }
+    }
+    __syncthreads();
+    {
+      int line, u; thread_map<C, 0>(t, line, u);
+#pragma unroll
+      for (int b = 0; b < I0::NB; ++b) {
+#pragma unroll
+        for (int q = 0; q < I0::R; ++q) v[b * I0::R + q] = cswap_if<true>(lds[lds_index<C>(line, u + b * C::TPL + q * (H / I0::R))]);
+      }
+    }
+    __syncthreads();   // everyone has its inputs before stage 0 re-uses the buffer
+    stage_compute_write<C, 0>(v, a, tile, t, lds, tw_lds, nullptr);
+    __syncthreads();
+    stage_read<C, 1>(v, a, tile, t, lds);
+    __syncthreads();
+    stage_compute_write<C, 1, false, true>(v, a, tile, t, lds, tw_lds, nullptr);
+    if constexpr (C::NSTAGES == 3) {
+      __syncthreads();
+      stage_read<C, 2>(v, a, tile, t, lds);
+      __syncthreads();
+      stage_compute_write<C, 2, false, true>(v, a, tile, t, lds, tw_lds, nullptr);
+    }
+    __syncthreads();
+    {
+      const SideMap& om = a.omap;
+      long long base = 0; bool zero;
+      if (side_line(om, tile * C::T + pl, a.num_lines, base, zero)) {
+        const long long so = om.stride[om.ax];
+        const int slo = om.lo[om.ax], shi = om.hi[om.ax], zlo = om.zlo[om.ax], zhi = om.zhi[om.ax];
+        for (int idx = pu; idx < H; idx += C::TPL) {
+          const cf r = lds[lds_index<C>(pl, idx)] * a.scale;      // (x[2 idx + 1], x[2 idx])
+          const int j = 2 * idx;
+          // padded -> logical: -1 for the indices that belong to no logical index
+          const int m0 = j < split ? j : (j >= split + padD ? j - padD : -1);
+          const int m1 = j + 1 < split ? j + 1 : (j + 1 >= split + padD ? j + 1 - padD : -1);
+          const float y0 = (zero || m0 < zlo || m0 >= zhi) ? 0.0f : r.y, y1 = (zero || m1 < zlo || m1 >= zhi) ? 0.0f : r.x;
+          if (so == 1 && m1 == m0 + 1 && m0 >= slo && m1 < shi && ((base + m0) & 1) == 0) *reinterpret_cast<cf*>(y + base + m0) = cf{y0, y1};   // one 8-byte store
+          else {
+            if (m0 >= slo && m0 < shi) y[base + (long long)m0 * so] = y0;
+            if (m1 >= slo && m1 < shi) y[base + (long long)m1 * so] = y1;
+          }
+        }
+      }
+    }
+    __syncthreads();   // LDS is re-used by the next tile
   }
 }
 

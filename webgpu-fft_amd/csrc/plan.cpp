@@ -156,6 +156,7 @@ PlannerOptions planner_options_from_env() {
   if (const char* s = std::getenv("MI355FFT_XCD_HX")) o.xcd_hx = std::atoi(s);
   if (const char* s = std::getenv("MI355FFT_CONV_PIPELINE")) o.conv_pipeline = std::atoi(s);
   if (const char* s = std::getenv("MI355FFT_CONV_PAD")) o.conv_pad = std::atoi(s);
+  if (const char* s = std::getenv("MI355FFT_RCONV_FUSED")) o.rconv_fused = std::atoi(s);
   if (const char* s = std::getenv("MI355FFT_SOLO_MAX_KB")) { const int v = std::atoi(s); if (v >= 0) o.solo_max_kb = v; }
   if (const char* s = std::getenv("MI355FFT_SOLO_CAP_MB")) { const int v = std::atoi(s); if (v >= 1) o.solo_cap_mb = v; }
   if (const char* s = std::getenv("MI355FFT_XCD_SLOTS")) { const int v = std::atoi(s); if (v >= 0 && v <= 2) o.xcd_slots = v; }
@@ -1921,10 +1922,249 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
   return MI355FFT_OK;
 }
 
+// ---- fftconv over real data (type MI355FFT_FFTCONV_REAL) ------------------------------------------------------------------------
+// Signals, kernels and results are f32 reals; the values are the real parts of what build_fftconv's plan returns for the same data
+// with zero imaginary parts.  Every option keeps its meaning; side layouts and the kernel stride count f32 elements.  Three routes:
+//   lines-rconv[N=P]  rank 1, FFT length P a power of two, 128 <= P <= 8192 by default (16384 and 32768 with strided sides or MI355FFT_RCONV_FUSED=2) (circular: P = shape; linear modes: the next power of two
+//                     >= max(shape + kernelShape - 1, 128) — a linear result is cropped, so any P >= that length is legal): one
+//                     lines-r2c-mapped launch writes the K packed kernel spectra, then ONE launch per kernel does r2c, product and c2r
+//                     of a data line inside LDS (kern_lines.hpp fft_lines_rconv_kernel).  Strided lanes, the embed, zeroPad and the
+//                     crop ride its two address maps: 4 B read + 4 B written per real point and kernel, 1 + K launches
+//   rconv[K]          everything else whose axis-0 FFT length can be made even (all linear requests: axis 0 is rounded up — rank 1 to
+//                     the next power of two up to 2^22; circular requests with even shape[0]); any rank; dense sides: the real
+//                     emitters on kernels and data, then per kernel a pointwise pass over the packed bins, the inverse, zeroPad.write
+//                     and the real crop
+//   rconv-widened     circular with odd shape[0] (no even domain is allowed): the complex plan between widening / narrowing passes
+// The padded-domain index map (split, padD) is build_fftconv's, on axis 0.
+int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
+  if (d.io_input.enabled || d.io_output.enabled) { err = "ioView is not an fftconv option"; return MI355FFT_ERR_INVALID; }
+  if (d.in_place) { err = "fftconv inPlace=true is not supported in current implementation"; return MI355FFT_ERR_INVALID; }
+  if (d.conv_mode != MI355FFT_CONVOLUTION && d.conv_mode != MI355FFT_CORRELATION) { err = "fftConv.mode must be one of \"convolution\", \"correlation\""; return MI355FFT_ERR_INVALID; }
+  if (d.conv_boundary < 0 || d.conv_boundary > 3) { err = "fftConv.boundary must be one of \"circular\", \"linear-full\", \"linear-same\", \"linear-valid\""; return MI355FFT_ERR_INVALID; }
+  if (d.conv_kernel_count <= 0) { err = "fftConv.kernelCount must be a positive integer; got " + std::to_string(d.conv_kernel_count); return MI355FFT_ERR_INVALID; }
+  const int rank = d.rank;
+  const int64_t K = d.conv_kernel_count, B = d.batch;
+  const bool linear = d.conv_boundary != MI355FFT_CIRCULAR, corr = d.conv_mode == MI355FFT_CORRELATION;
+  int64_t ks[8], fs[8], os[8], ooff[8], zero[8] = {0};
+  bool ks_given = false;
+  for (int i = 0; i < rank; ++i) if (d.conv_kernel_shape[i] != 0) ks_given = true;
+  for (int i = 0; i < rank; ++i) {
+    ks[i] = ks_given ? d.conv_kernel_shape[i] : d.shape[i];
+    if (ks[i] <= 0) { err = "fftConv.kernelShape must be an array of " + std::to_string(rank) + " positive ints"; return MI355FFT_ERR_INVALID; }
+    if (!linear) {
+      if (ks[i] > d.shape[i]) { err = "fftConv.kernelShape[" + std::to_string(i) + "] must be <= shape[" + std::to_string(i) + "] when fftConv.boundary=\"circular\""; return MI355FFT_ERR_INVALID; }
+      fs[i] = d.shape[i]; os[i] = d.shape[i]; ooff[i] = 0;
+    } else {
+      fs[i] = d.shape[i] + ks[i] - 1;
+      if (d.conv_boundary == MI355FFT_LINEAR_FULL) { os[i] = fs[i]; ooff[i] = 0; }
+      else if (d.conv_boundary == MI355FFT_LINEAR_SAME) { os[i] = d.shape[i]; ooff[i] = (ks[i] - 1) / 2; }
+      else {
+        os[i] = d.shape[i] - ks[i] + 1; ooff[i] = ks[i] - 1;
+        if (os[i] <= 0) { err = "fftConv.boundary=\"linear-valid\" requires kernelShape[" + std::to_string(i) + "] <= shape[" + std::to_string(i) + "]"; return MI355FFT_ERR_INVALID; }
+      }
+    }
+  }
+  if (int rv = validate_views(d, err, fs, fs)) return rv;
+  const int64_t lfN = fs[0];
+  const int64_t inN = prodv(d.shape, rank), kN = prodv(ks, rank), oN = prodv(os, rank);
+  const int64_t kstride = d.conv_output_kernel_stride_elements;
+  const bool strided = d.input.strided || d.output.strided;
+  const PtrRef in(BUF_INPUT, 0), out(BUF_OUTPUT, 0), kern(BUF_KERNEL, 0);
+  if (d.output.strided && K > 1 && kstride <= 0) { err = "multi-kernel strided output requires fftConv.channelPolicy.output or fftConv.outputKernelStrideElements"; return MI355FFT_ERR_INVALID; }
+  b.ir.kernel_bytes = (uint64_t)K * kN * 4;
+  b.ir.in_bytes = d.input.strided ? strided_extent_elems(d.input, d.shape, rank, B, 0) * 4 : (uint64_t)inN * B * 4;
+  b.ir.out_bytes = d.output.strided ? strided_extent_elems(d.output, os, rank, B, (K - 1) * kstride) * 4 : (uint64_t)K * B * oN * 4;
+  const int64_t split = corr ? d.shape[0] : lfN;
+
+  // ---- route 1: one launch per kernel on the line kernels --------------------------------------------------------------------
+  int64_t P1 = 0;
+  if (rank == 1 && !linear) { if (is_pow2(lfN) && lfN >= 128 && lfN <= 32768) P1 = lfN; }
+  else if (rank == 1 && lfN <= 32768) { P1 = 128; while (P1 < lfN) P1 <<= 1; }
+  // measured (profiles/fftconv_real_ab.log): the one-launch route is ahead of rconv[K] up to P = 8192 (1.3-1.9x at K = 1, 1.0-1.5x at K = 4); at
+  // P = 16384 and 32768 it ties at K = 1 and loses at K = 4 (0.75x: 40 registers spilt, one or two workgroups per CU running the stages twice
+  // behind barriers), so those lengths take rconv[K] unless a side is strided (only the line route's address maps carry lanes) or the
+  // switch is 2 (every length: tests and measurement)
+  const bool route1 = b.opt.rconv_fused == 2 || (b.opt.rconv_fused == 1 && (P1 <= 8192 || strided));
+  const LineKernelMeta* rm = (P1 && route1) ? b.lines_r2c_kernel(P1, false, true) : nullptr;
+  if (rm) {
+    const int64_t P = P1, H = P / 2, padD = P - lfN;
+    if (padD) b.ir.route += "pad[" + std::to_string(lfN) + "->" + std::to_string(P) + "] ";
+    const int64_t pf[1] = {P}, pp[1] = {H + 1};
+    // the K kernels, zero-embedded kN -> P by the load predicate, as packed spectra in the workspace
+    const PtrRef G = b.alloc_work((uint64_t)K * (H + 1) * 8);
+    SideMap km = Builder::dense_map(pf, 1), gm = Builder::dense_map(pp, 1);
+    km.hi[0] = (int)ks[0]; km.batch_stride = kN;
+    if (!b.emit_lines_r2c(kern, G, P, K, 1.0f, false, 0, &km, &gm)) { err = "no mapped r2c line kernel"; return MI355FFT_ERR_UNSUPPORTED; }
+    const PtrRef tables = b.line_tables(*rm);
+    // e^{-2 pi i k/P} = HI[k >> 10] LO[k & 1023], the HI factors directly behind the 1024 LO factors (one table: dispatch.hpp)
+    std::vector<float2h> roots(1024 + (size_t)std::max<int64_t>(1, (H + 1023) >> 10));
+    for (int64_t l = 0; l < 1024; ++l) roots[(size_t)l] = root_of_unity(l, P);
+    for (size_t h = 1024; h < roots.size(); ++h) roots[h] = root_of_unity((int64_t)(h - 1024) << 10, P);
+    const PtrRef proots = b.add_table(roots);
+    SideMap xm = Builder::dense_map(pf, 1);
+    {
+      int64_t lo = 0, hi = d.shape[0];
+      if (d.zero_read.enabled) { lo = std::max(lo, d.zero_read.start[0]); hi = std::min(hi, d.zero_read.end[0]); }
+      if (hi < lo) hi = lo;
+      xm.lo[0] = (int)lo; xm.hi[0] = (int)hi;
+      xm.stride[0] = d.input.strided ? d.input.strides[0] : 1;
+      xm.offset = d.input.strided ? d.input.offset_elements : 0;
+      xm.batch_stride = d.input.strided && d.input.batch_stride_elements > 0 ? d.input.batch_stride_elements : inN;
+    }
+    const int64_t tiles = (B + rm->T - 1) / rm->T;
+    for (int64_t k = 0; k < K; ++k) {
+      SideMap om = Builder::dense_map(pf, 1);
+      om.lo[0] = (int)ooff[0]; om.hi[0] = (int)(ooff[0] + os[0]);             // logical, as the zeroPad.write range
+      om.zlo[0] = d.zero_write.enabled ? (int)d.zero_write.start[0] : 0;
+      om.zhi[0] = d.zero_write.enabled ? (int)d.zero_write.end[0] : (int)lfN;
+      om.stride[0] = d.output.strided ? d.output.strides[0] : 1;
+      if (d.output.strided) { om.offset = d.output.offset_elements + k * kstride; om.batch_stride = d.output.batch_stride_elements > 0 ? d.output.batch_stride_elements : oN; }
+      else if (d.conv_output_layout == MI355FFT_KERNEL_MAJOR) { om.offset = k * B * oN; om.batch_stride = oN; }
+      else { om.offset = k * oN; om.batch_stride = K * oN; }
+      om.offset -= ooff[0] * om.stride[0];
+      Step& st = b.push(ST_LINES);
+      st.variant = rm->id;
+      st.p[0] = in; st.p[1] = out; st.p[2] = tables; st.p[3] = proots; st.p[4] = G.plus(k * (H + 1) * 8);
+      st.i[0] = tiles; st.i[1] = B; st.i[2] = 1; st.i[3] = H; st.i[4] = 1; st.i[5] = H; st.i[6] = 10; st.i[7] = 1023;
+      st.i[9] = 9; st.i[10] = 1; st.i[12] = corr ? 1 : 0; st.i[13] = split; st.i[14] = padD;
+      st.f[0] = (float)(1.0 / (double)P);
+      st.imap = xm; st.omap = om;
+      st.grid = b.lines_grid(*rm, tiles);
+    }
+    b.ir.route += "lines-rconv[N=" + std::to_string(P) + "] ";
+    return MI355FFT_OK;
+  }
+  if (strided) { err = "Unsupported: strided layouts on real fftconv outside the one-launch line route"; return MI355FFT_ERR_UNSUPPORTED; }
+
+  // ---- route 3: circular, odd shape[0]: the complex plan between a widening and a narrowing pass ----------------------------------
+  if (!linear && (lfN & 1)) {
+    mi355fft_plan_desc dc = d;
+    dc.type = MI355FFT_FFTCONV;
+    if (int rc = build_fftconv(dc, b, err)) return rc;
+    PlanIR& ir = b.ir;
+    const uint64_t in_c = (uint64_t)B * inN * 8, k_c = (uint64_t)K * kN * 8, out_c = (uint64_t)K * B * oN * 8;
+    const uint64_t in_stage = align_up(ir.work_bytes, 256), k_stage = align_up(in_stage + in_c, 256), out_stage = align_up(k_stage + k_c, 256);
+    ir.work_bytes = align_up(out_stage + out_c, 256);
+    for (Step& s : ir.steps)
+      for (PtrRef& p : s.p) {
+        if (p.buf == BUF_INPUT) p = PtrRef(BUF_WORK, (int64_t)in_stage + p.off);
+        else if (p.buf == BUF_KERNEL) p = PtrRef(BUF_WORK, (int64_t)k_stage + p.off);
+        else if (p.buf == BUF_OUTPUT) p = PtrRef(BUF_WORK, (int64_t)out_stage + p.off);
+      }
+    std::vector<Step> steps;
+    const auto convert = [&](StepKind kind, PtrRef src, PtrRef dst, int64_t count) {
+      Step c;
+      c.kind = kind; c.p[0] = src; c.p[1] = dst; c.i[0] = count; c.f[0] = 1.0f; c.grid = b.generic_grid(count);
+      steps.push_back(c);
+    };
+    convert(ST_REAL_TO_COMPLEX, in, PtrRef(BUF_WORK, (int64_t)in_stage), B * inN);
+    convert(ST_REAL_TO_COMPLEX, kern, PtrRef(BUF_WORK, (int64_t)k_stage), K * kN);
+    steps.insert(steps.end(), ir.steps.begin(), ir.steps.end());
+    convert(ST_COMPLEX_TO_REAL, PtrRef(BUF_WORK, (int64_t)out_stage), out, K * B * oN);
+    ir.steps.swap(steps);
+    ir.in_bytes = in_c / 2; ir.kernel_bytes = k_c / 2; ir.out_bytes = out_c / 2;
+    ir.route = "rconv-widened " + ir.route;
+    return MI355FFT_OK;
+  }
+
+  // ---- route 2: composed from the real emitters --------------------------------------------------------------------------------
+  // rank-1 linear requests take the next power of two (any domain >= lfN gives the same cropped values, and the half-length transforms
+  // stay off the mixed-radix / Bluestein routes); other linear requests round axis 0 up to an even length
+  if (linear) {
+    if (rank == 1 && b.opt.conv_pad && lfN <= ((int64_t)1 << 22)) { int64_t P = 2; while (P < lfN) P <<= 1; fs[0] = P; }
+    else fs[0] = lfN + (lfN & 1);
+  }
+  const int64_t padD = fs[0] - lfN;
+  if (padD) b.ir.route += "pad[" + std::to_string(lfN) + "->" + std::to_string(fs[0]) + "] ";
+  const auto pad_lo = [&](int64_t m) { return m < split ? m : m + padD; };
+  const auto pad_hi = [&](int64_t e) { return e <= split ? e : e + padD; };
+  int64_t ps[8];
+  for (int i = 0; i < rank; ++i) ps[i] = fs[i];
+  ps[0] = fs[0] / 2 + 1;
+  const int64_t fN = prodv(fs, rank), pN = prodv(ps, rank), F0 = fs[0];
+  const bool mapped0 = rank == 1 && fN < ((int64_t)1 << 31) && b.lines_r2c_kernel(F0, false, true) != nullptr;
+  mi355fft_side_layout dense{};
+  int rc;
+  // real lines [count][shape] -> packed spectra [count][ps]: embedded into the FFT domain (zeros elsewhere), restricted to `zr`
+  const auto forward = [&](PtrRef src, PtrRef dst, const int64_t* shp, int64_t count, const mi355fft_zero_range* zr) -> int {
+    bool emb = false;
+    for (int i = 0; i < rank; ++i) if (shp[i] != fs[i]) emb = true;
+    const int64_t n = prodv(shp, rank);
+    if ((emb || zr) && mapped0) {
+      SideMap im = Builder::dense_map(fs, 1), om = Builder::dense_map(ps, 1);
+      int64_t lo = 0, hi = shp[0];
+      if (zr) { lo = std::max(lo, zr->start[0]); hi = std::min(hi, zr->end[0]); }
+      if (hi < lo) hi = lo;
+      im.lo[0] = (int)lo; im.hi[0] = (int)hi; im.batch_stride = n;
+      if (!b.emit_lines_r2c(src, dst, F0, count, 1.0f, false, 0, &im, &om)) { err = "no mapped r2c line kernel"; return MI355FFT_ERR_UNSUPPORTED; }
+      return MI355FFT_OK;
+    }
+    PtrRef cur = src;
+    if (emb || zr) {
+      const PtrRef xr = b.alloc_work((uint64_t)count * fN * 4);
+      if (emb) {
+        Step& z = b.push(ST_ZERO); z.p[0] = xr; z.i[0] = count * fN; z.grid = b.generic_grid(count * fN);
+        b.emit_strided(true, src, xr, dense, shp, rank, count, fs, zero, fN, 0, true);
+      } else { Step& c = b.push(ST_COPY); c.p[0] = src; c.p[1] = xr; c.i[0] = count * fN * 4; }
+      if (zr) {
+        mi355fft_zero_range z2 = *zr;
+        z2.start[0] = pad_lo(z2.start[0]); z2.end[0] = pad_hi(z2.end[0]);
+        emit_zero_outside(b, xr, z2, fs, rank, count, true);
+        b.ir.route += "zero-read ";
+      }
+      cur = xr;
+    }
+    if (int r = b.emit_r2c_even(cur, dst, F0, count * (fN / F0), 1.0f, err)) return r;
+    if (rank > 1) return b.emit_nd(dst, dst, ps, rank, count, false, 1.0f, err, 1);
+    return MI355FFT_OK;
+  };
+  const PtrRef kf = b.alloc_work((uint64_t)K * pN * 8);
+  if ((rc = forward(kern, kf, ks, K, nullptr))) return rc;
+  const PtrRef xf = b.alloc_work((uint64_t)B * pN * 8);
+  if ((rc = forward(in, xf, d.shape, B, d.zero_read.enabled ? &d.zero_read : nullptr))) return rc;
+  const PtrRef y = b.alloc_work((uint64_t)B * pN * 8);
+  const bool direct_out = !linear && d.conv_output_layout == MI355FFT_KERNEL_MAJOR;     // the real inverse can land in the output itself
+  const PtrRef yr = direct_out ? PtrRef() : b.alloc_work((uint64_t)B * fN * 4);
+  const float inv_n = (float)(1.0 / (double)fN);
+  mi355fft_zero_range zw = d.zero_write;
+  int64_t poff[8];
+  for (int i = 0; i < rank; ++i) poff[i] = ooff[i];
+  if (padD) { zw.start[0] = pad_lo(zw.start[0]); zw.end[0] = pad_hi(zw.end[0]); poff[0] = pad_lo(ooff[0]); }
+  const bool straddle = padD > 0 && ooff[0] < split && ooff[0] + os[0] > split;
+  for (int64_t k = 0; k < K; ++k) {
+    Step& pm = b.push(ST_POINTWISE);
+    pm.p[0] = xf; pm.p[1] = y; pm.p[2] = kf.plus(k * pN * 8);
+    pm.i[0] = pN; pm.i[1] = B * pN; pm.i[2] = corr ? 1 : 0; pm.f[0] = 1.0f;
+    pm.grid = b.generic_grid(B * pN);
+    if (rank > 1 && (rc = b.emit_nd(y, y, ps, rank, B, true, 1.0f, err, 1))) return rc;
+    const PtrRef dst = direct_out ? out.plus(k * B * oN * 4) : yr;
+    if ((rc = b.emit_c2r_even(y, dst, F0, B * (fN / F0), inv_n, err))) return rc;
+    if (d.zero_write.enabled) emit_zero_outside(b, dst, zw, fs, rank, B, true);
+    if (direct_out) continue;
+    mi355fft_side_layout ol{};
+    ol.strided = 1;
+    int64_t st = 1;
+    for (int i = 0; i < rank; ++i) { ol.strides[i] = st; st *= os[i]; }
+    if (d.conv_output_layout == MI355FFT_KERNEL_MAJOR) { ol.offset_elements = k * B * oN; ol.batch_stride_elements = oN; }
+    else { ol.offset_elements = k * oN; ol.batch_stride_elements = K * oN; }
+    if (!straddle) b.emit_strided(false, out, yr, ol, os, rank, B, fs, poff, fN, 0, true);
+    else {   // positive and negative lags of a correlation: two pieces of the padded domain
+      int64_t s1[8], s2[8], o2[8];
+      for (int i = 0; i < rank; ++i) { s1[i] = s2[i] = os[i]; o2[i] = poff[i]; }
+      s1[0] = split - ooff[0]; s2[0] = os[0] - s1[0]; o2[0] = split + padD;
+      b.emit_strided(false, out, yr, ol, s1, rank, B, fs, poff, fN, 0, true);
+      b.emit_strided(false, out, yr, ol, s2, rank, B, fs, o2, fN, s1[0] * ol.strides[0], true);
+    }
+  }
+  if (d.zero_write.enabled) b.ir.route += "zero-write ";
+  b.ir.route += "rconv[K=" + std::to_string(K) + "] ";
+  return MI355FFT_OK;
+}
+
 // ---- precision "f16-storage" (reference src/kernels/f16_storage.js; runtime/plans/c2c.js:1036-1050, 3840-3861, 4163-4180) ----
 // The checks the reference makes before planning: custom strides (layout.strides, whdcn) and fftconv take f32 only.
 int validate_f16_storage(const mi355fft_plan_desc& d, std::string& err) {
-  if (d.type == MI355FFT_FFTCONV) { err = "fftconv supports precision:\"f32\" only in current implementation"; return MI355FFT_ERR_INVALID; }
+  if (d.type == MI355FFT_FFTCONV || d.type == MI355FFT_FFTCONV_REAL) { err = "fftconv supports precision:\"f32\" only in current implementation"; return MI355FFT_ERR_INVALID; }
   if (d.input.strided || d.output.strided) {
     if (d.type >= MI355FFT_DCT1) err = "custom strides for dct/dst currently support precision:\"f32\" only";
     else err = std::string("custom strides currently support precision:\"f32\" only") + (d.type == MI355FFT_R2C ? " for r2c" : d.type == MI355FFT_C2R ? " for c2r" : "");
@@ -2020,6 +2260,7 @@ int build_plan_f32(const mi355fft_plan_desc& desc, const PlannerOptions& opt, Pl
     case MI355FFT_DCT1: case MI355FFT_DCT2: case MI355FFT_DCT3: case MI355FFT_DCT4:
     case MI355FFT_DST1: case MI355FFT_DST2: case MI355FFT_DST3: case MI355FFT_DST4: rc = build_trig(desc, b, err); break;
     case MI355FFT_FFTCONV: rc = build_fftconv(desc, b, err); break;
+    case MI355FFT_FFTCONV_REAL: rc = build_fftconv_real(desc, b, err); break;
     default: err = "type must be one of \"c2c\", \"r2c\", \"c2r\", \"fftconv\" (other createPlan types are outside the MI355X hot path)"; rc = MI355FFT_ERR_UNSUPPORTED;
   }
   if (rc) return rc;

@@ -13,6 +13,7 @@
 // emulation used by the CPU tests (tests/emu).
 #pragma once
 #include <cstdint>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -157,6 +158,14 @@ struct PlannerOptions {
   int conv_pipeline = 1;               // fftconv on a 2^20-point FFT domain, dense sides: forward, products and inverses in one persistent launch (kern_regtile.hpp fft_xcd_conv1m_kernel;
                                        // the linear modes and zeroPad through its VIEW form); 0: the composed route
   int conv_pad = 1;                    // fftconv, rank 1, linear modes with 16384 < shape + kernelShape - 1 <= 2^22: transform on the next power of two (0: the exact length)
+#ifdef MI355_HOST_EMU
+  // the emulation harness builds its options without planner_options_from_env(): the switch's emulation twin is read here
+  int rconv_fused = std::getenv("MI355_EMU_RCONV_FUSED") ? std::atoi(std::getenv("MI355_EMU_RCONV_FUSED")) : 1;
+#else
+  int rconv_fused = 1;
+#endif
+                                       // real fftconv (MI355FFT_FFTCONV_REAL), rank 1, power-of-two FFT length 128..8192 (16384, 32768: strided sides only): r2c, product and c2r of a
+                                       // line in one launch per kernel (kern_lines.hpp fft_lines_rconv_kernel); 0: the composed route rconv[K]; 2: the line route up to 32768 as well
   int conv_lines = 1;                  // fftconv: kernel-spectrum product fused behind the forward line FFT (1-D, power-of-two FFT length <= max_line)
   int trig_fused = 1;                  // dct2 / dst2 of dense lines (half length a line-kernel size): permutation + real FFT + phase in one launch
   int trig_real = 1;                   // dct2/dst2/dct3/dst3 along a dense even axis through a real FFT of length N (kern_trig.hpp)

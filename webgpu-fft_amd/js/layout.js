@@ -16,6 +16,7 @@ const HOT_PATH_TYPES = ["c2c", "r2c", "c2r", "fftconv"];
 const ALL_TYPES = ["c2c", "r2c", "c2r", "dct1", "dct2", "dct3", "dct4", "dst1", "dst2", "dst3", "dst4", "fftconv", "conv2d"];
 
 export const TYPE_CODE = { c2c: 0, r2c: 1, c2r: 2, fftconv: 3, dct1: 4, dct2: 5, dct3: 6, dct4: 7, dst1: 8, dst2: 9, dst3: 10, dst4: 11 };
+export const FFTCONV_REAL_CODE = 12;   // MI355FFT_FFTCONV_REAL: type "fftconv" with layout.interleavedComplex false
 const TRIG_TYPES = ["dct1", "dct2", "dct3", "dct4", "dst1", "dst2", "dst3", "dst4"];   // real-to-real, real f32 buffers (dct_fft.js)
 export const DIRECTION_CODE = { forward: 0, inverse: 1 };
 export const NORMALIZE_CODE = { none: 0, backward: 1, unitary: 2 };
@@ -314,7 +315,10 @@ export function resolvePlanOptions(opts) {
     if (!isPlainObject(layout) || layout.interleavedComplex !== false) throw new Error("DCT/DST uses real buffers; set layout.interleavedComplex=false");
     if (shape.some((n) => n < 2)) throw new Error("All DCT/DST dimensions must be >= 2; got shape=" + JSON.stringify(shape));
     if (opts.inPlace) throw new Error("DCT/DST inPlace is not supported in current implementation");
+  } else if (type === "fftconv" && isPlainObject(layout) && layout.interleavedComplex === false) {
+    // real fftconv: signals, kernels and results are f32 reals (include/mi355fft.h MI355FFT_FFTCONV_REAL)
   } else if (!isPlainObject(layout) || layout.interleavedComplex !== true) throw new Error(type + " requires layout.interleavedComplex=true");
+  const realConv = type === "fftconv" && layout.interleavedComplex === false;
   const precision = dflt(opts.precision, "f32");
   assertOneOf(precision, ["f32", "f16-storage"], "precision");
   if (precision !== "f32" && type === "fftconv") throw new Error('fftconv supports precision:"f32" only in current implementation');
@@ -400,6 +404,11 @@ export function resolvePlanOptions(opts) {
     if (sides.output) desc.output = sides.output;
     Object.assign(meta, { mode, boundary, kernelCount, outputLayout, kernelShape: kernelShape.slice(), outputShape,
       inputLayout: sides.input, outputLayoutResolved: sides.output, outputKernelStrideElements: desc.convOutputKernelStrideElements });
+    if (realConv) {      // element = one f32 on both sides and in the kernel buffer
+      desc.type = FFTCONV_REAL_CODE;
+      Object.assign(meta, { real: true, inputBytes: 4 * batch * prod(shape), kernelBytes: 4 * kernelCount * prod(kernelShape),
+        outputBytes: 4 * batch * kernelCount * prod(outputShape) });
+    }
     return { desc, meta };
   }
 

@@ -65,7 +65,7 @@ export class Plan extends NativePlanBase {
   // commandEncoder: kernels given as an array of GPU buffers / BufferViews ("array-sources", fftconv.js:920-941) are packed by
   // one copyBufferToBuffer per kernel recorded ahead of the plan's own launches
   _prepareKernel(kernel, commandEncoder) {
-    const single = 2 * prod(this.kernelShape);
+    const single = (this.real ? 1 : 2) * prod(this.kernelShape);      // real fftconv plans take real kernels
     const packed = single * this.kernelCount;
     let payload = null;
     if (kernel instanceof Float32Array) {

@@ -311,7 +311,7 @@ static napi_value js_plan_create(napi_env env, napi_callback_info info) {
   mi355fft_plan_desc d;
   memset(&d, 0, sizeof d);
   d.struct_size = sizeof d;
-  d.type = (int32_t)prop_i64(env, o, "type", -1);
+  d.type = (int32_t)prop_i64(env, o, "type", -1);   /* MI355FFT_C2C ... MI355FFT_FFTCONV_REAL (12: js/layout.js maps fftconv with real buffers to it) */
   d.direction = (int32_t)prop_i64(env, o, "direction", 0);
   d.normalize = (int32_t)prop_i64(env, o, "normalize", 0);
   d.in_place = (int32_t)prop_i64(env, o, "inPlace", 0);

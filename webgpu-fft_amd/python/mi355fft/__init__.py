@@ -172,7 +172,7 @@ class Plan:
         resolved = resolve_plan_options(opts)
         self._resolved = resolved
         self.type = resolved["type"]
-        self._desc = _abi.make_desc(resolved["type"], resolved["shape"], resolved["batch"], resolved["direction"], resolved["normalize"],
+        self._desc = _abi.make_desc(resolved.get("abi_type", resolved["type"]), resolved["shape"], resolved["batch"], resolved["direction"], resolved["normalize"],
                                     resolved["inPlace"], resolved["input_layout"], resolved["output_layout"], resolved.get("conv"),
                                     resolved.get("io_view"), resolved.get("zero_pad"), resolved.get("axes"),
                                     resolved.get("precision", "f32"))
@@ -202,7 +202,8 @@ class Plan:
             return kernel
         conv = self._resolved["conv"]
         kn = int(np.prod(conv.get("kernelShape") or self._resolved["shape"]))
-        single, packed = 2 * kn, 2 * kn * conv["kernelCount"]
+        per = 1 if self._resolved.get("real") else 2      # real fftconv plans take real kernels
+        single, packed = per * kn, per * kn * conv["kernelCount"]
         if isinstance(kernel, (list, tuple)):
             if len(kernel) != conv["kernelCount"]:
                 raise Mi355Error(1, f"kernel array length must equal fftConv.kernelCount={conv['kernelCount']}; got {len(kernel)}")

@@ -408,8 +408,11 @@ def resolve_plan_options(opts):
             raise ValueError(f"All DCT/DST dimensions must be >= 2; got shape={shape!r}")
         if opts.get("inPlace", False):
             raise ValueError("DCT/DST inPlace is not supported in current implementation")
+    elif typ == "fftconv" and isinstance(layout, dict) and layout.get("interleavedComplex") is False:
+        pass       # real fftconv: signals, kernels and results are f32 reals (include/mi355fft.h MI355FFT_FFTCONV_REAL)
     elif not isinstance(layout, dict) or layout.get("interleavedComplex") is not True:
         raise ValueError(f"{typ} requires layout.interleavedComplex=true")
+    real_conv = typ == "fftconv" and layout.get("interleavedComplex") is False
     precision = opts.get("precision", "f32")
     _assert_one_of(precision, ("f32", "f16-storage"), "precision")
     if precision != "f32" and typ == "fftconv":
@@ -486,6 +489,9 @@ def resolve_plan_options(opts):
                     "conv": {"mode": mode, "boundary": boundary, "kernelCount": kernel_count, "outputLayout": output_layout,
                              "kernelShape": kshape, "outputKernelStrideElements": explicit_kstride or policy_kstride or 0},
                     "outputShape": out_shape})
+        if real_conv:      # element = one f32 on both sides and in the kernel buffer
+            out.update({"abi_type": "fftconv-real", "real": True, "inputBytes": 4 * batch * _prod(shape),
+                        "kernelBytes": 4 * kernel_count * _prod(kshape), "outputBytes": 4 * batch * kernel_count * _prod(out_shape)})
         if in_place:
             raise ValueError("fftconv inPlace=true is not supported in current implementation")
         return out
