@@ -237,6 +237,53 @@ int emu_plan_only(const mi355fft_plan_desc* desc, int compute_units, char* err, 
   return 0;
 }
 
+// Planner only, the whole PlanIR as text: two plans are the same plan when their dumps are equal (tools/plan_snapshot.py compares
+// the planner of two builds this way).  Returns the planner status; `out` receives the error text or the dump, cut at out_bytes;
+// `needed` the bytes the full text takes (with its terminator).  Floats are printed as their bit patterns, the table as its length
+// and the FNV-1a hash of its bytes.
+int emu_plan_dump(const mi355fft_plan_desc* desc, int compute_units, char* out, size_t out_bytes, size_t* needed) {
+  using namespace mi355;
+  PlannerOptions opt = planner_options_from_env();
+  opt.compute_units = compute_units > 0 ? compute_units : 256;
+  PlanIR ir;
+  std::string t;
+  const int rc = build_plan(*desc, opt, ir, t);
+  if (!rc) {
+    const auto num = [&](const char* name, long long v) { t += name; t += std::to_string(v); };
+    const auto bits = [](float v) { uint32_t u; std::memcpy(&u, &v, 4); return (long long)u; };
+    const auto ints = [&](const char* name, const auto* v, int n) { t += name; for (int i = 0; i < n; ++i) { t += i ? "," : ""; t += std::to_string((long long)v[i]); } };
+    const auto side = [&](const char* name, const SideMap& m) {
+      t += name; num(" rank=", m.rank); num(" ax=", m.ax); ints(" dims=", m.dims, 8); ints(" lo=", m.lo, 8); ints(" hi=", m.hi, 8);
+      ints(" zlo=", m.zlo, 8); ints(" zhi=", m.zhi, 8); ints(" stride=", m.stride, 8); num(" offset=", m.offset); num(" batch_stride=", m.batch_stride);
+      t += "\n";
+    };
+    uint64_t h = 1469598103934665603ull;
+    const unsigned char* tb = (const unsigned char*)ir.table.data();
+    for (size_t i = 0; i < ir.table.size() * sizeof(float2h); ++i) h = (h ^ tb[i]) * 1099511628211ull;
+    t = "route=" + ir.route + "\n";
+    num("work_bytes=", (long long)ir.work_bytes); num(" in_bytes=", (long long)ir.in_bytes); num(" out_bytes=", (long long)ir.out_bytes);
+    num(" kernel_bytes=", (long long)ir.kernel_bytes); num(" table_len=", (long long)ir.table.size());
+    char hex[32];
+    std::snprintf(hex, sizeof hex, " table_hash=%016llx\n", (unsigned long long)h);
+    t += hex;
+    num("steps=", (long long)ir.steps.size()); t += "\n";
+    for (size_t n = 0; n < ir.steps.size(); ++n) {
+      const Step& s = ir.steps[n];
+      num("step ", (long long)n); num(" kind=", s.kind); num(" variant=", s.variant); num(" grid=", s.grid);
+      t += " p=";
+      for (int i = 0; i < 5; ++i) { t += i ? "," : ""; t += std::to_string(s.p[i].buf) + ":" + std::to_string((long long)s.p[i].off); }
+      ints(" i=", s.i, 20); num(" f=", bits(s.f[0])); num(",", bits(s.f[1]));
+      ints(" shape=", s.shape, 8); ints(" sa=", s.sa, 8); ints(" sb=", s.sb, 8);
+      t += "\n";
+      side("  imap", s.imap);
+      side("  omap", s.omap);
+    }
+  }
+  if (needed) *needed = t.size() + 1;
+  if (out && out_bytes) std::snprintf(out, out_bytes, "%s", t.c_str());
+  return rc;
+}
+
 // support kernels: PRNG twin + reductions
 int emu_fill_random(float* out, uint64_t row_floats, uint64_t rows, uint32_t seed0, uint64_t first_transform) {
   EmuLauncher l;

@@ -32,6 +32,8 @@ def lib():
         L.emu_plan_only.restype = ctypes.c_int
         L.emu_plan_only.argtypes = [ctypes.POINTER(_abi.PlanDesc), ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
                                     ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint64)]
+        L.emu_plan_dump.restype = ctypes.c_int
+        L.emu_plan_dump.argtypes = [ctypes.POINTER(_abi.PlanDesc), ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
         _LIB = L
     return _LIB
 
@@ -52,6 +54,18 @@ def plan_only(desc, compute_units=256):
     if rc != 0:
         raise EmuError(rc, err.value.decode())
     return route.value.decode(), launches.value, work.value
+
+
+def plan_dump(desc, compute_units=256):
+    """The product planner's whole PlanIR as text (emu_plan_dump): (status, dump), or (status, error text) when planning fails."""
+    size = 1 << 16
+    while True:
+        buf = ctypes.create_string_buffer(size)
+        needed = ctypes.c_size_t(0)
+        rc = lib().emu_plan_dump(ctypes.byref(desc), compute_units, buf, size, ctypes.byref(needed))
+        if needed.value <= size:
+            return rc, buf.value.decode()
+        size = needed.value
 
 
 def run_plan(desc, x, out_floats, kernel=None, force_generic=False, chunk_bytes=0, out_init=None):

@@ -256,6 +256,8 @@ struct Builder {
   }
   unsigned oneshot_grid(int64_t items) const { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(items, MAX_BLOCKS)); }
   Step& push(StepKind k) { ir.steps.emplace_back(); ir.steps.back().kind = k; return ir.steps.back(); }
+  // clears `scalars` 32-bit words at ptr
+  Step& zero(PtrRef ptr, int64_t scalars) { Step& z = push(ST_ZERO); z.p[0] = ptr; z.i[0] = scalars; z.grid = generic_grid(scalars); return z; }
 
   // stage-2 roots of the register-tile passes (kern_regtile.hpp): e^{-2 pi i q2 j2/2048}, rows q2 = 1..31, j2 = 0..63 fastest
   PtrRef regtile_table() {
@@ -367,7 +369,7 @@ struct Builder {
   // the ST_ZERO of the control block (shared mode) and the launch with the fields every fused emitter fills (dispatch.hpp
   // ST_XCD_FUSED); the caller adds the scale, pitches other than N (i[9] in, i[10] out) and its own fields
   Step& push_xcd(StepKind kind, int variant, const XcdLaunch& x, PtrRef src, PtrRef dst, int64_t transforms, int64_t N) {
-    if (!x.solo) { Step& z = push(ST_ZERO); z.p[0] = x.ctl; z.i[0] = XCD_CTL_ZERO_FLOATS; z.grid = 1; }
+    if (!x.solo) zero(x.ctl, XCD_CTL_ZERO_FLOATS).grid = 1;   // (8 KiB: one workgroup)
     Step& st = push(kind);
     st.variant = variant;
     st.p[0] = src; st.p[1] = dst; st.p[2] = x.wslots; st.p[3] = x.ctl; st.p[4] = PtrRef(BUF_TABLE, 0);
@@ -1202,9 +1204,10 @@ uint64_t side_bytes(const mi355fft_side_layout& lay, const mi355fft_io_view& vie
   return lay.strided ? strided_extent_elems(lay, pshape, rank, batch, 0) * elem : (uint64_t)prodv(pshape, rank) * batch * elem;
 }
 
-// ---- the two sides of an r2c / c2r plan (the same staging build_c2c does inline, for real or complex elements) ----
+// ---- the two sides of a plan that its launches cannot map (c2c, r2c, c2r and the trig plans; real or complex elements) ----
 // Input: strided layout, ioView.input (embed into the zero-filled logical domain) and zeroPad.read produce a dense logical
-// array in the workspace; a plain dense input is used where it lies.  `phys_n`: elements of one physical item.
+// array in the workspace; a plain dense input is used where it lies.  In place (c2c only, where nothing but zeroPad.read can be
+// asked for) the range is zeroed in the caller's buffer itself.
 PtrRef stage_side_input(const mi355fft_plan_desc& d, Builder& b, PtrRef in, const int64_t* lshape, bool real, uint64_t& in_bytes) {
   const int rank = d.rank;
   const int64_t elem = real ? 4 : 8, n = prodv(lshape, rank);
@@ -1213,13 +1216,13 @@ PtrRef stage_side_input(const mi355fft_plan_desc& d, Builder& b, PtrRef in, cons
   const int64_t in_n = prodv(ishape, rank);
   in_bytes = d.input.strided ? strided_extent_elems(d.input, ishape, rank, d.batch, 0) * elem : (uint64_t)in_n * d.batch * elem;
   if (!(d.input.strided || vin || d.zero_read.enabled)) return in;
-  const PtrRef src = b.alloc_work((uint64_t)n * d.batch * elem);
+  const PtrRef src = d.in_place ? in : b.alloc_work((uint64_t)n * d.batch * elem);
   if (vin) {
     int64_t ext[8], ls[8], vs[8];
     const bool any = view_region(d.io_input, lshape, rank, ext, ls, vs);
     bool covers = any;
     for (int i = 0; any && i < rank; ++i) covers = covers && ext[i] == lshape[i];
-    if (!covers) { Step& z = b.push(ST_ZERO); z.p[0] = src; z.i[0] = n * d.batch * (elem / 4); z.grid = b.generic_grid(z.i[0]); }
+    if (!covers) b.zero(src, n * d.batch * (elem / 4));
     if (any) {
       mi355fft_side_layout lay = d.input;
       int64_t vstride = 1, poff = 0;
@@ -1232,7 +1235,7 @@ PtrRef stage_side_input(const mi355fft_plan_desc& d, Builder& b, PtrRef in, cons
   } else if (d.input.strided) {
     b.emit_strided(true, in, src, d.input, lshape, rank, d.batch, lshape, nullptr, n, 0, real);
     b.ir.route += "gather ";
-  } else {
+  } else if (!d.in_place) {
     Step& c = b.push(ST_COPY); c.p[0] = in; c.p[1] = src; c.i[0] = n * d.batch * elem;
   }
   if (d.zero_read.enabled) { emit_zero_outside(b, src, d.zero_read, lshape, rank, d.batch, real); b.ir.route += "zero-read "; }
@@ -1257,7 +1260,7 @@ int finish_side_output(const mi355fft_plan_desc& d, Builder& b, PtrRef out, PtrR
     const int64_t out_n = prodv(oshape, rank);
     if (d.io_output.clear_outside) {
       if (d.output.strided) { err = "Unsupported: ioView.output.clearOutside with a strided output layout"; return MI355FFT_ERR_UNSUPPORTED; }
-      Step& z = b.push(ST_ZERO); z.p[0] = out; z.i[0] = out_n * d.batch * (elem / 4); z.grid = b.generic_grid(z.i[0]);
+      b.zero(out, out_n * d.batch * (elem / 4));
     }
     int64_t ext[8], ls[8], vs[8];
     if (view_region(d.io_output, lshape, rank, ext, ls, vs)) {
@@ -1286,12 +1289,10 @@ int build_c2c(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
   const float scale = (float)scale_factor(d.normalize, inverse, (double)n);
   const bool vin = d.io_input.enabled != 0, vout = d.io_output.enabled != 0;
   if (d.in_place && (vin || vout || d.input.strided || d.output.strided)) { err = "inPlace=true cannot be combined with ioView or strided layouts"; return MI355FFT_ERR_INVALID; }
-  const int64_t* ishape = vin ? d.io_input.shape : d.shape;     // physical shapes of the two sides
-  const int64_t* oshape = vout ? d.io_output.shape : d.shape;
-  const int64_t in_n = prodv(ishape, rank), out_n = prodv(oshape, rank);
+  const int64_t out_n = prodv(vout ? d.io_output.shape : d.shape, rank);     // physical elements of an output item
   PtrRef in(BUF_INPUT, 0), out(d.in_place ? BUF_INPUT : BUF_OUTPUT, 0);
-  b.ir.in_bytes = d.input.strided ? strided_extent_elems(d.input, ishape, rank, d.batch, 0) * 8 : (uint64_t)in_n * d.batch * 8;
-  b.ir.out_bytes = d.output.strided ? strided_extent_elems(d.output, oshape, rank, d.batch, 0) * 8 : (uint64_t)out_n * d.batch * 8;
+  b.ir.in_bytes = side_bytes(d.input, d.io_input, d.shape, rank, d.batch, 8);
+  b.ir.out_bytes = side_bytes(d.output, d.io_output, d.shape, rank, d.batch, 8);
   if (d.axes_mask >> rank) { err = "Invalid axis in axes for rank " + std::to_string(rank); return MI355FFT_ERR_INVALID; }
   if (vout && d.io_output.clear_outside && d.output.strided) { err = "Unsupported: ioView.output.clearOutside with a strided output layout"; return MI355FFT_ERR_UNSUPPORTED; }
 
@@ -1324,7 +1325,7 @@ int build_c2c(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
     const SideMap im = input_side_map(d, d.shape, 1), om = output_side_map(d, d.shape, 1);
     if (im.stride[0] == 1 && om.stride[0] == 1 && n < ((int64_t)1 << 30)) {
       const size_t mark = b.ir.steps.size();
-      if (vout && d.io_output.clear_outside) { Step& z = b.push(ST_ZERO); z.p[0] = out; z.i[0] = out_n * d.batch * 2; z.grid = b.generic_grid(z.i[0]); }
+      if (vout && d.io_output.clear_outside) b.zero(out, out_n * d.batch * 2);
       if (b.emit_xcd_view(in, out, n, d.batch, inverse, scale, im, om)) return MI355FFT_OK;
       b.ir.steps.resize(mark);
     }
@@ -1346,34 +1347,8 @@ int build_c2c(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
   if (fuse_out) omap = output_side_map(d, d.shape, rank);
 
   // ---- input side: dense logical staging when anything but a plain dense read is asked for and the first pass cannot map it ----
-  PtrRef src = in;
-  const bool stage_in = !fuse_in && (d.input.strided || vin || (d.zero_read.enabled && !d.in_place));
-  if (stage_in) {
-    src = b.alloc_work((uint64_t)n * d.batch * 8);
-    if (vin) {
-      int64_t ext[8], ls[8], vs[8];
-      const bool any = view_region(d.io_input, d.shape, rank, ext, ls, vs);
-      bool covers = any;
-      for (int i = 0; any && i < rank; ++i) covers = covers && ext[i] == d.shape[i];
-      if (!covers) { Step& z = b.push(ST_ZERO); z.p[0] = src; z.i[0] = n * d.batch * 2; z.grid = b.generic_grid(z.i[0]); }
-      if (any) {
-        // physical offset of the region's first element inside the view
-        mi355fft_side_layout lay = d.input;
-        int64_t vstride = 1, poff = 0;
-        for (int i = 0; i < rank; ++i) { poff += vs[i] * (lay.strided ? lay.strides[i] : vstride); vstride *= ishape[i]; }
-        if (!lay.strided) { lay.strided = 1; int64_t st = 1; for (int i = 0; i < rank; ++i) { lay.strides[i] = st; st *= ishape[i]; } lay.offset_elements = 0; lay.batch_stride_elements = in_n; }
-        else if (lay.batch_stride_elements <= 0) lay.batch_stride_elements = in_n;
-        b.emit_strided(true, in, src, lay, ext, rank, d.batch, d.shape, ls, n, poff);
-      }
-      b.ir.route += "embed ";
-    } else if (d.input.strided) {
-      b.emit_strided(true, in, src, d.input, d.shape, rank, d.batch, d.shape, nullptr, n, 0);
-      b.ir.route += "gather ";
-    } else {
-      Step& c = b.push(ST_COPY); c.p[0] = in; c.p[1] = src; c.i[0] = n * d.batch * 8;
-    }
-  }
-  if (d.zero_read.enabled && !fuse_in) { emit_zero_outside(b, src, d.zero_read, d.shape, rank, d.batch); b.ir.route += "zero-read "; }
+  const PtrRef src = fuse_in ? in : stage_side_input(d, b, in, d.shape, false, b.ir.in_bytes);
+  const bool stage_in = !src.same(in);
 
   // ---- transform ----
   // dst: the dense array the passes work on.  A staged or mapped output side needs one that is not the caller's output: the
@@ -1381,32 +1356,11 @@ int build_c2c(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
   const bool stage_out = !fuse_out && (d.output.strided || vout);
   PtrRef dst = out;
   if (stage_out || (fuse_out && (d.output.strided || vout) && !(fuse_in && fa == la))) dst = stage_in ? src : b.alloc_work((uint64_t)n * d.batch * 8);
-  if (fuse_out && vout && d.io_output.clear_outside) {   // view elements outside the logical domain: zeroed before the store pass
-    Step& z = b.push(ST_ZERO); z.p[0] = out; z.i[0] = out_n * d.batch * 2; z.grid = b.generic_grid(z.i[0]);
-  }
+  if (fuse_out && vout && d.io_output.clear_outside) b.zero(out, out_n * d.batch * 2);   // view elements outside the logical domain: zeroed before the store pass
   rc = b.emit_nd(src, dst, d.shape, rank, d.batch, inverse, scale, err, 0, d.axes_mask, fuse_in ? &imap : nullptr, fuse_out ? &omap : nullptr, out);
   if (rc) return rc;
   if (fuse_out) return MI355FFT_OK;
-  if (d.zero_write.enabled) { emit_zero_outside(b, dst, d.zero_write, d.shape, rank, d.batch); b.ir.route += "zero-write "; }
-
-  // ---- output side ----
-  if (vout) {
-    if (d.io_output.clear_outside) { Step& z = b.push(ST_ZERO); z.p[0] = out; z.i[0] = out_n * d.batch * 2; z.grid = b.generic_grid(z.i[0]); }
-    int64_t ext[8], ls[8], vs[8];
-    if (view_region(d.io_output, d.shape, rank, ext, ls, vs)) {
-      mi355fft_side_layout lay = d.output;
-      int64_t vstride = 1, poff = 0;
-      for (int i = 0; i < rank; ++i) { poff += vs[i] * (lay.strided ? lay.strides[i] : vstride); vstride *= oshape[i]; }
-      if (!lay.strided) { lay.strided = 1; int64_t st = 1; for (int i = 0; i < rank; ++i) { lay.strides[i] = st; st *= oshape[i]; } lay.offset_elements = 0; lay.batch_stride_elements = out_n; }
-      else if (lay.batch_stride_elements <= 0) lay.batch_stride_elements = out_n;
-      b.emit_strided(false, out, dst, lay, ext, rank, d.batch, d.shape, ls, n, poff);
-    }
-    b.ir.route += "extract ";
-  } else if (d.output.strided) {
-    b.emit_strided(false, out, dst, d.output, d.shape, rank, d.batch, d.shape, nullptr, n, 0);
-    b.ir.route += "scatter ";
-  }
-  return MI355FFT_OK;
+  return finish_side_output(d, b, out, dst, d.shape, false, err);
 }
 
 // r2c along axis 0 (packed P = N/2+1 bins), then c2c along the remaining axes of the packed array
@@ -1445,9 +1399,7 @@ int build_r2c(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
   // the dense packed array the passes work on: the caller's output unless a strided layout / ioView follows (staged or mapped)
   PtrRef out = (d.output.strided || d.io_output.enabled) ? b.alloc_work((uint64_t)lines * P * 8) : user_out;
   const SideMap omap = fuse_out ? output_side_map(d, pshape, rank) : SideMap();
-  if (fuse_out && d.io_output.enabled && d.io_output.clear_outside) {   // view elements outside the logical domain: zeroed before the store pass
-    Step& z = b.push(ST_ZERO); z.p[0] = user_out; z.i[0] = prodv(d.io_output.shape, rank) * d.batch * 2; z.grid = b.generic_grid(z.i[0]);
-  }
+  if (fuse_out && d.io_output.enabled && d.io_output.clear_outside) b.zero(user_out, prodv(d.io_output.shape, rank) * d.batch * 2);   // view elements outside the logical domain: zeroed before the store pass
   if (map0) {
     const SideMap im = fuse_in ? input_side_map(d, d.shape, rank) : Builder::dense_map(d.shape, rank);
     const bool store0 = fuse_out && la < 1;
@@ -1524,9 +1476,7 @@ int build_c2r(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
     if (rc) return rc;
     in_mapped_done = first_mapped;
   }
-  if (fuse_out && d.io_output.enabled && d.io_output.clear_outside) {
-    Step& z = b.push(ST_ZERO); z.p[0] = user_out; z.i[0] = prodv(d.io_output.shape, rank) * d.batch; z.grid = b.generic_grid(z.i[0]);
-  }
+  if (fuse_out && d.io_output.enabled && d.io_output.clear_outside) b.zero(user_out, prodv(d.io_output.shape, rank) * d.batch);
   if (map0) {
     const SideMap im = (fuse_in && !in_mapped_done) ? imap : Builder::dense_map(pshape, rank);
     const SideMap om = fuse_out ? output_side_map(d, d.shape, rank) : Builder::dense_map(d.shape, rank);
@@ -1551,8 +1501,6 @@ int build_c2r(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
   return MI355FFT_OK;
 }
 
-// y_k = IFFT( FFT(x) .* (conj?)FFT(h_k) ) / Nfft, cropped per boundary, written per output layout / lanes
-// (runtime/plans/fftconv.js:308-709, exec :1415-1712; reference semantics: src/utils/math.js:469-603)
 // DCT-I..IV / DST-I..IV over real buffers (dct_fft.js): per axis a pre-pass into complex lines of length L, the complex FFT
 // of those lines, a post-pass back into the real array (kern_trig.hpp); one scale by normalizeScaleFactor(prod(shape)) folded
 // into the last post-pass (dct_fft.js:882).  Layout strides, ioView and zeroPad ride the same side staging as r2c / c2r.
@@ -1648,68 +1596,185 @@ int build_trig(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
   return finish_side_output(d, b, user_out, dst, d.shape, true, err);
 }
 
-int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
+// ---- fftconv: what both builders share ------------------------------------------------------------------------------------------
+// The shapes of an fftconv plan, its output lanes and the index map of a padded axis 0.  A linear result is cropped out of the FFT
+// domain, so any domain of at least shape + kernelShape - 1 points gives the same values: a builder may transform axis 0 on a longer
+// one (pad_axis0).  Everything the caller states (zeroPad ranges, output shape and offset) stays on the logical domain [0, lfN).
+// Padded index k is logical index k below `split` and k - padD from split + padD on; the padD indices in between belong to no logical
+// index.  Convolution: split = lfN (the padding is the tail).  Correlation conjugates the kernel spectra, so its kernelShape - 1
+// negative lags wrap to the TOP of the domain: split = shape.  pad_lo / pad_hi carry the start / the end of a logical range onto
+// the padded domain.
+struct ConvGeom {
+  int rank;
+  int64_t K, B;
+  bool linear, corr;
+  int64_t ks[8], fs[8], os[8], ooff[8];   // kernel shape, FFT domain (axis 0 as padded), output shape, crop offset on the logical domain
+  int64_t inN, kN, oN, lfN;               // elements of a data item, a kernel and an output item; logical axis-0 length of the FFT domain
+  int64_t padD = 0, split;
+  // output lanes in elements (fftconv.js:868-871): result (k, b) starts at lane0 + k * lane_k + b * lane_b — the caller's strided
+  // lanes, kernel-major [K][B][oN] or batch-major [B][K][oN]
+  int64_t lane0, lane_k, lane_b;
+
+  void pad_axis0(int64_t F0) { padD = F0 - lfN; fs[0] = F0; }
+  int64_t pad_lo(int64_t m) const { return m < split ? m : m + padD; }
+  int64_t pad_hi(int64_t e) const { return e <= split ? e : e + padD; }
+  // a zeroPad range as ONE padded range (what lies between its two images is never read or extracted)
+  mi355fft_zero_range padded(mi355fft_zero_range z) const { z.start[0] = pad_lo(z.start[0]); z.end[0] = pad_hi(z.end[0]); return z; }
+  // the crop holds both positive and negative lags of a correlation: two pieces of the padded domain
+  bool straddle() const { return padD > 0 && ooff[0] < split && ooff[0] + os[0] > split; }
+  int64_t lane_offset(int64_t k) const { return lane0 + k * lane_k; }
+};
+
+// Validates the fftconv options and fills the geometry and the plan's extents for elements of `elem` bytes (8: complex, 4: real)
+int conv_geometry(const mi355fft_plan_desc& d, int64_t elem, ConvGeom& g, PlanIR& ir, std::string& err) {
   if (d.io_input.enabled || d.io_output.enabled) { err = "ioView is not an fftconv option"; return MI355FFT_ERR_INVALID; }
   if (d.in_place) { err = "fftconv inPlace=true is not supported in current implementation"; return MI355FFT_ERR_INVALID; }
   if (d.conv_mode != MI355FFT_CONVOLUTION && d.conv_mode != MI355FFT_CORRELATION) { err = "fftConv.mode must be one of \"convolution\", \"correlation\""; return MI355FFT_ERR_INVALID; }
   if (d.conv_boundary < 0 || d.conv_boundary > 3) { err = "fftConv.boundary must be one of \"circular\", \"linear-full\", \"linear-same\", \"linear-valid\""; return MI355FFT_ERR_INVALID; }
   if (d.conv_kernel_count <= 0) { err = "fftConv.kernelCount must be a positive integer; got " + std::to_string(d.conv_kernel_count); return MI355FFT_ERR_INVALID; }
-  const int rank = d.rank;
-  const int64_t K = d.conv_kernel_count, B = d.batch;
-  int64_t ks[8], fs[8], os[8], ooff[8], zero[8] = {0};
+  const int rank = g.rank = d.rank;
+  const int64_t K = g.K = d.conv_kernel_count, B = g.B = d.batch;
+  g.linear = d.conv_boundary != MI355FFT_CIRCULAR;
+  g.corr = d.conv_mode == MI355FFT_CORRELATION;
   bool ks_given = false;
   for (int i = 0; i < rank; ++i) if (d.conv_kernel_shape[i] != 0) ks_given = true;
   for (int i = 0; i < rank; ++i) {
-    ks[i] = ks_given ? d.conv_kernel_shape[i] : d.shape[i];
-    if (ks[i] <= 0) { err = "fftConv.kernelShape must be an array of " + std::to_string(rank) + " positive ints"; return MI355FFT_ERR_INVALID; }
-    if (d.conv_boundary == MI355FFT_CIRCULAR) {
-      if (ks[i] > d.shape[i]) { err = "fftConv.kernelShape[" + std::to_string(i) + "] must be <= shape[" + std::to_string(i) + "] when fftConv.boundary=\"circular\""; return MI355FFT_ERR_INVALID; }
-      fs[i] = d.shape[i]; os[i] = d.shape[i]; ooff[i] = 0;
+    int64_t &ks = g.ks[i], &fs = g.fs[i], &os = g.os[i], &ooff = g.ooff[i];
+    ks = ks_given ? d.conv_kernel_shape[i] : d.shape[i];
+    if (ks <= 0) { err = "fftConv.kernelShape must be an array of " + std::to_string(rank) + " positive ints"; return MI355FFT_ERR_INVALID; }
+    if (!g.linear) {
+      if (ks > d.shape[i]) { err = "fftConv.kernelShape[" + std::to_string(i) + "] must be <= shape[" + std::to_string(i) + "] when fftConv.boundary=\"circular\""; return MI355FFT_ERR_INVALID; }
+      fs = d.shape[i]; os = d.shape[i]; ooff = 0;
     } else {
-      fs[i] = d.shape[i] + ks[i] - 1;
-      if (d.conv_boundary == MI355FFT_LINEAR_FULL) { os[i] = fs[i]; ooff[i] = 0; }
-      else if (d.conv_boundary == MI355FFT_LINEAR_SAME) { os[i] = d.shape[i]; ooff[i] = (ks[i] - 1) / 2; }
+      fs = d.shape[i] + ks - 1;
+      if (d.conv_boundary == MI355FFT_LINEAR_FULL) { os = fs; ooff = 0; }
+      else if (d.conv_boundary == MI355FFT_LINEAR_SAME) { os = d.shape[i]; ooff = (ks - 1) / 2; }
       else {
-        os[i] = d.shape[i] - ks[i] + 1; ooff[i] = ks[i] - 1;
-        if (os[i] <= 0) { err = "fftConv.boundary=\"linear-valid\" requires kernelShape[" + std::to_string(i) + "] <= shape[" + std::to_string(i) + "]"; return MI355FFT_ERR_INVALID; }
+        os = d.shape[i] - ks + 1; ooff = ks - 1;
+        if (os <= 0) { err = "fftConv.boundary=\"linear-valid\" requires kernelShape[" + std::to_string(i) + "] <= shape[" + std::to_string(i) + "]"; return MI355FFT_ERR_INVALID; }
       }
     }
   }
   // zeroPad ranges live on the FFT domain: read = the embedded data before the forward transform, write = the inverse
   // transform before the crop (fftconv.js:386,542,565)
-  if (int rv = validate_views(d, err, fs, fs)) return rv;
-  const bool zpad = d.zero_read.enabled || d.zero_write.enabled;
-  // Long rank-1 linear modes: the result is cropped out of the FFT domain, so any domain of at least shape + kernelShape - 1 points gives
-  // the same values; the next power of two keeps the transforms off the Bluestein / mixed-radix routes.  Everything the caller states
-  // (zeroPad ranges, output shape and offset) stays on the logical domain [0, lfN).  Padded index k is logical index k below `split`
-  // and k - padD from split + padD on; the padD indices in between belong to no logical index.  Convolution: split = lfN (the padding
-  // is the tail).  Correlation conjugates the kernel spectra, so its kernelShape - 1 negative lags wrap to the TOP of the domain:
-  // split = shape.  pad_lo / pad_hi carry the start / the end of a logical range onto the padded domain.
-  const int64_t lfN = fs[0];
-  int64_t padD = 0;
-  if (b.opt.conv_pad && rank == 1 && d.conv_boundary != MI355FFT_CIRCULAR && lfN > 16384 && lfN <= ((int64_t)1 << 22) && !is_pow2(lfN)) {
-    int64_t P = 32768;
-    while (P < lfN) P <<= 1;
-    padD = P - lfN; fs[0] = P;
-    b.ir.route += "pad[" + std::to_string(lfN) + "->" + std::to_string(P) + "] ";
-  }
-  const int64_t split = d.conv_mode == MI355FFT_CORRELATION ? d.shape[0] : lfN;
-  const auto pad_lo = [&](int64_t m) { return m < split ? m : m + padD; };
-  const auto pad_hi = [&](int64_t e) { return e <= split ? e : e + padD; };
-  const int64_t inN = prodv(d.shape, rank), kN = prodv(ks, rank), fN = prodv(fs, rank), oN = prodv(os, rank);
-  PtrRef in(BUF_INPUT, 0), out(BUF_OUTPUT, 0), kern(BUF_KERNEL, 0);
-  b.ir.kernel_bytes = (uint64_t)K * kN * 8;
-  b.ir.in_bytes = d.input.strided ? strided_extent_elems(d.input, d.shape, rank, B, 0) * 8 : (uint64_t)inN * B * 8;
+  if (int rv = validate_views(d, err, g.fs, g.fs)) return rv;
+  g.lfN = g.fs[0];
+  g.split = g.corr ? d.shape[0] : g.lfN;
+  const int64_t inN = g.inN = prodv(d.shape, rank), kN = g.kN = prodv(g.ks, rank), oN = g.oN = prodv(g.os, rank);
   const int64_t kstride = d.conv_output_kernel_stride_elements;
-  if (d.output.strided) {
-    if (K > 1 && kstride <= 0) { err = "multi-kernel strided output requires fftConv.channelPolicy.output or fftConv.outputKernelStrideElements"; return MI355FFT_ERR_INVALID; }
-    b.ir.out_bytes = strided_extent_elems(d.output, os, rank, B, (K - 1) * kstride) * 8;
-  } else b.ir.out_bytes = (uint64_t)K * B * oN * 8;
+  if (d.output.strided && K > 1 && kstride <= 0) { err = "multi-kernel strided output requires fftConv.channelPolicy.output or fftConv.outputKernelStrideElements"; return MI355FFT_ERR_INVALID; }
+  ir.kernel_bytes = (uint64_t)K * kN * elem;
+  ir.in_bytes = d.input.strided ? strided_extent_elems(d.input, d.shape, rank, B, 0) * elem : (uint64_t)inN * B * elem;
+  ir.out_bytes = d.output.strided ? strided_extent_elems(d.output, g.os, rank, B, (K - 1) * kstride) * elem : (uint64_t)K * B * oN * elem;
+  const bool kmajor = d.conv_output_layout == MI355FFT_KERNEL_MAJOR;
+  g.lane0 = d.output.strided ? d.output.offset_elements : 0;
+  g.lane_k = d.output.strided ? kstride : kmajor ? B * oN : oN;
+  g.lane_b = d.output.strided ? (d.output.batch_stride_elements > 0 ? d.output.batch_stride_elements : oN) : kmajor ? oN : K * oN;
+  return MI355FFT_OK;
+}
+
+// ---- the sides of an fftconv launch as address maps over the domain `dom` (the FFT domain, or the axis-0 line a route is dense over) ----
+// Data: element i is read at offset + sum i_d * stride_d where zeroPad.read meets [0, shape), and is zero elsewhere (the embed)
+SideMap conv_load_map(const mi355fft_plan_desc& d, const ConvGeom& g, const int64_t* dom, int rank) {
+  SideMap m = Builder::dense_map(dom, rank);
+  int64_t st = 1;
+  for (int i = 0; i < rank; ++i) {
+    m.stride[i] = d.input.strided ? d.input.strides[i] : st;
+    st *= d.shape[i];
+    int64_t lo = 0, hi = d.shape[i];
+    if (d.zero_read.enabled) { lo = std::max(lo, d.zero_read.start[i]); hi = std::min(hi, d.zero_read.end[i]); }
+    if (hi < lo) hi = lo;
+    m.lo[i] = (int)lo; m.hi[i] = (int)hi;
+  }
+  m.offset = d.input.strided ? d.input.offset_elements : 0;
+  m.batch_stride = d.input.strided && d.input.batch_stride_elements > 0 ? d.input.batch_stride_elements : g.inN;
+  return m;
+}
+// Kernels: kernelShape zero-padded into the domain
+SideMap conv_kernel_map(const ConvGeom& g, const int64_t* dom, int rank) {
+  SideMap m = Builder::dense_map(dom, rank);
+  int64_t st = 1;
+  for (int i = 0; i < rank; ++i) { m.stride[i] = st; st *= g.ks[i]; m.hi[i] = (int)g.ks[i]; }
+  m.batch_stride = g.kN;
+  return m;
+}
+// Result of kernel k: element i - ooff of its lane is stored for i inside the crop [ooff, ooff + os), as zero outside the
+// zeroPad.write range; both ranges are logical (the VIEW and rconv kernels carry them onto a padded axis themselves)
+SideMap conv_store_map(const mi355fft_plan_desc& d, const ConvGeom& g, const int64_t* dom, int rank, int64_t k) {
+  SideMap m = Builder::dense_map(dom, rank);
+  m.offset = g.lane_offset(k);
+  m.batch_stride = g.lane_b;
+  int64_t st = 1;
+  for (int i = 0; i < rank; ++i) {
+    m.stride[i] = d.output.strided ? d.output.strides[i] : st;
+    st *= g.os[i];
+    m.lo[i] = (int)g.ooff[i]; m.hi[i] = (int)(g.ooff[i] + g.os[i]);
+    m.zlo[i] = d.zero_write.enabled ? (int)d.zero_write.start[i] : 0;
+    m.zhi[i] = d.zero_write.enabled ? (int)d.zero_write.end[i] : (int)(i == 0 ? g.lfN : g.fs[i]);
+    m.offset -= g.ooff[i] * m.stride[i];
+  }
+  return m;
+}
+// The crop as a pass of its own: kernel k's inverse transform `y`, dense over the FFT domain, into its lane of the output
+void conv_staged_crop(Builder& b, const mi355fft_plan_desc& d, const ConvGeom& g, PtrRef out, PtrRef y, int64_t k, bool real_elements) {
+  const int rank = g.rank;
+  const int64_t fN = prodv(g.fs, rank);
+  mi355fft_side_layout lay = d.output;
+  if (!lay.strided) { lay.strided = 1; int64_t st = 1; for (int i = 0; i < rank; ++i) { lay.strides[i] = st; st *= g.os[i]; } }
+  lay.offset_elements = g.lane_offset(k);
+  lay.batch_stride_elements = g.lane_b;
+  int64_t poff[8], s1[8], s2[8], o2[8];
+  for (int i = 0; i < rank; ++i) { poff[i] = o2[i] = g.ooff[i]; s1[i] = s2[i] = g.os[i]; }
+  poff[0] = g.pad_lo(g.ooff[0]);
+  if (!g.straddle()) { b.emit_strided(false, out, y, lay, g.os, rank, g.B, g.fs, poff, fN, 0, real_elements); return; }
+  s1[0] = g.split - g.ooff[0]; s2[0] = g.os[0] - s1[0]; o2[0] = g.split + g.padD;
+  b.emit_strided(false, out, y, lay, s1, rank, g.B, g.fs, poff, fN, 0, real_elements);
+  b.emit_strided(false, out, y, lay, s2, rank, g.B, g.fs, o2, fN, s1[0] * lay.strides[0], real_elements);
+}
+
+// ---- re-basing a finished plan onto workspace staging (f16-storage, rconv-widened) ----
+Step convert_step(StepKind kind, PtrRef src, PtrRef dst, int64_t count, unsigned grid) {
+  Step c;
+  c.kind = kind; c.p[0] = src; c.p[1] = dst; c.i[0] = count; c.grid = grid;
+  return c;
+}
+// Every reference to the caller's input / output / kernel buffer moves to the workspace offset given for it; the converter steps
+// `front` go in front of the plan's steps and `back` behind
+void restage(PlanIR& ir, uint64_t in_stage, uint64_t out_stage, uint64_t kernel_stage, std::vector<Step> front, const std::vector<Step>& back) {
+  for (Step& s : ir.steps)
+    for (PtrRef& p : s.p) {
+      if (p.buf == BUF_INPUT) p = PtrRef(BUF_WORK, (int64_t)in_stage + p.off);
+      else if (p.buf == BUF_OUTPUT) p = PtrRef(BUF_WORK, (int64_t)out_stage + p.off);
+      else if (p.buf == BUF_KERNEL) p = PtrRef(BUF_WORK, (int64_t)kernel_stage + p.off);
+    }
+  front.insert(front.end(), ir.steps.begin(), ir.steps.end());
+  front.insert(front.end(), back.begin(), back.end());
+  ir.steps.swap(front);
+}
+
+// y_k = IFFT( FFT(x) .* (conj?)FFT(h_k) ) / Nfft, cropped per boundary, written per output layout / lanes
+// (runtime/plans/fftconv.js:308-709, exec :1415-1712; reference semantics: src/utils/math.js:469-603)
+int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
+  ConvGeom g;
+  if (int rv = conv_geometry(d, 8, g, b.ir, err)) return rv;
+  const int rank = g.rank;
+  const int64_t K = g.K, B = g.B, inN = g.inN;
+  const int64_t *ks = g.ks, *fs = g.fs, zero[8] = {0};
+  const bool zpad = d.zero_read.enabled || d.zero_write.enabled;
+  // Long rank-1 linear modes: the next power of two keeps the transforms off the Bluestein / mixed-radix routes (ConvGeom)
+  if (b.opt.conv_pad && rank == 1 && g.linear && g.lfN > 16384 && g.lfN <= ((int64_t)1 << 22) && !is_pow2(g.lfN)) {
+    int64_t P = 32768;
+    while (P < g.lfN) P <<= 1;
+    g.pad_axis0(P);
+    b.ir.route += "pad[" + std::to_string(g.lfN) + "->" + std::to_string(P) + "] ";
+  }
+  const int64_t fN = prodv(fs, rank);
+  PtrRef in(BUF_INPUT, 0), out(BUF_OUTPUT, 0), kern(BUF_KERNEL, 0);
 
   // small 1-D circular problems: one launch, one workgroup per batch entry (kern_fftconv.hpp)
   // (throughput-sized problems do better on the line kernels below: measured 49 vs 150 GPoints/s at N=1024, batch 65536)
   const bool lines_mul_ok = b.opt.conv_lines && is_pow2(fN) && fN >= 64 && fN <= b.opt.max_line;
-  if (!b.opt.force_generic && !zpad && rank == 1 && d.conv_boundary == MI355FFT_CIRCULAR && K <= 15 &&
+  if (!b.opt.force_generic && !zpad && rank == 1 && !g.linear && K <= 15 &&
       !(lines_mul_ok && B * fN * K > b.opt.conv_fused_max_points)) {
     const ConvKernelMeta* cm = nullptr;
     for (const auto& m : conv_kernel_registry())
@@ -1720,23 +1785,18 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
       Step& st = b.push(ST_FFTCONV_FUSED);
       st.variant = cm->id;
       st.p[0] = in; st.p[1] = kern; st.p[2] = out; st.p[3] = b.add_table(tw);
-      st.i[0] = B; st.i[1] = K; st.i[2] = ks[0]; st.i[3] = d.conv_mode == MI355FFT_CORRELATION ? 1 : 0;
+      st.i[0] = B; st.i[1] = K; st.i[2] = ks[0]; st.i[3] = g.corr ? 1 : 0;
       st.i[4] = d.input.strided ? d.input.offset_elements : 0;
       st.i[5] = (d.input.strided && d.input.batch_stride_elements > 0) ? d.input.batch_stride_elements : inN;
       st.i[6] = d.input.strided ? d.input.strides[0] : 1;
-      if (d.output.strided) {
-        st.i[7] = d.output.offset_elements; st.i[8] = kstride;
-        st.i[9] = d.output.batch_stride_elements > 0 ? d.output.batch_stride_elements : oN;
-        st.i[10] = d.output.strides[0];
-      } else if (d.conv_output_layout == MI355FFT_KERNEL_MAJOR) { st.i[7] = 0; st.i[8] = B * oN; st.i[9] = oN; st.i[10] = 1; }
-      else { st.i[7] = 0; st.i[8] = oN; st.i[9] = K * oN; st.i[10] = 1; }
+      st.i[7] = g.lane0; st.i[8] = g.lane_k; st.i[9] = g.lane_b; st.i[10] = d.output.strided ? d.output.strides[0] : 1;
       st.f[0] = (float)(1.0 / (double)fN);
       st.grid = (unsigned)std::min<int64_t>(B, (int64_t)b.opt.compute_units * 4);
       b.ir.route += "fftconv-fused[N=" + std::to_string(fN) + ",K=" + std::to_string(K) + ",TL=" + std::to_string(cm->TL) + "] ";
       return MI355FFT_OK;
     }
   }
-  const bool embed = d.conv_boundary != MI355FFT_CIRCULAR;
+  const bool embed = g.linear;
   mi355fft_side_layout dense{};  // strided == 0
   // ---- sides fused into the launches (fftconv.js:353-373): the zero-padded embed of kernels and data, the
   // strided lanes and zeroPad.read ride the first forward axis' loads; zeroPad.write, the crop of the linear modes and the output
@@ -1753,14 +1813,11 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
   for (int i = 0; i < rank; ++i) if (ks[i] != fs[i]) kernel_embed = true;
   int rc;
   if (kernel_embed && map_fwd) {
-    SideMap km = Builder::dense_map(fs, rank);
-    int64_t st = 1;
-    for (int i = 0; i < rank; ++i) { km.stride[i] = st; st *= ks[i]; km.hi[i] = (int)ks[i]; }
-    km.batch_stride = kN;
+    const SideMap km = conv_kernel_map(g, fs, rank);
     rc = b.emit_nd(kern, kf, fs, rank, K, false, 1.0f, err, 0, 0, &km, nullptr);
   } else {
     if (kernel_embed) {
-      Step& z = b.push(ST_ZERO); z.p[0] = kf; z.i[0] = K * fN * 2; z.grid = b.generic_grid(K * fN * 2);
+      b.zero(kf, K * fN * 2);
       b.emit_strided(true, kern, kf, dense, ks, rank, K, fs, zero, fN, 0);
     }
     rc = b.emit_nd(kernel_embed ? kf : kern, kf, fs, rank, K, false, 1.0f, err);
@@ -1772,30 +1829,27 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
   // first loads, crop and zeroPad.write are predicates of its last stores (A reads 8 shape, C writes 8 os bytes per line and kernel)
   if (b.opt.conv_pipeline && !b.opt.force_generic && b.opt.xcd_fused == 1 && b.opt.xcd_shared && !b.opt.only_pass && rank == 1 && fN == ((int64_t)1 << 20) &&
       !d.input.strided && !d.output.strided) {
-    const bool view = d.conv_boundary != MI355FFT_CIRCULAR || zpad;
+    const bool view = g.linear || zpad;
     const XcdKernelMeta* xm = nullptr;
     for (const auto& m : xcd_kernel_registry()) if (m.kind == (view ? XK_CONV_VIEW : XK_CONV)) xm = &m;
     if (xm) {
       Builder::XcdLaunch x = b.xcd_launch(*xm, false, 2 * fN, B);   // two slots per data line in a round (W and W2): Builder::xcd_groups
       x.ta = x.tb = b.line_tables(make_meta(0, 1024, 32, 32, 1, 32, true, true, false, false, 0));
       b.xcd_roots(x, fN);
-      Step& st = b.push_xcd(ST_XCD_FUSED, xm->id, x, in, view ? out.plus(-ooff[0] * 8) : out, B, fN);
-      const bool kmajor = d.conv_output_layout == MI355FFT_KERNEL_MAJOR;
-      st.i[10] = kmajor ? oN : K * oN;        // between data lines
-      st.i[17] = kmajor ? B * oN : oN;        // between the kernels of one data line
-      st.i[14] = kf.off - x.wslots.off; st.i[15] = K; st.i[16] = d.conv_mode == MI355FFT_CORRELATION ? 1 : 0;
+      Step& st = b.push_xcd(ST_XCD_FUSED, xm->id, x, in, view ? out.plus(-g.ooff[0] * 8) : out, B, fN);
+      st.i[10] = g.lane_b;                    // between data lines
+      st.i[17] = g.lane_k;                    // between the kernels of one data line
+      st.i[14] = kf.off - x.wslots.off; st.i[15] = K; st.i[16] = g.corr ? 1 : 0;
       st.f[0] = (float)(1.0 / (double)fN);
       if (view) {
         st.i[9] = inN;                        // the data lines keep their own length: nothing is embedded
-        int64_t lo = 0, hi = d.shape[0];
-        if (d.zero_read.enabled) { lo = std::max(lo, d.zero_read.start[0]); hi = std::min(hi, d.zero_read.end[0]); }
-        if (hi < lo) hi = lo;
-        st.imap = st.omap = Builder::dense_map(fs, rank);
-        st.imap.lo[0] = (int)lo; st.imap.hi[0] = (int)hi;
-        st.omap.lo[0] = (int)ooff[0]; st.omap.hi[0] = (int)(ooff[0] + os[0]);      // logical, as the zeroPad.write range
-        st.omap.zlo[0] = d.zero_write.enabled ? (int)d.zero_write.start[0] : 0;
-        st.omap.zhi[0] = d.zero_write.enabled ? (int)d.zero_write.end[0] : (int)lfN;
-        st.i[18] = split; st.i[19] = padD;
+        // the launch addresses both sides itself (the pitches above, `out - ooff` as its pointer): its maps carry the ranges
+        // only and stay dense over the domain
+        st.imap = conv_load_map(d, g, fs, rank);
+        st.omap = conv_store_map(d, g, fs, rank, 0);
+        st.omap.offset = 0;
+        st.imap.batch_stride = st.omap.batch_stride = fN;
+        st.i[18] = g.split; st.i[19] = g.padD;
         b.ir.route += "fftconv-pipeline-view[N=1024x1024,K=" + std::to_string(K) + "] ";
       } else b.ir.route += "fftconv-pipeline[N=1024x1024,K=" + std::to_string(K) + "] ";
       return MI355FFT_OK;
@@ -1805,22 +1859,9 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
   PtrRef xf = b.alloc_work((uint64_t)B * fN * 8);
   const bool side_in = embed || d.input.strided || d.zero_read.enabled;
   const bool fuse_in = side_in && map_fwd;
-  SideMap xmap;
-  if (fuse_in) {
-    xmap = Builder::dense_map(fs, rank);
-    int64_t st = 1;
-    for (int i = 0; i < rank; ++i) {
-      xmap.stride[i] = d.input.strided ? d.input.strides[i] : st;
-      st *= d.shape[i];
-      int64_t lo = 0, hi = d.shape[i];
-      if (d.zero_read.enabled) { lo = std::max(lo, d.zero_read.start[i]); hi = std::min(hi, d.zero_read.end[i]); }
-      if (hi < lo) hi = lo;
-      xmap.lo[i] = (int)lo; xmap.hi[i] = (int)hi;
-    }
-    xmap.offset = d.input.strided ? d.input.offset_elements : 0;
-    xmap.batch_stride = d.input.strided && d.input.batch_stride_elements > 0 ? d.input.batch_stride_elements : inN;
-  } else {
-    if (embed) { Step& z = b.push(ST_ZERO); z.p[0] = xf; z.i[0] = B * fN * 2; z.grid = b.generic_grid(B * fN * 2); }
+  const SideMap xmap = fuse_in ? conv_load_map(d, g, fs, rank) : SideMap();
+  if (!fuse_in) {
+    if (embed) b.zero(xf, B * fN * 2);
     if (embed || d.input.strided) b.emit_strided(true, in, xf, d.input, d.shape, rank, B, fs, zero, fN, 0);
     else if (d.zero_read.enabled) { Step& c = b.push(ST_COPY); c.p[0] = in; c.p[1] = xf; c.i[0] = B * fN * 8; }
     if (d.zero_read.enabled) { emit_zero_outside(b, xf, d.zero_read, fs, rank, B); b.ir.route += "zero-read "; }
@@ -1842,23 +1883,9 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
   // 3. per kernel: product, inverse transform scaled by 1/Nfft, crop + place
   PtrRef y = b.alloc_work((uint64_t)B * fN * 8);
   const float inv_n = (float)(1.0 / (double)fN);
-  const bool direct_out = !embed && !d.output.strided;   // the inverse FFT can land in the output itself
+  const bool direct_out = !embed && !d.output.strided && d.conv_output_layout == MI355FFT_KERNEL_MAJOR;   // the inverse FFT can land in the output itself
   const bool side_out = embed || d.output.strided || d.zero_write.enabled || d.conv_output_layout != MI355FFT_KERNEL_MAJOR;
-  const bool fuse_out = side_out && map_inv && padD == 0;
-  // padded domain: the zeroPad.write range as ONE padded range (what lies between its two images is never extracted), the crop from
-  // its padded offset — in two pieces where it holds both positive and negative lags of a correlation
-  mi355fft_zero_range zw = d.zero_write;
-  int64_t poff[8];
-  for (int i = 0; i < rank; ++i) poff[i] = ooff[i];
-  if (padD) { zw.start[0] = pad_lo(zw.start[0]); zw.end[0] = pad_hi(zw.end[0]); poff[0] = pad_lo(ooff[0]); }
-  const bool straddle = padD > 0 && ooff[0] < split && ooff[0] + os[0] > split;
-  const auto extract = [&](mi355fft_side_layout lay, int64_t extra) {
-    if (!straddle) { b.emit_strided(false, out, y, lay, os, rank, B, fs, poff, fN, extra); return; }
-    const int64_t n1 = split - ooff[0], n2 = os[0] - n1, o2 = split + padD;
-    if (lay.batch_stride_elements <= 0) lay.batch_stride_elements = oN;
-    b.emit_strided(false, out, y, lay, &n1, 1, B, fs, ooff, fN, extra);
-    b.emit_strided(false, out, y, lay, &n2, 1, B, fs, &o2, fN, extra + n1 * lay.strides[0]);
-  };
+  const bool fuse_out = side_out && map_inv && g.padD == 0;
   for (int64_t k = 0; k < K; ++k) {
     if (mul_m) {
       Step& st = b.push(ST_LINES);
@@ -1866,7 +1893,7 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
       st.p[0] = staged ? xf : in; st.p[1] = y; st.p[2] = mul_tables; st.p[3] = kf.plus(k * fN * 8);
       const int64_t tiles = (B + mul_m->T - 1) / mul_m->T;
       st.i[0] = tiles; st.i[1] = B; st.i[2] = 1; st.i[3] = fN; st.i[4] = 1; st.i[5] = fN;
-      st.i[6] = d.conv_mode == MI355FFT_CORRELATION ? 1 : 0; st.i[9] = 4;
+      st.i[6] = g.corr ? 1 : 0; st.i[9] = 4;
       st.f[0] = 1.0f;
       st.grid = b.lines_grid(*mul_m, tiles);
       if (fuse_in) { st.i[10] = 1; st.imap = xmap; st.imap.ax = 0; st.omap = Builder::dense_map(fs, rank); }
@@ -1874,48 +1901,26 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
     } else {
       Step& pm = b.push(ST_POINTWISE);
       pm.p[0] = xf; pm.p[1] = y; pm.p[2] = kf.plus(k * fN * 8);
-      pm.i[0] = fN; pm.i[1] = B * fN; pm.i[2] = d.conv_mode == MI355FFT_CORRELATION ? 1 : 0; pm.f[0] = 1.0f;
+      pm.i[0] = fN; pm.i[1] = B * fN; pm.i[2] = g.corr ? 1 : 0; pm.f[0] = 1.0f;
       pm.grid = b.generic_grid(B * fN);
     }
     if (fuse_out) {
-      // output element (i - ooff) of the cropped result, lane of kernel k (fftconv.js:868-871), zeroPad.write on the FFT domain
-      SideMap om = Builder::dense_map(fs, rank);
-      int64_t st = 1;
-      for (int i = 0; i < rank; ++i) {
-        om.stride[i] = d.output.strided ? d.output.strides[i] : st;
-        st *= os[i];
-        om.lo[i] = (int)ooff[i]; om.hi[i] = (int)(ooff[i] + os[i]);
-        if (d.zero_write.enabled) { om.zlo[i] = (int)d.zero_write.start[i]; om.zhi[i] = (int)d.zero_write.end[i]; }
-      }
-      if (d.output.strided) { om.offset = d.output.offset_elements + k * kstride; om.batch_stride = d.output.batch_stride_elements > 0 ? d.output.batch_stride_elements : oN; }
-      else if (d.conv_output_layout == MI355FFT_KERNEL_MAJOR) { om.offset = k * B * oN; om.batch_stride = oN; }
-      else { om.offset = k * oN; om.batch_stride = K * oN; }
-      for (int i = 0; i < rank; ++i) om.offset -= ooff[i] * om.stride[i];
+      const SideMap om = conv_store_map(d, g, fs, rank, k);
       rc = b.emit_nd(y, y, fs, rank, B, true, inv_n, err, 0, 0, nullptr, &om, out);
       if (rc) return rc;
       continue;
     }
-    if (direct_out && d.conv_output_layout == MI355FFT_KERNEL_MAJOR) {
-      rc = b.emit_nd(y, out.plus(k * B * oN * 8), fs, rank, B, true, inv_n, err);
+    if (direct_out) {
+      const PtrRef lane = out.plus(g.lane_offset(k) * 8);
+      rc = b.emit_nd(y, lane, fs, rank, B, true, inv_n, err);
       if (rc) return rc;
-      if (d.zero_write.enabled) emit_zero_outside(b, out.plus(k * B * oN * 8), d.zero_write, fs, rank, B);
+      if (d.zero_write.enabled) emit_zero_outside(b, lane, d.zero_write, fs, rank, B);
       continue;
     }
     rc = b.emit_nd(y, y, fs, rank, B, true, inv_n, err);
     if (rc) return rc;
-    if (d.zero_write.enabled) emit_zero_outside(b, y, zw, fs, rank, B);
-    if (d.output.strided) {
-      // lane of kernel k: outputOffset + k*kernelStride + b*batchStride (fftconv.js:868-871)
-      extract(d.output, k * kstride);
-    } else {
-      mi355fft_side_layout ol{};
-      ol.strided = 1;
-      int64_t st = 1;
-      for (int i = 0; i < rank; ++i) { ol.strides[i] = st; st *= os[i]; }
-      if (d.conv_output_layout == MI355FFT_KERNEL_MAJOR) { ol.offset_elements = k * B * oN; ol.batch_stride_elements = oN; }
-      else { ol.offset_elements = k * oN; ol.batch_stride_elements = K * oN; }
-      extract(ol, 0);
-    }
+    if (d.zero_write.enabled) emit_zero_outside(b, y, g.padded(d.zero_write), fs, rank, B);
+    conv_staged_crop(b, d, g, out, y, k, false);
   }
   if (d.zero_write.enabled && !fuse_out) b.ir.route += "zero-write ";
   b.ir.route += "fftconv[K=" + std::to_string(K) + "] ";
@@ -1935,46 +1940,17 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
 //                     emitters on kernels and data, then per kernel a pointwise pass over the packed bins, the inverse, zeroPad.write
 //                     and the real crop
 //   rconv-widened     circular with odd shape[0] (no even domain is allowed): the complex plan between widening / narrowing passes
-// The padded-domain index map (split, padD) is build_fftconv's, on axis 0.
+// Validation, shapes, lanes and the padded-domain index map are ConvGeom's, shared with build_fftconv; each route hands it the
+// axis-0 length it transforms on.
 int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
-  if (d.io_input.enabled || d.io_output.enabled) { err = "ioView is not an fftconv option"; return MI355FFT_ERR_INVALID; }
-  if (d.in_place) { err = "fftconv inPlace=true is not supported in current implementation"; return MI355FFT_ERR_INVALID; }
-  if (d.conv_mode != MI355FFT_CONVOLUTION && d.conv_mode != MI355FFT_CORRELATION) { err = "fftConv.mode must be one of \"convolution\", \"correlation\""; return MI355FFT_ERR_INVALID; }
-  if (d.conv_boundary < 0 || d.conv_boundary > 3) { err = "fftConv.boundary must be one of \"circular\", \"linear-full\", \"linear-same\", \"linear-valid\""; return MI355FFT_ERR_INVALID; }
-  if (d.conv_kernel_count <= 0) { err = "fftConv.kernelCount must be a positive integer; got " + std::to_string(d.conv_kernel_count); return MI355FFT_ERR_INVALID; }
-  const int rank = d.rank;
-  const int64_t K = d.conv_kernel_count, B = d.batch;
-  const bool linear = d.conv_boundary != MI355FFT_CIRCULAR, corr = d.conv_mode == MI355FFT_CORRELATION;
-  int64_t ks[8], fs[8], os[8], ooff[8], zero[8] = {0};
-  bool ks_given = false;
-  for (int i = 0; i < rank; ++i) if (d.conv_kernel_shape[i] != 0) ks_given = true;
-  for (int i = 0; i < rank; ++i) {
-    ks[i] = ks_given ? d.conv_kernel_shape[i] : d.shape[i];
-    if (ks[i] <= 0) { err = "fftConv.kernelShape must be an array of " + std::to_string(rank) + " positive ints"; return MI355FFT_ERR_INVALID; }
-    if (!linear) {
-      if (ks[i] > d.shape[i]) { err = "fftConv.kernelShape[" + std::to_string(i) + "] must be <= shape[" + std::to_string(i) + "] when fftConv.boundary=\"circular\""; return MI355FFT_ERR_INVALID; }
-      fs[i] = d.shape[i]; os[i] = d.shape[i]; ooff[i] = 0;
-    } else {
-      fs[i] = d.shape[i] + ks[i] - 1;
-      if (d.conv_boundary == MI355FFT_LINEAR_FULL) { os[i] = fs[i]; ooff[i] = 0; }
-      else if (d.conv_boundary == MI355FFT_LINEAR_SAME) { os[i] = d.shape[i]; ooff[i] = (ks[i] - 1) / 2; }
-      else {
-        os[i] = d.shape[i] - ks[i] + 1; ooff[i] = ks[i] - 1;
-        if (os[i] <= 0) { err = "fftConv.boundary=\"linear-valid\" requires kernelShape[" + std::to_string(i) + "] <= shape[" + std::to_string(i) + "]"; return MI355FFT_ERR_INVALID; }
-      }
-    }
-  }
-  if (int rv = validate_views(d, err, fs, fs)) return rv;
-  const int64_t lfN = fs[0];
-  const int64_t inN = prodv(d.shape, rank), kN = prodv(ks, rank), oN = prodv(os, rank);
-  const int64_t kstride = d.conv_output_kernel_stride_elements;
+  ConvGeom g;
+  if (int rv = conv_geometry(d, 4, g, b.ir, err)) return rv;
+  const int rank = g.rank;
+  const int64_t K = g.K, B = g.B, inN = g.inN, kN = g.kN, oN = g.oN, lfN = g.lfN;
+  const bool linear = g.linear, corr = g.corr;
+  const int64_t *ks = g.ks, *fs = g.fs, zero[8] = {0};
   const bool strided = d.input.strided || d.output.strided;
   const PtrRef in(BUF_INPUT, 0), out(BUF_OUTPUT, 0), kern(BUF_KERNEL, 0);
-  if (d.output.strided && K > 1 && kstride <= 0) { err = "multi-kernel strided output requires fftConv.channelPolicy.output or fftConv.outputKernelStrideElements"; return MI355FFT_ERR_INVALID; }
-  b.ir.kernel_bytes = (uint64_t)K * kN * 4;
-  b.ir.in_bytes = d.input.strided ? strided_extent_elems(d.input, d.shape, rank, B, 0) * 4 : (uint64_t)inN * B * 4;
-  b.ir.out_bytes = d.output.strided ? strided_extent_elems(d.output, os, rank, B, (K - 1) * kstride) * 4 : (uint64_t)K * B * oN * 4;
-  const int64_t split = corr ? d.shape[0] : lfN;
 
   // ---- route 1: one launch per kernel on the line kernels --------------------------------------------------------------------
   int64_t P1 = 0;
@@ -1987,13 +1963,13 @@ int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err
   const bool route1 = b.opt.rconv_fused == 2 || (b.opt.rconv_fused == 1 && (P1 <= 8192 || strided));
   const LineKernelMeta* rm = (P1 && route1) ? b.lines_r2c_kernel(P1, false, true) : nullptr;
   if (rm) {
-    const int64_t P = P1, H = P / 2, padD = P - lfN;
-    if (padD) b.ir.route += "pad[" + std::to_string(lfN) + "->" + std::to_string(P) + "] ";
-    const int64_t pf[1] = {P}, pp[1] = {H + 1};
+    const int64_t P = P1, H = P / 2;
+    g.pad_axis0(P);
+    if (g.padD) b.ir.route += "pad[" + std::to_string(lfN) + "->" + std::to_string(P) + "] ";
+    const int64_t pp[1] = {H + 1};
     // the K kernels, zero-embedded kN -> P by the load predicate, as packed spectra in the workspace
     const PtrRef G = b.alloc_work((uint64_t)K * (H + 1) * 8);
-    SideMap km = Builder::dense_map(pf, 1), gm = Builder::dense_map(pp, 1);
-    km.hi[0] = (int)ks[0]; km.batch_stride = kN;
+    const SideMap km = conv_kernel_map(g, fs, 1), gm = Builder::dense_map(pp, 1);
     if (!b.emit_lines_r2c(kern, G, P, K, 1.0f, false, 0, &km, &gm)) { err = "no mapped r2c line kernel"; return MI355FFT_ERR_UNSUPPORTED; }
     const PtrRef tables = b.line_tables(*rm);
     // e^{-2 pi i k/P} = HI[k >> 10] LO[k & 1023], the HI factors directly behind the 1024 LO factors (one table: dispatch.hpp)
@@ -2001,34 +1977,16 @@ int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err
     for (int64_t l = 0; l < 1024; ++l) roots[(size_t)l] = root_of_unity(l, P);
     for (size_t h = 1024; h < roots.size(); ++h) roots[h] = root_of_unity((int64_t)(h - 1024) << 10, P);
     const PtrRef proots = b.add_table(roots);
-    SideMap xm = Builder::dense_map(pf, 1);
-    {
-      int64_t lo = 0, hi = d.shape[0];
-      if (d.zero_read.enabled) { lo = std::max(lo, d.zero_read.start[0]); hi = std::min(hi, d.zero_read.end[0]); }
-      if (hi < lo) hi = lo;
-      xm.lo[0] = (int)lo; xm.hi[0] = (int)hi;
-      xm.stride[0] = d.input.strided ? d.input.strides[0] : 1;
-      xm.offset = d.input.strided ? d.input.offset_elements : 0;
-      xm.batch_stride = d.input.strided && d.input.batch_stride_elements > 0 ? d.input.batch_stride_elements : inN;
-    }
+    const SideMap xm = conv_load_map(d, g, fs, 1);
     const int64_t tiles = (B + rm->T - 1) / rm->T;
     for (int64_t k = 0; k < K; ++k) {
-      SideMap om = Builder::dense_map(pf, 1);
-      om.lo[0] = (int)ooff[0]; om.hi[0] = (int)(ooff[0] + os[0]);             // logical, as the zeroPad.write range
-      om.zlo[0] = d.zero_write.enabled ? (int)d.zero_write.start[0] : 0;
-      om.zhi[0] = d.zero_write.enabled ? (int)d.zero_write.end[0] : (int)lfN;
-      om.stride[0] = d.output.strided ? d.output.strides[0] : 1;
-      if (d.output.strided) { om.offset = d.output.offset_elements + k * kstride; om.batch_stride = d.output.batch_stride_elements > 0 ? d.output.batch_stride_elements : oN; }
-      else if (d.conv_output_layout == MI355FFT_KERNEL_MAJOR) { om.offset = k * B * oN; om.batch_stride = oN; }
-      else { om.offset = k * oN; om.batch_stride = K * oN; }
-      om.offset -= ooff[0] * om.stride[0];
       Step& st = b.push(ST_LINES);
       st.variant = rm->id;
       st.p[0] = in; st.p[1] = out; st.p[2] = tables; st.p[3] = proots; st.p[4] = G.plus(k * (H + 1) * 8);
       st.i[0] = tiles; st.i[1] = B; st.i[2] = 1; st.i[3] = H; st.i[4] = 1; st.i[5] = H; st.i[6] = 10; st.i[7] = 1023;
-      st.i[9] = 9; st.i[10] = 1; st.i[12] = corr ? 1 : 0; st.i[13] = split; st.i[14] = padD;
+      st.i[9] = 9; st.i[10] = 1; st.i[12] = corr ? 1 : 0; st.i[13] = g.split; st.i[14] = g.padD;
       st.f[0] = (float)(1.0 / (double)P);
-      st.imap = xm; st.omap = om;
+      st.imap = xm; st.omap = conv_store_map(d, g, fs, 1, k);
       st.grid = b.lines_grid(*rm, tiles);
     }
     b.ir.route += "lines-rconv[N=" + std::to_string(P) + "] ";
@@ -2045,23 +2003,10 @@ int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err
     const uint64_t in_c = (uint64_t)B * inN * 8, k_c = (uint64_t)K * kN * 8, out_c = (uint64_t)K * B * oN * 8;
     const uint64_t in_stage = align_up(ir.work_bytes, 256), k_stage = align_up(in_stage + in_c, 256), out_stage = align_up(k_stage + k_c, 256);
     ir.work_bytes = align_up(out_stage + out_c, 256);
-    for (Step& s : ir.steps)
-      for (PtrRef& p : s.p) {
-        if (p.buf == BUF_INPUT) p = PtrRef(BUF_WORK, (int64_t)in_stage + p.off);
-        else if (p.buf == BUF_KERNEL) p = PtrRef(BUF_WORK, (int64_t)k_stage + p.off);
-        else if (p.buf == BUF_OUTPUT) p = PtrRef(BUF_WORK, (int64_t)out_stage + p.off);
-      }
-    std::vector<Step> steps;
-    const auto convert = [&](StepKind kind, PtrRef src, PtrRef dst, int64_t count) {
-      Step c;
-      c.kind = kind; c.p[0] = src; c.p[1] = dst; c.i[0] = count; c.f[0] = 1.0f; c.grid = b.generic_grid(count);
-      steps.push_back(c);
-    };
-    convert(ST_REAL_TO_COMPLEX, in, PtrRef(BUF_WORK, (int64_t)in_stage), B * inN);
-    convert(ST_REAL_TO_COMPLEX, kern, PtrRef(BUF_WORK, (int64_t)k_stage), K * kN);
-    steps.insert(steps.end(), ir.steps.begin(), ir.steps.end());
-    convert(ST_COMPLEX_TO_REAL, PtrRef(BUF_WORK, (int64_t)out_stage), out, K * B * oN);
-    ir.steps.swap(steps);
+    const auto convert = [&](StepKind kind, PtrRef src, PtrRef dst, int64_t count) { return convert_step(kind, src, dst, count, b.generic_grid(count)); };
+    restage(ir, in_stage, out_stage, k_stage,
+            {convert(ST_REAL_TO_COMPLEX, in, PtrRef(BUF_WORK, (int64_t)in_stage), B * inN), convert(ST_REAL_TO_COMPLEX, kern, PtrRef(BUF_WORK, (int64_t)k_stage), K * kN)},
+            {convert(ST_COMPLEX_TO_REAL, PtrRef(BUF_WORK, (int64_t)out_stage), out, K * B * oN)});
     ir.in_bytes = in_c / 2; ir.kernel_bytes = k_c / 2; ir.out_bytes = out_c / 2;
     ir.route = "rconv-widened " + ir.route;
     return MI355FFT_OK;
@@ -2071,13 +2016,11 @@ int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err
   // rank-1 linear requests take the next power of two (any domain >= lfN gives the same cropped values, and the half-length transforms
   // stay off the mixed-radix / Bluestein routes); other linear requests round axis 0 up to an even length
   if (linear) {
-    if (rank == 1 && b.opt.conv_pad && lfN <= ((int64_t)1 << 22)) { int64_t P = 2; while (P < lfN) P <<= 1; fs[0] = P; }
-    else fs[0] = lfN + (lfN & 1);
+    int64_t P = lfN + (lfN & 1);
+    if (rank == 1 && b.opt.conv_pad && lfN <= ((int64_t)1 << 22)) { P = 2; while (P < lfN) P <<= 1; }
+    g.pad_axis0(P);
   }
-  const int64_t padD = fs[0] - lfN;
-  if (padD) b.ir.route += "pad[" + std::to_string(lfN) + "->" + std::to_string(fs[0]) + "] ";
-  const auto pad_lo = [&](int64_t m) { return m < split ? m : m + padD; };
-  const auto pad_hi = [&](int64_t e) { return e <= split ? e : e + padD; };
+  if (g.padD) b.ir.route += "pad[" + std::to_string(lfN) + "->" + std::to_string(fs[0]) + "] ";
   int64_t ps[8];
   for (int i = 0; i < rank; ++i) ps[i] = fs[i];
   ps[0] = fs[0] / 2 + 1;
@@ -2085,17 +2028,13 @@ int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err
   const bool mapped0 = rank == 1 && fN < ((int64_t)1 << 31) && b.lines_r2c_kernel(F0, false, true) != nullptr;
   mi355fft_side_layout dense{};
   int rc;
-  // real lines [count][shape] -> packed spectra [count][ps]: embedded into the FFT domain (zeros elsewhere), restricted to `zr`
-  const auto forward = [&](PtrRef src, PtrRef dst, const int64_t* shp, int64_t count, const mi355fft_zero_range* zr) -> int {
+  // real lines [count][shape] -> packed spectra [count][ps]: embedded into the FFT domain (zeros elsewhere), restricted to `zr`;
+  // `im`: the same as the address map of a line launch
+  const auto forward = [&](PtrRef src, PtrRef dst, const int64_t* shp, int64_t count, const mi355fft_zero_range* zr, const SideMap& im) -> int {
     bool emb = false;
     for (int i = 0; i < rank; ++i) if (shp[i] != fs[i]) emb = true;
-    const int64_t n = prodv(shp, rank);
     if ((emb || zr) && mapped0) {
-      SideMap im = Builder::dense_map(fs, 1), om = Builder::dense_map(ps, 1);
-      int64_t lo = 0, hi = shp[0];
-      if (zr) { lo = std::max(lo, zr->start[0]); hi = std::min(hi, zr->end[0]); }
-      if (hi < lo) hi = lo;
-      im.lo[0] = (int)lo; im.hi[0] = (int)hi; im.batch_stride = n;
+      const SideMap om = Builder::dense_map(ps, 1);
       if (!b.emit_lines_r2c(src, dst, F0, count, 1.0f, false, 0, &im, &om)) { err = "no mapped r2c line kernel"; return MI355FFT_ERR_UNSUPPORTED; }
       return MI355FFT_OK;
     }
@@ -2103,13 +2042,11 @@ int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err
     if (emb || zr) {
       const PtrRef xr = b.alloc_work((uint64_t)count * fN * 4);
       if (emb) {
-        Step& z = b.push(ST_ZERO); z.p[0] = xr; z.i[0] = count * fN; z.grid = b.generic_grid(count * fN);
+        b.zero(xr, count * fN);
         b.emit_strided(true, src, xr, dense, shp, rank, count, fs, zero, fN, 0, true);
       } else { Step& c = b.push(ST_COPY); c.p[0] = src; c.p[1] = xr; c.i[0] = count * fN * 4; }
       if (zr) {
-        mi355fft_zero_range z2 = *zr;
-        z2.start[0] = pad_lo(z2.start[0]); z2.end[0] = pad_hi(z2.end[0]);
-        emit_zero_outside(b, xr, z2, fs, rank, count, true);
+        emit_zero_outside(b, xr, g.padded(*zr), fs, rank, count, true);
         b.ir.route += "zero-read ";
       }
       cur = xr;
@@ -2119,42 +2056,23 @@ int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err
     return MI355FFT_OK;
   };
   const PtrRef kf = b.alloc_work((uint64_t)K * pN * 8);
-  if ((rc = forward(kern, kf, ks, K, nullptr))) return rc;
+  if ((rc = forward(kern, kf, ks, K, nullptr, conv_kernel_map(g, fs, 1)))) return rc;
   const PtrRef xf = b.alloc_work((uint64_t)B * pN * 8);
-  if ((rc = forward(in, xf, d.shape, B, d.zero_read.enabled ? &d.zero_read : nullptr))) return rc;
+  if ((rc = forward(in, xf, d.shape, B, d.zero_read.enabled ? &d.zero_read : nullptr, conv_load_map(d, g, fs, 1)))) return rc;
   const PtrRef y = b.alloc_work((uint64_t)B * pN * 8);
   const bool direct_out = !linear && d.conv_output_layout == MI355FFT_KERNEL_MAJOR;     // the real inverse can land in the output itself
   const PtrRef yr = direct_out ? PtrRef() : b.alloc_work((uint64_t)B * fN * 4);
   const float inv_n = (float)(1.0 / (double)fN);
-  mi355fft_zero_range zw = d.zero_write;
-  int64_t poff[8];
-  for (int i = 0; i < rank; ++i) poff[i] = ooff[i];
-  if (padD) { zw.start[0] = pad_lo(zw.start[0]); zw.end[0] = pad_hi(zw.end[0]); poff[0] = pad_lo(ooff[0]); }
-  const bool straddle = padD > 0 && ooff[0] < split && ooff[0] + os[0] > split;
   for (int64_t k = 0; k < K; ++k) {
     Step& pm = b.push(ST_POINTWISE);
     pm.p[0] = xf; pm.p[1] = y; pm.p[2] = kf.plus(k * pN * 8);
     pm.i[0] = pN; pm.i[1] = B * pN; pm.i[2] = corr ? 1 : 0; pm.f[0] = 1.0f;
     pm.grid = b.generic_grid(B * pN);
     if (rank > 1 && (rc = b.emit_nd(y, y, ps, rank, B, true, 1.0f, err, 1))) return rc;
-    const PtrRef dst = direct_out ? out.plus(k * B * oN * 4) : yr;
+    const PtrRef dst = direct_out ? out.plus(g.lane_offset(k) * 4) : yr;
     if ((rc = b.emit_c2r_even(y, dst, F0, B * (fN / F0), inv_n, err))) return rc;
-    if (d.zero_write.enabled) emit_zero_outside(b, dst, zw, fs, rank, B, true);
-    if (direct_out) continue;
-    mi355fft_side_layout ol{};
-    ol.strided = 1;
-    int64_t st = 1;
-    for (int i = 0; i < rank; ++i) { ol.strides[i] = st; st *= os[i]; }
-    if (d.conv_output_layout == MI355FFT_KERNEL_MAJOR) { ol.offset_elements = k * B * oN; ol.batch_stride_elements = oN; }
-    else { ol.offset_elements = k * oN; ol.batch_stride_elements = K * oN; }
-    if (!straddle) b.emit_strided(false, out, yr, ol, os, rank, B, fs, poff, fN, 0, true);
-    else {   // positive and negative lags of a correlation: two pieces of the padded domain
-      int64_t s1[8], s2[8], o2[8];
-      for (int i = 0; i < rank; ++i) { s1[i] = s2[i] = os[i]; o2[i] = poff[i]; }
-      s1[0] = split - ooff[0]; s2[0] = os[0] - s1[0]; o2[0] = split + padD;
-      b.emit_strided(false, out, yr, ol, s1, rank, B, fs, poff, fN, 0, true);
-      b.emit_strided(false, out, yr, ol, s2, rank, B, fs, o2, fN, s1[0] * ol.strides[0], true);
-    }
+    if (d.zero_write.enabled) emit_zero_outside(b, dst, g.padded(d.zero_write), fs, rank, B, true);
+    if (!direct_out) conv_staged_crop(b, d, g, out, yr, k, true);
   }
   if (d.zero_write.enabled) b.ir.route += "zero-write ";
   b.ir.route += "rconv[K=" + std::to_string(K) + "] ";
@@ -2200,23 +2118,12 @@ void wrap_f16_storage(const mi355fft_plan_desc& d, PlanIR& ir) {
   const uint64_t in_stage = align_up(ir.work_bytes, 256);
   const uint64_t out_stage = d.in_place ? in_stage : align_up(in_stage + in32, 256);
   ir.work_bytes = d.in_place ? align_up(in_stage + in32, 256) : align_up(out_stage + out32, 256);
-  for (Step& s : ir.steps)
-    for (PtrRef& p : s.p) {
-      if (p.buf == BUF_INPUT) p = PtrRef(BUF_WORK, (int64_t)in_stage + p.off);
-      else if (p.buf == BUF_OUTPUT) p = PtrRef(BUF_WORK, (int64_t)out_stage + p.off);
-    }
-  std::vector<Step> steps;
-  const auto convert = [&](StepKind kind, PtrRef src, PtrRef dst, uint64_t scalars) {
-    Step c;
-    c.kind = kind; c.p[0] = src; c.p[1] = dst; c.i[0] = (int64_t)scalars; c.grid = grid((int64_t)scalars);
-    steps.push_back(c);
-  };
-  convert(ST_F16_TO_F32, PtrRef(BUF_INPUT, 0), PtrRef(BUF_WORK, (int64_t)in_stage), in32 / 4);
+  const auto convert = [&](StepKind kind, PtrRef src, PtrRef dst, uint64_t scalars) { return convert_step(kind, src, dst, (int64_t)scalars, grid((int64_t)scalars)); };
   const bool keep_out = d.io_output.enabled && !d.io_output.clear_outside;
-  if (keep_out) convert(ST_F16_TO_F32, PtrRef(BUF_OUTPUT, 0), PtrRef(BUF_WORK, (int64_t)out_stage), out32 / 4);
-  steps.insert(steps.end(), ir.steps.begin(), ir.steps.end());
-  convert(ST_F32_TO_F16, PtrRef(BUF_WORK, (int64_t)out_stage), PtrRef(d.in_place ? BUF_INPUT : BUF_OUTPUT, 0), out32 / 4);
-  ir.steps.swap(steps);
+  std::vector<Step> front{convert(ST_F16_TO_F32, PtrRef(BUF_INPUT, 0), PtrRef(BUF_WORK, (int64_t)in_stage), in32 / 4)};
+  if (keep_out) front.push_back(convert(ST_F16_TO_F32, PtrRef(BUF_OUTPUT, 0), PtrRef(BUF_WORK, (int64_t)out_stage), out32 / 4));
+  restage(ir, in_stage, out_stage, 0, front,
+          {convert(ST_F32_TO_F16, PtrRef(BUF_WORK, (int64_t)out_stage), PtrRef(d.in_place ? BUF_INPUT : BUF_OUTPUT, 0), out32 / 4)});
   ir.route = std::string(keep_out ? "f16-in+out " : "f16-in ") + ir.route + "f16-out ";
 }
 
