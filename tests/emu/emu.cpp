@@ -158,9 +158,11 @@ int emu_check_xcd_registry(char* msg, size_t msg_bytes) {
 // Plans `desc` and runs it on host buffers.  input/output/kernel are host pointers of at least the byte
 // extents the plan reports (checked).  output == NULL for in-place plans.  Returns the planner status or
 // 100+ for harness errors; err receives the message; route (optional) the plan's route string.
-int emu_run_plan(const mi355fft_plan_desc* desc, void* input, uint64_t input_bytes, void* output, uint64_t output_bytes, void* kernel,
-                 uint64_t kernel_bytes, int force_generic, uint64_t chunk_bytes, char* err, size_t err_bytes, char* route, size_t route_bytes,
-                 int* launches) {
+// input == NULL plans only.  work_fill: the byte the workspace (and its 256 spare bytes) is filled with before the first launch; tail_modified (optional) is set
+// when a launch changed one of the spare bytes behind the workspace.
+int emu_run_plan_ex(const mi355fft_plan_desc* desc, void* input, uint64_t input_bytes, void* output, uint64_t output_bytes, void* kernel,
+                    uint64_t kernel_bytes, int force_generic, uint64_t chunk_bytes, int work_fill, int* tail_modified, char* err, size_t err_bytes,
+                    char* route, size_t route_bytes, int* launches) {
   using namespace mi355;
   PlannerOptions opt;
   opt.force_generic = force_generic;
@@ -191,14 +193,22 @@ int emu_run_plan(const mi355fft_plan_desc* desc, void* input, uint64_t input_byt
   emu::g_xcds = std::getenv("MI355_EMU_XCDS") ? (unsigned)std::atoi(std::getenv("MI355_EMU_XCDS")) : 2u;
   PlanIR ir;
   std::string e;
-  const int rc = build_plan(*desc, opt, ir, e);
+  int rc = build_plan(*desc, opt, ir, e);
+  // output and input of an out-of-place c2c plan in one allocation: what mi355fft_plan_exec does then (plan.hpp alias_variant), the two
+  // pointers standing for the offsets
+  if (!rc && input && output) {
+    const AliasVariant v = alias_variant(ir, (uint64_t)(uintptr_t)input, (uint64_t)(uintptr_t)output, e);
+    if (v == ALIAS_REFUSED) { std::snprintf(err, err_bytes, "%s", e.c_str()); return MI355FFT_ERR_INVALID; }
+    if (v == ALIAS_STAGED) { opt.fuse_views = 0; rc = build_plan(*desc, opt, ir, e); }
+  }
   if (rc) { std::snprintf(err, err_bytes, "%s", e.c_str()); return rc; }
   if (route) std::snprintf(route, route_bytes, "%s", ir.route.c_str());
   if (launches) *launches = (int)ir.steps.size();
+  if (!input) return 0;   // route and launches only, under the emulator's own planner switches
   if (input_bytes < ir.in_bytes) { std::snprintf(err, err_bytes, "input too small: need %llu", (unsigned long long)ir.in_bytes); return 100; }
   if (!desc->in_place && output_bytes < ir.out_bytes) { std::snprintf(err, err_bytes, "output too small: need %llu", (unsigned long long)ir.out_bytes); return 101; }
   if (kernel_bytes < ir.kernel_bytes) { std::snprintf(err, err_bytes, "kernel too small: need %llu", (unsigned long long)ir.kernel_bytes); return 102; }
-  std::vector<char> work(ir.work_bytes + 256);
+  std::vector<char> work(ir.work_bytes + 256, (char)work_fill);
   void* base[5] = {input, desc->in_place ? input : output, work.data(), kernel, ir.table.data()};
   EmuLauncher l;
   auto lines_fn = [&](int family, int id, const LineArgs& a, unsigned grid) -> bool {
@@ -217,8 +227,20 @@ int emu_run_plan(const mi355fft_plan_desc* desc, void* input, uint64_t input_byt
     auto xcd_fn = [&](int id, const XcdFusedArgs& a, unsigned grid) { return launch_xcd_fused(id, a, grid, l); };
     if (!dispatch_step(s, ptr, l, lines_fn, xcd_fn)) { std::snprintf(err, err_bytes, "no kernel for step kind %d variant %d", (int)s.kind, s.variant); return 103; }
   }
+  if (tail_modified) {
+    *tail_modified = 0;
+    for (size_t i = ir.work_bytes; i < work.size(); ++i) if (work[i] != (char)work_fill) *tail_modified = 1;
+  }
   if (l.sticky) { std::snprintf(err, err_bytes, "XCD-fused kernel gave up waiting (sticky=%u)", l.sticky); return 104; }
   return 0;
+}
+
+// the same on a zero-filled workspace (what the test_emu_* modules run)
+int emu_run_plan(const mi355fft_plan_desc* desc, void* input, uint64_t input_bytes, void* output, uint64_t output_bytes, void* kernel,
+                 uint64_t kernel_bytes, int force_generic, uint64_t chunk_bytes, char* err, size_t err_bytes, char* route, size_t route_bytes,
+                 int* launches) {
+  return emu_run_plan_ex(desc, input, input_bytes, output, output_bytes, kernel, kernel_bytes, force_generic, chunk_bytes, 0, nullptr, err, err_bytes,
+                         route, route_bytes, launches);
 }
 
 // Planner only (host logic tests: routes, guards, workspace sizes) — nothing is run, so shapes far beyond host memory are fine.

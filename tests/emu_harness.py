@@ -23,6 +23,10 @@ def lib():
         L.emu_run_plan.argtypes = [ctypes.POINTER(_abi.PlanDesc), ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
                                    ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_size_t,
                                    ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]
+        L.emu_run_plan_ex.restype = ctypes.c_int
+        L.emu_run_plan_ex.argtypes = [ctypes.POINTER(_abi.PlanDesc), ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                      ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                      ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]
         L.emu_check_registry.restype = ctypes.c_int
         L.emu_check_registry.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
         L.emu_check_xcd_registry.restype = ctypes.c_int
@@ -91,3 +95,65 @@ def run_plan(desc, x, out_floats, kernel=None, force_generic=False, chunk_bytes=
     if rc != 0:
         raise EmuError(rc, err.value.decode())
     return out, route.value.decode(), launches.value
+
+
+def banded(payload, guard, pad, room, word=0x7FC17FC1):
+    """a uint8 array: `guard` bytes, `pad` more, `room` bytes (rounded up to 16) that start with `payload`, `guard` bytes again; `word`
+    (a quiet NaN as f32 and as two binary16 values) everywhere but in the payload"""
+    total = guard + pad + ((room + 15) // 16) * 16 + guard
+    buf = np.full(total // 4, word, np.uint32).view(np.uint8)
+    raw = np.ascontiguousarray(payload).reshape(-1).view(np.uint8)
+    buf[guard + pad:guard + pad + raw.size] = raw
+    return buf
+
+
+def route_of(desc):
+    """(route, launches) as run_plan would plan `desc` (the MI355_EMU_* switches and the emulator's defaults), nothing run"""
+    err = ctypes.create_string_buffer(1024)
+    route = ctypes.create_string_buffer(2048)
+    launches = ctypes.c_int(0)
+    rc = lib().emu_run_plan_ex(ctypes.byref(desc), None, 0, None, 0, None, 0, 0, 0, 0, None, err, 1024, route, 2048, ctypes.byref(launches))
+    if rc != 0:
+        raise EmuError(rc, err.value.decode())
+    return route.value.decode(), launches.value
+
+
+class GuardedRun:
+    """What run_plan_guarded leaves behind: every buffer whole, before and after, as bytes"""
+
+
+def run_plan_guarded(desc, x, out_bytes, kernel=None, in_pad=8, out_pad=8, kernel_pad=8, guard=1 << 20, word=0x7FC17FC1, work_fill=0xFF, alias=False):
+    """Runs the plan with each side at byte offset guard + pad of a larger array filled with `word`, the workspace (and its spare tail)
+    filled with `work_fill`.  alias: the output is the input region itself (in-place plans, and out-of-place c2c run on one buffer).
+    Returns a GuardedRun: in_before / in_after, out_after (None when aliased), kernel_before / kernel_after, the offsets, tail_modified,
+    route, launches."""
+    r = GuardedRun()
+    alias = alias or bool(desc.in_place)
+    x = np.ascontiguousarray(x)
+    ibuf = banded(x, guard, in_pad, max(x.nbytes, out_bytes) if alias else x.nbytes, word)
+    r.in_before, r.in_off = ibuf.copy(), guard + in_pad
+    obuf = None
+    if not alias:
+        obuf = banded(np.empty(0, np.uint8), guard, out_pad, out_bytes, word)
+    r.out_off = r.in_off if alias else guard + out_pad
+    kbuf, kp, kb = None, None, 0
+    if kernel is not None:
+        kernel = np.ascontiguousarray(kernel, dtype=np.float32)
+        kbuf = banded(kernel, guard, kernel_pad, kernel.nbytes, word)
+        r.kernel_before = kbuf.copy()
+        kp, kb = kbuf.ctypes.data + guard + kernel_pad, kernel.nbytes
+    err = ctypes.create_string_buffer(1024)
+    route = ctypes.create_string_buffer(2048)
+    launches, tail = ctypes.c_int(0), ctypes.c_int(0)
+    ip = ibuf.ctypes.data + r.in_off
+    if desc.in_place:
+        op, ob = None, 0
+    else:
+        op, ob = (ip if alias else obuf.ctypes.data + r.out_off), out_bytes
+    rc = lib().emu_run_plan_ex(ctypes.byref(desc), ip, ibuf.size - r.in_off - guard, op, ob, kp, kb, 0, 0, work_fill, ctypes.byref(tail),
+                               err, 1024, route, 2048, ctypes.byref(launches))
+    if rc != 0:
+        raise EmuError(rc, err.value.decode())
+    r.in_after, r.out_after, r.kernel_after = ibuf, obuf, kbuf
+    r.tail_modified, r.route, r.launches = bool(tail.value), route.value.decode(), launches.value
+    return r

@@ -107,16 +107,21 @@ def _run_complex(opts, x, h):
     return got[0::2].copy(), route
 
 
+def check_against_f64(a, e, what):
+    """the bar of the real fftconv routes against float64 (shared with exec_contract_cases.py)"""
+    a, e = np.asarray(a, np.float64), np.asarray(e, np.float64)
+    l2 = float(np.linalg.norm(a - e) / np.linalg.norm(e))
+    print(f"{what}: rel_l2={l2:.3e} max_abs={np.abs(a - e).max():.3e}")
+    _close(a.astype(np.float32), e.astype(np.float32), 4e-3, 4e-3, what)
+    assert l2 < 1e-5, what
+
+
 def _check(oracle, got, want, batch, K, out_layout, route):
     on = want.shape[-1] if want.ndim == 3 else int(np.prod(want.shape[2:]))
     g = _kernel_major(got, batch, K, on, out_layout)
     w = want.reshape(K, batch, on)
     for k in range(K):
-        a, e = g[k].reshape(-1), w[k].reshape(-1)
-        l2 = float(np.linalg.norm(a - e) / np.linalg.norm(e))
-        print(f"{route.strip()} kernel {k}: rel_l2={l2:.3e} max_abs={np.abs(a - e).max():.3e}")
-        _close(a.astype(np.float32), e.astype(np.float32), 4e-3, 4e-3, f"{route.strip()} kernel {k}")
-        assert l2 < 1e-5, route
+        check_against_f64(g[k].reshape(-1), w[k].reshape(-1), f"{route.strip()} kernel {k}")
 
 
 def _rel(a, b):

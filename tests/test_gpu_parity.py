@@ -69,6 +69,15 @@ def check(oracle, got, want, what, atol=3e-4, rtol=3e-4, tol=TOL):
     oracle.assert_close_elementwise(got, want, atol * max(1.0, rms / 64.0), rtol, what)
 
 
+def check_bluestein(oracle, got, want, what):
+    """the bar of the chirp-z routes (shared with exec_contract_cases.py)"""
+    l2, mx = oracle.rel_l2(got, want), oracle.rel_max(got, want)
+    # north_star's bar in both norms (r02 had loosened rel_max to 2e-5 here; measured against an f64 FFT the route is at
+    # 1-5e-7 in both norms for every length of this list, fused or not: profiles/r03_bluestein_error.log)
+    assert l2 <= 1e-5 and mx <= 1e-5, f"{what}: {l2:.2e} {mx:.2e}"
+    oracle.assert_close_elementwise(got, want, 3e-4 * max(1.0, float(np.max(np.abs(want))) / 30), 3e-4, what)
+
+
 # ---- c2c ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n", [2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096])
 def test_c2c_lines_all_sizes(fft, dev, oracle, n):
@@ -336,11 +345,7 @@ def test_c2c_bluestein_lengths(fft, dev, oracle, monkeypatch, n, fused):
             c = x.astype(np.float64).view(np.complex128)
             w = np.fft.fft(c) if direction == "forward" else np.fft.ifft(c)
             want = np.stack([w.real, w.imag], axis=-1).reshape(-1)
-        l2, mx = oracle.rel_l2(got, want), oracle.rel_max(got, want)
-        # north_star's bar in both norms (r02 had loosened rel_max to 2e-5 here; measured against an f64 FFT the route is at
-        # 1-5e-7 in both norms for every length of this list, fused or not: profiles/r03_bluestein_error.log)
-        assert l2 <= 1e-5 and mx <= 1e-5, f"bluestein N={n} {direction}: {l2:.2e} {mx:.2e}"
-        oracle.assert_close_elementwise(got, want, 3e-4 * max(1.0, float(np.max(np.abs(want))) / 30), 3e-4, f"bluestein N={n}")
+        check_bluestein(oracle, got, want, f"bluestein N={n} {direction}")
 
 
 @pytest.mark.parametrize("shape", [[8, 4], [16, 16], [4, 8, 2], [96, 105], [24, 25, 27], [1024, 8], [64, 64, 4], [17, 4], [8, 19]])

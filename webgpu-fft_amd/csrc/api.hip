@@ -86,6 +86,9 @@ struct mi355fft_plan {
   uint64_t arena_bytes = 0;
   bool destroyed = false;
   bool uses_xcd_sync = false;     // has a step whose workgroups wait for each other (needs co-residency)
+  bool staged_sides = false;      // planned with fuse_views = 0 (plan.hpp ALIAS_STAGED)
+  mi355fft_plan* alias_twin = nullptr;   // c2c with ioView: the staged plan that runs when output and input overlap (plan.hpp alias_variant); built at the
+                                         // first such exec, like the arena (a plan is recorded from one thread at a time)
 };
 
 namespace {
@@ -270,6 +273,7 @@ bool step_needs_coresidency(const Step& s) { return s.kind == ST_XCD_RES || (s.k
 int build_and_upload(mi355fft_device* dev, const mi355fft_plan_desc& desc, mi355fft_plan* p) {
   PlannerOptions opt = planner_options_from_env();
   opt.compute_units = dev->compute_units;
+  if (p->staged_sides) opt.fuse_views = 0;
   HIP_TRY(hipSetDevice(dev->ordinal));
   for (int attempt = 0; attempt < 2; ++attempt) {
     if (dev->xcd_disabled || attempt == 1) opt.xcd_shared = 0;
@@ -382,6 +386,26 @@ MI_API int mi355fft_plan_exec(mi355fft_plan* plan, mi355fft_encoder* enc, const 
   if ((d.type == MI355FFT_FFTCONV || d.type == MI355FFT_FFTCONV_REAL) && args->kernel_offset_bytes + plan->ir.kernel_bytes > args->kernel->bytes)
     return fail(MI355FFT_ERR_INVALID, "kernel buffer too small: need %llu bytes, have %llu", (unsigned long long)plan->ir.kernel_bytes,
                 (unsigned long long)args->kernel->bytes);
+  // out-of-place c2c with output and input in one buffer (plan.hpp alias_variant): ioView plans on overlapping ranges run their staged twin
+  if (!d.in_place && d.type == MI355FFT_C2C && !plan->staged_sides && args->output->ptr == args->input->ptr) {
+    std::string why;
+    const AliasVariant v = alias_variant(plan->ir, args->input_offset_bytes, out_off, why);
+    if (v == ALIAS_REFUSED) return fail(MI355FFT_ERR_INVALID, "%s", why.c_str());
+    if (v == ALIAS_STAGED) {
+      if (!plan->alias_twin) {
+        std::unique_ptr<mi355fft_plan> t(new mi355fft_plan());
+        t->dev = plan->dev;
+        t->staged_sides = true;
+        const mi355fft_plan_desc desc_copy = plan->ir.desc;
+        const int trc = build_and_upload(plan->dev, desc_copy, t.get());
+        if (trc) return trc;
+        plan->alias_twin = t.release();
+      }
+      const int xrc = mi355fft_plan_exec(plan->alias_twin, enc, args);
+      if (!xrc) enc->deps.push_back(plan->alive);
+      return xrc;
+    }
+  }
   // workspace: caller's temp when it is big enough and does not alias input/output, else the plan's arena
   void* work = nullptr;
   if (plan->ir.work_bytes) {
@@ -419,6 +443,7 @@ MI_API int mi355fft_plan_exec(mi355fft_plan* plan, mi355fft_encoder* enc, const 
 
 MI_API int mi355fft_plan_destroy(mi355fft_plan* plan) {
   if (!plan || plan->destroyed) return MI355FFT_OK;
+  if (plan->alias_twin) { mi355fft_plan_release(plan->alias_twin); plan->alias_twin = nullptr; }
   *plan->alive = false;
   (void)hipSetDevice(plan->dev->ordinal);
   (void)hipStreamSynchronize(plan->dev->stream);

@@ -2131,6 +2131,17 @@ void wrap_f16_storage(const mi355fft_plan_desc& d, PlanIR& ir) {
 
 int build_plan_f32(const mi355fft_plan_desc& desc, const PlannerOptions& opt, PlanIR& out, std::string& err);
 
+AliasVariant alias_variant(const PlanIR& ir, uint64_t in_off, uint64_t out_off, std::string& err) {
+  const mi355fft_plan_desc& d = ir.desc;
+  if (d.in_place || d.type != MI355FFT_C2C) return ALIAS_AS_IS;
+  if (!(in_off < out_off + ir.out_bytes && out_off < in_off + ir.in_bytes)) return ALIAS_AS_IS;
+  if (d.input.strided || d.output.strided) return ALIAS_AS_IS;
+  if (d.io_input.enabled || d.io_output.enabled) return ALIAS_STAGED;
+  if (in_off == out_off) return ALIAS_AS_IS;
+  err = "output range overlaps the input range at another offset: run the plan on one range (same buffer and offset) or on two disjoint ones";
+  return ALIAS_REFUSED;
+}
+
 int build_plan(const mi355fft_plan_desc& desc, const PlannerOptions& opt, PlanIR& out, std::string& err) {
   out = PlanIR();
   out.desc = desc;

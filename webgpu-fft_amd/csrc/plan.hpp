@@ -181,6 +181,18 @@ PlannerOptions planner_options_from_env();
 // returns MI355FFT_OK or an error status with `err` filled (message style follows the reference's throws)
 int build_plan(const mi355fft_plan_desc& desc, const PlannerOptions& opt, PlanIR& out, std::string& err);
 
+// An out-of-place c2c plan may be run with output and input in one buffer (exec exempts c2c from "different buffers"); in_off / out_off are
+// the two ranges' byte offsets in it.  What such an exec does:
+//   ALIAS_AS_IS    the plan's own steps.  Disjoint ranges; strided layouts (the element sets are the caller's: lanes of one tensor); dense
+//                  sides on ONE range (same offset): every dense route reads a line, tile or transform whole before it stores it to the
+//                  same addresses, or goes through the workspace (tests/exec_contract_cases.py runs each route that way)
+//   ALIAS_STAGED   ioView on overlapping ranges: the view sides differ in shape, and the mapped launches clear and store the output view
+//                  while input elements are still unread.  The same request planned with fuse_views = 0 runs instead: its input side is
+//                  staged into the workspace before the first store to the output
+//   ALIAS_REFUSED  dense sides on ranges that overlap at different offsets: `err` says why
+enum AliasVariant { ALIAS_AS_IS = 0, ALIAS_STAGED = 2, ALIAS_REFUSED = -1 };
+AliasVariant alias_variant(const PlanIR& ir, uint64_t in_off, uint64_t out_off, std::string& err);
+
 // radix factorisation of the generic route: greedy largest-first over {32,16,8,4,2,13,11,7,5,3}
 // (superset of src/plan.js:20-33's {13,11,8,7,5,4,3,2}); empty when n has another prime factor
 std::vector<int> factorize_radices(int64_t n, int max_radix = 32);

@@ -231,10 +231,15 @@ class Plan:
         a.input = inp._h if inp is not None else None
         a.output = out._h if out is not None else None
         a.temp = temp._h if temp is not None else None
+        koff = int(o.get("kernelOffsetBytes", 0))
         if kern is not None:
+            # a Buffer is used as given, at kernelOffsetBytes; arrays are uploaded to the start of a buffer of their own
+            if koff and not isinstance(kern, Buffer):
+                raise Mi355Error(1, f"kernelOffsetBytes requires kernel to be a buffer; got {koff} with a kernel array")
             a.kernel = self._kernel_buffer(kern)._h
         a.input_offset_bytes = int(o.get("inputOffsetBytes", 0))
         a.output_offset_bytes = int(o.get("outputOffsetBytes", 0))
+        a.kernel_offset_bytes = koff
         _chk(lib().mi355fft_plan_exec(self._h, commandEncoder._h, ctypes.byref(a)))
 
     def destroy(self):
