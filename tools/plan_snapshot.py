@@ -9,7 +9,9 @@ Two builds of the planner plan alike when their snapshots are equal:
     MI355_EMU_LIB=<this build>/libmi355emu.so   python tools/plan_snapshot.py -o branch.txt
     python tools/plan_snapshot.py --compare parent.txt branch.txt
 
-Without MI355_EMU_LIB the library is built from this tree (tests/emu/Makefile).  --full writes the dumps themselves.
+Without MI355_EMU_LIB the library is built from this tree (tests/emu/Makefile).  --full writes the dumps themselves.  --env NAME=VALUE
+adds a planner switch to every environment (a build that does not know the switch plans as ever): MI355FFT_RCONV_OLS=0 on both sides
+compares a planner with the overlap-save route switched off against one without it.
 """
 import argparse
 import hashlib
@@ -28,6 +30,7 @@ ENVS = [{}, {"MI355FFT_CONV_PAD": "0"}, {"MI355FFT_CONV_PIPELINE": "0"}, {"MI355
 BOUNDARIES = ["circular", "linear-full", "linear-same", "linear-valid"]
 MODES = ["convolution", "correlation"]
 LAYOUTS = ["kernel-major", "batch-major"]
+EXTRA_ENV = {}      # --env: set in every environment (inherited by the worker processes)
 
 
 def strided(shape, mult=2, offset=3, pad=5, batch_stride=True):
@@ -171,6 +174,13 @@ def conv_corpus(real):
     add([64, 32], [5, 3], "linear-same", K=1, sin=True)          # real: lanes outside the line route
     add([1000], None, "circular", K=1, sout=True)
     add([256], precision="f16-storage")
+    # real: long lines with short kernels (overlap-save by default: MI355FFT_RCONV_OLS; its 0 restores pad[..] rconv[K] and, above 2^22, Bluestein)
+    if real:
+        add([1 << 20], [1024], "linear-same", K=1, batch=8)
+        add([100000], [129], "linear-same", K=2, batch=4)
+        add([9000], [33], "linear-same", K=1, batch=4)
+        add([5000000], [255], "linear-same", K=1, batch=2)
+        add([100000], [129], "linear-full", "correlation", K=2, batch=4, sin=True, sout=True, zr=True, zw=True)
     return cases
 
 
@@ -258,6 +268,7 @@ def plan_case(job):
     for env in ENVS:
         for k in [k for k in os.environ if k.startswith("MI355FFT_") or k.startswith("MI355_EMU_") and k != "MI355_EMU_LIB"]:
             del os.environ[k]
+        os.environ.update(EXTRA_ENV)
         os.environ.update(env)
         rc, text = emu_harness.plan_dump(desc)
         envs = ",".join("%s=%s" % (k[len("MI355FFT_"):], v) for k, v in env.items()) or "default"
@@ -285,7 +296,9 @@ def main():
     ap.add_argument("--full", action="store_true", help="write the IR dumps themselves instead of their hashes")
     ap.add_argument("-j", "--jobs", type=int, default=min(8, os.cpu_count() or 1), help="worker processes")
     ap.add_argument("--compare", nargs=2, metavar=("A", "B"), help="compare two snapshots; exit status 1 when they differ")
+    ap.add_argument("--env", action="append", default=[], metavar="NAME=VALUE", help="a planner switch set in every environment")
     a = ap.parse_args()
+    EXTRA_ENV.update(e.split("=", 1) for e in a.env)
     if a.compare:
         la, lb = (open(p).read().splitlines() for p in a.compare)
         diff = [(x, y) for x, y in itertools.zip_longest(la, lb) if x != y]

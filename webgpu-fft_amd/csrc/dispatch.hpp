@@ -41,6 +41,35 @@ template <class C, class L> bool launch_lines_rconv(const LineArgs& a, unsigned 
   } else return false;
 }
 #endif
+// its overlap-save form (fft_lines_rconv_ols_kernel, route lines-rconv-ols): block lengths P = 128 .. 8192 on the same configurations (no scratch
+// up to there), in the same unit.  `id`: the registry id of the forward ROW configuration of P / 2 points
+template <class L> bool launch_lines_rconv_ols(int id, const RconvOlsArgs& a, unsigned grid, L& l);
+#if defined(MI355_RCONV_DEFINE_INSTANCES) || defined(MI355_HOST_EMU)
+template <class L> bool launch_lines_rconv_ols(int id, const RconvOlsArgs& a, unsigned grid, L& l) {
+  int cur = 0;
+#define LINE_ROW(N, R0, R1, R2, T)                                                                          \
+  if (id == cur) {                                                                                          \
+    using C = LineCfg<N, R0, R1, R2, T, false, false, false, false, 0>;                                     \
+    if constexpr (C::NSTAGES >= 2 && (N) <= 4096) {                                                         \
+      l.launch(fft_lines_rconv_ols_kernel<C>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a);       \
+      return true;                                                                                          \
+    } else return false;                                                                                    \
+  }                                                                                                         \
+  cur += 2;
+#define LINE_ROW_TRIG(N, R0, R1, R2, T) cur += 1;
+#define LINE_PASS_A(N, R0, R1, R2, T) cur += 3;
+#define LINE_PASS_B(N, R0, R1, R2, T) cur += 2;
+#define LINE_COL_RAGGED(N, R0, R1, R2, T) cur += 2;
+#include "line_kernels.def"
+#undef LINE_ROW
+#undef LINE_ROW_TRIG
+#undef LINE_PASS_A
+#undef LINE_PASS_B
+#undef LINE_COL_RAGGED
+  (void)cur; (void)a; (void)grid; (void)l;
+  return false;
+}
+#endif
 
 template <int FAMILY, class L>
 bool launch_lines_family(int id, const LineArgs& a, unsigned grid, L& l) {
@@ -312,6 +341,13 @@ bool dispatch_step(const Step& s, void* const ptr[5], L& l, LinesFn&& lines_fn, 
       a.scale = s.f[0];
       if (a.real_mode == 9) {   // real fftconv line: p[4] (tw_hi) is the packed kernel spectrum; the HI roots sit directly behind the 1024 LO roots (one table)
         a.v_out_lo = (int)s.i[12]; a.v_in_lo = (int)s.i[13]; a.v_in_hi = (int)s.i[14];
+      }
+      if (a.real_mode == 10) {  // its overlap-save form: no padded domain; the block geometry in an argument block of its own (kern_lines.hpp RconvOls)
+        RconvOlsArgs oa{};
+        a.v_out_lo = (int)s.i[12];
+        oa.a = a;
+        oa.o.fN = (int)s.i[13]; oa.o.plim = (int)s.i[14]; oa.o.nb = (int)s.i[15]; oa.o.L = (int)s.i[16]; oa.o.w0 = (int)s.i[17]; oa.o.pre = (int)s.i[18];
+        return launch_lines_rconv_ols(s.variant, oa, s.grid, l);
       }
       const LineKernelMeta& m = line_kernel_registry()[(size_t)s.variant];
       return lines_fn(family_of_line_kernel(m), s.variant, a, s.grid);

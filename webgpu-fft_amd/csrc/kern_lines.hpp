@@ -1081,6 +1081,208 @@ __global__ void __launch_bounds__(C::THREADS, C::THREADS == 256 && C::T == 1 ? 2
   }
 }
 
+// Overlap-save form of the kernel above (route lines-rconv-ols).  A signal line of any length is cut into nb block-lines of P points
+// that overlap by kernelShape - 1; line G of the launch is block j = G % nb of signal line G / nb (the block index runs fastest: the
+// points two neighbouring blocks share are L2 hits).  Block position i is index s0 + i of the signal, s0 = j L - pre, pre = M - 1 + e,
+// M = kernelShape, e = (M - 1) & 1, L = (P - pre) & ~1: s0 and L are even, so a dense line on an even base keeps the 8-byte loads and stores
+// in every block.  Only the head and the store sweep differ from the full-line form:
+//   load    : the bounds of a.imap move with the block: [lo - s0, hi - s0) cut to [0, P)
+//   store   : the circular result of a block is the linear one on a window of L positions, i in [w0, w0 + L): w0 = pre convolving, w0 = e
+//             correlating (conjugated spectrum: the wrap-around sits at the top of the block).  p = s0 + i is kept below plim (convolution: fN,
+//             the logical domain shape + kernelShape - 1; correlation: shape) and is logical index m = p, or m = p + fN for the negative lags
+//             p < 0 of a correlation (they sit at the top of the domain: split = shape, no padD).  From m on nothing changes
+// (the planner keeps fN and the number of block-lines well below 2^31: 32-bit index arithmetic)
+struct RconvOls { int nb, fN, L, w0, pre, plim; };
+struct RconvOlsArgs { LineArgs a; RconvOls o; };     // LineArgs itself stays as it is: every other line kernel takes it by value
+// The stages and the pair step are the kernel's above, repeated rather than shared: with the body in one template the register allocation
+// of the existing instances moved (P = 16384: 41 -> 43 VGPRs spilt), and those stay what they were (profiles/fftconv_ols_resource_usage.log)
+template <class C>
+__global__ void __launch_bounds__(C::THREADS, C::THREADS == 256 && C::T == 1 ? 2 : 1) fft_lines_rconv_ols_kernel(const RconvOlsArgs p) {
+  const LineArgs& a = p.a;
+  const RconvOls& o = p.o;
+  static_assert(!C::IN_COL && !C::OUT_COL && !C::SWAP_IN && !C::SWAP_OUT && C::TWID == TWID_NONE && C::NSTAGES >= 2, "forward ROW configuration with an LDS line buffer");
+  MI_SMEM_DECL(smem);
+  cf* lds = reinterpret_cast<cf*>(smem);
+  cf* tw_lds = lds + C::DATA_ELEMS;
+  const int t = threadIdx.x;
+  if constexpr (C::TW_LDS_ELEMS > 0) {
+    for (int i = t; i < C::TW_LDS_ELEMS; i += C::THREADS) tw_lds[i] = a.tw[i];
+    __syncthreads();
+  }
+  constexpr int H = C::N;
+  constexpr int NP = (H / 2) / C::TPL;          // pairs per lane (k = pu + TPL i < H/2); lane 0 of a line takes the self-mirrored bin H/2 too
+  constexpr int PB = NP > 4 ? 4 : NP;           // pairs per batch: six complex registers each
+  static_assert((H / 2) % C::TPL == 0 && NP % PB == 0, "the pairs of a line are dealt out in whole strides");
+  using I0 = StageInfo<C, 0>;
+  const int pl = t / C::TPL, pu = t % C::TPL;   // pair step and store sweep: a thread stays on one line
+  const bool conj = a.v_out_lo != 0;
+  const float* xin = reinterpret_cast<const float*>(a.in);
+  float* y = reinterpret_cast<float*>(a.out);
+  for (long long tile = blockIdx.x; tile < a.num_tiles; tile += gridDim.x) {
+    cf v[C::E];
+    {
+      const SideMap& im = a.imap;
+      int line, u; thread_map<C, 0>(t, line, u);
+      const long long sa = im.stride[im.ax];
+      const unsigned G = (unsigned)(tile * C::T + line), sb = G / (unsigned)o.nb;
+      const int s0 = (int)(G - sb * (unsigned)o.nb) * o.L - o.pre;       // the block's first signal index
+      const bool ok = G < a.num_lines;
+      long long base = im.offset + (long long)sb * im.batch_stride + (long long)s0 * sa;
+      const int l0 = im.lo[im.ax] - s0, h0 = im.hi[im.ax] - s0;
+      const int lo = l0 < 0 ? 0 : (l0 > 2 * H ? 2 * H : l0), hi = h0 < 0 ? 0 : (h0 > 2 * H ? 2 * H : h0);     // the block's share of [lo, hi)
+      // unit stride and an even base: z[n] is one 8-byte load wherever both of its samples lie inside [lo, hi).  Whatever is left (a
+      // sample pair cut by lo or hi, strided lanes, odd bases) is fetched by the lanes that need it in a rolled loop that parks the
+      // values in the lane's own LDS slots: unrolled beside the first sweep, its two 4-byte loads per element and their addresses cost
+      // every instance 60-90 registers
+#ifndef MI355_HOST_EMU
+      // one line per workgroup: its base is the same in every lane; saying so keeps it in scalar registers and the loads on 32-bit lane offsets
+      if constexpr (C::T == 1) base = (long long)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(base >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)base));
+#endif
+      const bool pairs = ok && sa == 1 && (base & 1) == 0;
+      const cf* xp = reinterpret_cast<const cf*>(xin + base);
+      bool rest = false;
+#pragma unroll
+      for (int b = 0; b < I0::NB; ++b) {
+#pragma unroll
+        for (int q = 0; q < I0::R; ++q) {
+          const int n = u + b * C::TPL + q * (H / I0::R), j = 2 * n;     // z[n] = x[2n] + i x[2n+1]
+          cf x = {0.0f, 0.0f};
+          if (pairs && j >= lo && j + 1 < hi) x = xp[n];
+          else rest = rest || (ok && j + 1 >= lo && j < hi);
+          v[b * I0::R + q] = x;
+        }
+      }
+      if (rest) {
+        const bool whole = !pairs;      // every element of this lane's
+#pragma unroll 4
+        for (int e = 0; e < C::E; ++e) {
+          const int n = u + (e / I0::R) * C::TPL + (e % I0::R) * (H / I0::R), j = 2 * n;
+          cf x = {0.0f, 0.0f};
+          if (whole || j < lo || j + 1 >= hi) {
+            if (j >= lo && j < hi) x.x = xin[base + (long long)j * sa];
+            if (j + 1 >= lo && j + 1 < hi) x.y = xin[base + (long long)(j + 1) * sa];
+          }
+          lds[lds_index<C>(line, n)] = x;
+        }
+#pragma unroll
+        for (int b = 0; b < I0::NB; ++b) {
+#pragma unroll
+          for (int q = 0; q < I0::R; ++q) {
+            const int n = u + b * C::TPL + q * (H / I0::R), j = 2 * n;
+            if (whole || j < lo || j + 1 >= hi) v[b * I0::R + q] = lds[lds_index<C>(line, n)];
+          }
+        }
+      }
+    }
+    __syncthreads();      // (the parked values are read before stage 0 of another lane overwrites the slots)
+    stage_compute_write<C, 0>(v, a, tile, t, lds, tw_lds, nullptr);
+    __syncthreads();
+    stage_read<C, 1>(v, a, tile, t, lds);
+    __syncthreads();
+    stage_compute_write<C, 1, false, true>(v, a, tile, t, lds, tw_lds, nullptr);
+    if constexpr (C::NSTAGES == 3) {
+      __syncthreads();
+      stage_read<C, 2>(v, a, tile, t, lds);
+      __syncthreads();
+      stage_compute_write<C, 2, false, true>(v, a, tile, t, lds, tw_lds, nullptr);
+    }
+    __syncthreads();
+    {
+      // split, product and pre-split of one pair; zk = Z[k], zm = Z[H-k]
+      const auto pair = [&](cf zk, cf zm, cf g0, cf g1, cf w, int k) {
+        const cf zmc = {zm.x, -zm.y};
+        const cf e = (zk + zmc) * 0.5f;
+        const cf wo = cmul(w, mul_neg_i((zk - zmc) * 0.5f));
+        const cf xk = e + wo;
+        cf xm = e - wo;
+        xm.y = -xm.y;
+        if (conj) { g0.y = -g0.y; g1.y = -g1.y; }
+        if (k == 0) { g0.y = 0.0f; g1.y = 0.0f; }           // bins 0 and H are real
+        const cf yk = cmul(xk, g0), ym = cmul(xm, g1);
+        const cf mc = {ym.x, -ym.y};
+        const cf e2 = yk + mc;
+        const cf o2 = cmul_conj(yk - mc, w);
+        lds[lds_index<C>(pl, k)] = e2 + mul_pos_i(o2);
+        if (k != 0 && H - k != k) { const cf ec = {e2.x, -e2.y}, oc = {o2.x, -o2.y}; lds[lds_index<C>(pl, H - k)] = ec + mul_pos_i(oc); }
+      };
+      int toff = 0;
+#ifndef MI355_HOST_EMU
+      asm volatile("" : "+s"(toff));     // opaque zero, per tile: the loads below stay in the tile loop
+#endif
+      const cf* mul = a.tw_hi + toff;
+      const cf* lo = a.tw_lo + toff;
+      const cf* hi = lo + 1024;
+#pragma unroll 1
+      for (int i0 = 0; i0 < NP; i0 += PB) {
+        cf g0[PB], g1[PB], wh[PB], wl[PB], zk[PB], zm[PB];
+#pragma unroll
+        for (int i = 0; i < PB; ++i) {
+          const int k = pu + (i0 + i) * C::TPL;
+          g0[i] = mul[k]; g1[i] = mul[H - k];
+          wh[i] = hi[(unsigned)k >> a.fs_shift]; wl[i] = lo[(unsigned)k & a.fs_lo_mask];
+        }
+#pragma unroll
+        for (int i = 0; i < PB; ++i) {
+          const int k = pu + (i0 + i) * C::TPL;
+          zk[i] = lds[lds_index<C>(pl, k)]; zm[i] = lds[lds_index<C>(pl, k == 0 ? 0 : H - k)];
+        }
+#pragma unroll
+        for (int i = 0; i < PB; ++i) pair(zk[i], zm[i], g0[i], g1[i], cmul(wh[i], wl[i]), pu + (i0 + i) * C::TPL);
+      }
+      if (pu == 0) {
+        const cf zh = lds[lds_index<C>(pl, H / 2)], gh = mul[H / 2];
+        pair(zh, zh, gh, gh, cmul(hi[(unsigned)(H / 2) >> a.fs_shift], lo[(unsigned)(H / 2) & a.fs_lo_mask]), H / 2);
+      }
+    }
+    __syncthreads();
+    {
+      int line, u; thread_map<C, 0>(t, line, u);
+#pragma unroll
+      for (int b = 0; b < I0::NB; ++b) {
+#pragma unroll
+        for (int q = 0; q < I0::R; ++q) v[b * I0::R + q] = cswap_if<true>(lds[lds_index<C>(line, u + b * C::TPL + q * (H / I0::R))]);
+      }
+    }
+    __syncthreads();   // everyone has its inputs before stage 0 re-uses the buffer
+    stage_compute_write<C, 0>(v, a, tile, t, lds, tw_lds, nullptr);
+    __syncthreads();
+    stage_read<C, 1>(v, a, tile, t, lds);
+    __syncthreads();
+    stage_compute_write<C, 1, false, true>(v, a, tile, t, lds, tw_lds, nullptr);
+    if constexpr (C::NSTAGES == 3) {
+      __syncthreads();
+      stage_read<C, 2>(v, a, tile, t, lds);
+      __syncthreads();
+      stage_compute_write<C, 2, false, true>(v, a, tile, t, lds, tw_lds, nullptr);
+    }
+    __syncthreads();
+    {
+      const SideMap& om = a.omap;
+      const unsigned G = (unsigned)(tile * C::T + pl), sb = G / (unsigned)o.nb;
+      if (G < a.num_lines) {
+        const int s0 = (int)(G - sb * (unsigned)o.nb) * o.L - o.pre;
+        const long long base = om.offset + (long long)sb * om.batch_stride;
+        const long long so = om.stride[om.ax];
+        const int slo = om.lo[om.ax], shi = om.hi[om.ax], zlo = om.zlo[om.ax], zhi = om.zhi[om.ax];
+        for (int idx = pu; idx < H; idx += C::TPL) {
+          const cf r = lds[lds_index<C>(pl, idx)] * a.scale;      // (x[2 idx + 1], x[2 idx])
+          const int j = 2 * idx;
+          // block -> logical: -1 outside the block's window and beyond the last index the signal gives
+          const auto logical = [&](int i) { const int q = s0 + i; return (i >= o.w0 && i < o.w0 + o.L && q < o.plim) ? (q < 0 ? q + o.fN : q) : -1; };
+          const int m0 = logical(j), m1 = logical(j + 1);
+          const float y0 = (m0 < zlo || m0 >= zhi) ? 0.0f : r.y, y1 = (m1 < zlo || m1 >= zhi) ? 0.0f : r.x;
+          if (so == 1 && m1 == m0 + 1 && m0 >= slo && m1 < shi && ((base + m0) & 1) == 0) *reinterpret_cast<cf*>(y + base + m0) = cf{y0, y1};   // one 8-byte store
+          else {
+            if (m0 >= slo && m0 < shi) y[base + (long long)m0 * so] = y0;
+            if (m1 >= slo && m1 < shi) y[base + (long long)m1 * so] = y1;
+          }
+        }
+      }
+    }
+    __syncthreads();   // LDS is re-used by the next tile
+  }
+}
+
 // c2r of packed spectra (H+1 bins per line, N = 2H) into real lines: the pre-split of the half-length trick
 // (kern_generic.hpp c2r_pre_kernel: Z[k] = E + iO, E = X[k] + conj X[H-k], O = (X[k] - conj X[H-k]) e^{+2 pi i k/N}; the
 // imaginary parts of X[0] and X[H] are ignored, real_complex.js:147-155) is applied in LDS before the first stage (directly

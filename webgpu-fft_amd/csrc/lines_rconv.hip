@@ -1,5 +1,6 @@
 // device code + launch stubs of the real fftconv line kernel (kern_lines.hpp fft_lines_rconv_kernel): one instance per forward ROW
-// configuration of line_kernels.def with an LDS line buffer (see dispatch.hpp launch_lines_rconv)
+// configuration of line_kernels.def with an LDS line buffer (see dispatch.hpp launch_lines_rconv), and of its overlap-save form
+// (fft_lines_rconv_ols_kernel, dispatch.hpp launch_lines_rconv_ols): half lengths 64 .. 4096
 #define MI355_RCONV_DEFINE_INSTANCES
 #include "hip_launcher.hpp"
 namespace mi355 {
@@ -15,4 +16,5 @@ namespace mi355 {
 #undef LINE_PASS_A
 #undef LINE_PASS_B
 #undef LINE_COL_RAGGED
+template bool launch_lines_rconv_ols<HipLauncher>(int, const RconvOlsArgs&, unsigned, HipLauncher&);
 }

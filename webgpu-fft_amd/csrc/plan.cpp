@@ -157,6 +157,7 @@ PlannerOptions planner_options_from_env() {
   if (const char* s = std::getenv("MI355FFT_CONV_PIPELINE")) o.conv_pipeline = std::atoi(s);
   if (const char* s = std::getenv("MI355FFT_CONV_PAD")) o.conv_pad = std::atoi(s);
   if (const char* s = std::getenv("MI355FFT_RCONV_FUSED")) o.rconv_fused = std::atoi(s);
+  if (const char* s = std::getenv("MI355FFT_RCONV_OLS")) o.rconv_ols = std::atoi(s);
   if (const char* s = std::getenv("MI355FFT_SOLO_MAX_KB")) { const int v = std::atoi(s); if (v >= 0) o.solo_max_kb = v; }
   if (const char* s = std::getenv("MI355FFT_SOLO_CAP_MB")) { const int v = std::atoi(s); if (v >= 1) o.solo_cap_mb = v; }
   if (const char* s = std::getenv("MI355FFT_XCD_SLOTS")) { const int v = std::atoi(s); if (v >= 0 && v <= 2) o.xcd_slots = v; }
@@ -287,6 +288,15 @@ struct Builder {
     for (size_t h = 0; h < hi.size(); ++h) hi[h] = root_of_unity((int64_t)h << 10, M);
     const PtrRef plo = add_table(lo), phi = add_table(hi);   // add_table may reallocate ir.steps? no: tables live in ir.table
     st.p[2] = plo; st.p[3] = phi; st.i[3] = 10; st.i[4] = 1023;
+  }
+
+  // the real fftconv line kernels' roots e^{-2 pi i k/P} = HI[k >> 10] LO[k & 1023], k <= P/2: the HI factors directly behind the 1024 LO factors
+  // (one table: dispatch.hpp)
+  PtrRef rconv_roots(int64_t P) {
+    std::vector<float2h> roots(1024 + (size_t)std::max<int64_t>(1, (P / 2 + 1023) >> 10));
+    for (int64_t l = 0; l < 1024; ++l) roots[(size_t)l] = root_of_unity(l, P);
+    for (size_t h = 1024; h < roots.size(); ++h) roots[h] = root_of_unity((int64_t)(h - 1024) << 10, P);
+    return add_table(roots);
   }
 
   unsigned lines_grid(const LineKernelMeta& m, int64_t tiles, bool plain_c2c = false) const {
@@ -1929,7 +1939,9 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
 
 // ---- fftconv over real data (type MI355FFT_FFTCONV_REAL) ------------------------------------------------------------------------
 // Signals, kernels and results are f32 reals; the values are the real parts of what build_fftconv's plan returns for the same data
-// with zero imaginary parts.  Every option keeps its meaning; side layouts and the kernel stride count f32 elements.  Three routes:
+// with zero imaginary parts.  Every option keeps its meaning; side layouts and the kernel stride count f32 elements.  Four routes:
+//   lines-rconv-ols[N=P,L=L]  rank 1, linear modes, shape + kernelShape - 1 > 8192 and kernelShape <= 4096 by default (MI355FFT_RCONV_OLS): overlap-save,
+//                     the line cut into blocks of P points that each run the pipeline of lines-rconv; 1 + K launches for any length, strided lanes too
 //   lines-rconv[N=P]  rank 1, FFT length P a power of two, 128 <= P <= 8192 by default (16384 and 32768 with strided sides or MI355FFT_RCONV_FUSED=2) (circular: P = shape; linear modes: the next power of two
 //                     >= max(shape + kernelShape - 1, 128) — a linear result is cropped, so any P >= that length is legal): one
 //                     lines-r2c-mapped launch writes the K packed kernel spectra, then ONE launch per kernel does r2c, product and c2r
@@ -1942,6 +1954,7 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
 //   rconv-widened     circular with odd shape[0] (no even domain is allowed): the complex plan between widening / narrowing passes
 // Validation, shapes, lanes and the padded-domain index map are ConvGeom's, shared with build_fftconv; each route hands it the
 // axis-0 length it transforms on.
+constexpr int64_t OLS_MAX_KERNEL = 4096;   // the longest kernel the default rule gives to overlap-save: the longest one measured (3.8x / 2.5x ahead at K = 1 / 4)
 int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
   ConvGeom g;
   if (int rv = conv_geometry(d, 4, g, b.ir, err)) return rv;
@@ -1951,6 +1964,48 @@ int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err
   const int64_t *ks = g.ks, *fs = g.fs, zero[8] = {0};
   const bool strided = d.input.strided || d.output.strided;
   const PtrRef in(BUF_INPUT, 0), out(BUF_OUTPUT, 0), kern(BUF_KERNEL, 0);
+
+  // ---- overlap-save: long real lines, short kernels, one launch per kernel on blocks of P points ---------------------------------
+  // Block j of a line holds signal indices [s0, s0 + P), s0 = j L - pre, pre = M - 1 + e, e = (M - 1) & 1, and gives L = (P - pre) & ~1
+  // results (kern_lines.hpp fft_lines_rconv_ols_kernel has the index map).  The switch 0 keeps the routes below for every request; a
+  // power of two 128 .. 8192 forces that block length on every request it fits (L >= 2), whatever its length; 1 is the measured rule
+  if (rank == 1 && linear && b.opt.rconv_fused == 1 && b.opt.rconv_ols != 0 && lfN < ((int64_t)1 << 31) - 16384) {   // (the kernel's indices are 32-bit)
+    const int64_t M = ks[0], pre = (M - 1) + ((M - 1) & 1);
+    int64_t P = 0;
+    if (b.opt.rconv_ols > 1) { if (is_pow2(b.opt.rconv_ols) && b.opt.rconv_ols >= 128 && b.opt.rconv_ols <= 8192) P = b.opt.rconv_ols; }
+    // measured (profiles/fftconv_ols_ab.log, 256 x 2^20 (*) {31, 255, 1024, 4096}, K = 1 and 4, and three longer / shorter lines): every block length
+    // 1024 .. 8192 is 2.5-8x ahead of pad[..] rconv[K] and 46-66x ahead of the Bluestein plans above 2^22; the fastest P is the smallest power of two
+    // >= 8 (M - 1) from 1024 on (M = 31: 1024, 255: 2048, 1024 and 4096: 8192), except that P = 4096 is behind 8192 on every request (its instance
+    // holds 190 VGPRs: two workgroups per CU where the LDS would take three) and is never chosen
+    else if (lfN > 8192 && M <= OLS_MAX_KERNEL) { P = 1024; while (P < 8 * (M - 1) && P < 8192) P <<= 1; if (P == 4096) P = 8192; }
+    const int64_t L = (P - pre) & ~(int64_t)1;
+    const int64_t nb = L >= 2 ? (lfN + L - 1) / L : 0, lines = B * nb;
+    const LineKernelMeta* om = (P && L >= 2 && lines < ((int64_t)1 << 31) - 64) ? b.lines_r2c_kernel(P, false, true) : nullptr;
+    if (om) {
+      const int64_t H = P / 2;
+      const int64_t pd[1] = {P}, pp[1] = {H + 1};
+      const PtrRef G = b.alloc_work((uint64_t)K * (H + 1) * 8);
+      const SideMap km = conv_kernel_map(g, pd, 1);
+      const SideMap gm = Builder::dense_map(pp, 1);
+      if (!b.emit_lines_r2c(kern, G, P, K, 1.0f, false, 0, &km, &gm)) { err = "no mapped r2c line kernel"; return MI355FFT_ERR_UNSUPPORTED; }
+      const PtrRef tables = b.line_tables(*om), proots = b.rconv_roots(P);
+      const SideMap xm = conv_load_map(d, g, fs, 1);
+      const int64_t tiles = (lines + om->T - 1) / om->T;
+      for (int64_t k = 0; k < K; ++k) {
+        Step& st = b.push(ST_LINES);
+        st.variant = om->id;
+        st.p[0] = in; st.p[1] = out; st.p[2] = tables; st.p[3] = proots; st.p[4] = G.plus(k * (H + 1) * 8);
+        st.i[0] = tiles; st.i[1] = lines; st.i[2] = 1; st.i[3] = H; st.i[4] = 1; st.i[5] = H; st.i[6] = 10; st.i[7] = 1023;
+        st.i[9] = 10; st.i[10] = 1; st.i[12] = corr ? 1 : 0;
+        st.i[13] = lfN; st.i[14] = corr ? d.shape[0] : lfN; st.i[15] = nb; st.i[16] = L; st.i[17] = corr ? pre - (M - 1) : pre; st.i[18] = pre;
+        st.f[0] = (float)(1.0 / (double)P);
+        st.imap = xm; st.omap = conv_store_map(d, g, fs, 1, k);
+        st.grid = b.lines_grid(*om, tiles);
+      }
+      b.ir.route += "lines-rconv-ols[N=" + std::to_string(P) + ",L=" + std::to_string(L) + "] ";
+      return MI355FFT_OK;
+    }
+  }
 
   // ---- route 1: one launch per kernel on the line kernels --------------------------------------------------------------------
   int64_t P1 = 0;
@@ -1971,12 +2026,7 @@ int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err
     const PtrRef G = b.alloc_work((uint64_t)K * (H + 1) * 8);
     const SideMap km = conv_kernel_map(g, fs, 1), gm = Builder::dense_map(pp, 1);
     if (!b.emit_lines_r2c(kern, G, P, K, 1.0f, false, 0, &km, &gm)) { err = "no mapped r2c line kernel"; return MI355FFT_ERR_UNSUPPORTED; }
-    const PtrRef tables = b.line_tables(*rm);
-    // e^{-2 pi i k/P} = HI[k >> 10] LO[k & 1023], the HI factors directly behind the 1024 LO factors (one table: dispatch.hpp)
-    std::vector<float2h> roots(1024 + (size_t)std::max<int64_t>(1, (H + 1023) >> 10));
-    for (int64_t l = 0; l < 1024; ++l) roots[(size_t)l] = root_of_unity(l, P);
-    for (size_t h = 1024; h < roots.size(); ++h) roots[h] = root_of_unity((int64_t)(h - 1024) << 10, P);
-    const PtrRef proots = b.add_table(roots);
+    const PtrRef tables = b.line_tables(*rm), proots = b.rconv_roots(P);
     const SideMap xm = conv_load_map(d, g, fs, 1);
     const int64_t tiles = (B + rm->T - 1) / rm->T;
     for (int64_t k = 0; k < K; ++k) {

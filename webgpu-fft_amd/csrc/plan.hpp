@@ -166,6 +166,14 @@ struct PlannerOptions {
 #endif
                                        // real fftconv (MI355FFT_FFTCONV_REAL), rank 1, power-of-two FFT length 128..8192 (16384, 32768: strided sides only): r2c, product and c2r of a
                                        // line in one launch per kernel (kern_lines.hpp fft_lines_rconv_kernel); 0: the composed route rconv[K]; 2: the line route up to 32768 as well
+#ifdef MI355_HOST_EMU
+  int rconv_ols = std::getenv("MI355_EMU_RCONV_OLS") ? std::atoi(std::getenv("MI355_EMU_RCONV_OLS")) : 1;
+#else
+  int rconv_ols = 1;
+#endif
+                                       // real fftconv, rank 1, linear boundaries: overlap-save on blocks of P points, one launch per kernel whatever the line's length
+                                       // (kern_lines.hpp fft_lines_rconv_ols_kernel); 1: where measured ahead (plan.cpp build_fftconv_real); 0: never; a power of two
+                                       // 128..8192: that block length on every request it fits (tests and measurement).  rconv_fused = 0 / 2 come first
   int conv_lines = 1;                  // fftconv: kernel-spectrum product fused behind the forward line FFT (1-D, power-of-two FFT length <= max_line)
   int trig_fused = 1;                  // dct2 / dst2 of dense lines (half length a line-kernel size): permutation + real FFT + phase in one launch
   int trig_real = 1;                   // dct2/dst2/dct3/dst3 along a dense even axis through a real FFT of length N (kern_trig.hpp)
