@@ -730,6 +730,12 @@ __global__ void __launch_bounds__(HxCfg::THREADS, MI355_HX_WAVES) fft_xcd_hx_ker
 #ifndef MI355_RT1K_W_NT
 #define MI355_RT1K_W_NT 0      /* experiment: nontemporal accesses to the intermediate */
 #endif
+#ifndef MI355_RT1K_SPLIT_HANDOFF
+#define MI355_RT1K_SPLIT_HANDOFF 1   /* one-slot mode, N1 = 1024: the slot-reuse barrier arrives in the last phase-B tile and waits in the next transform's first phase-A tile (kern_xcd.hpp); 0: arrive + wait at the end of the transform */
+#endif
+#ifndef MI355_RT1K_LEAN_VALU
+#define MI355_RT1K_LEAN_VALU 1       /* vector instructions of the tile loops that do no arithmetic, removed bit-identically: the output scale is an unconditional multiply (x * 1.0f is exact) instead of a multiply and a select per component, the complex products carry negation and broadcast as source modifiers (rt1k_cmul); 0: the guarded scale and cmul (profiles/rt1k_handoff_valu_isa_counts.log) */
+#endif
 // T = 32: one 512-thread workgroup per CU.  T = 16 (r03 experiment, MI355FFT_XCD_HX=3): the same code on 16-line tiles with 256 threads — 72 KB of
 // LDS and still 256 VGPRs per thread, so TWO independent workgroups share a CU and their load / compute / store phases interleave (the 512-thread
 // two-per-CU form of fft_xcd_hx_kernel had to live in 128 VGPRs).
@@ -740,6 +746,21 @@ template <int T_ = 32> struct Rt1kCfgT {
   static constexpr int LDS_BYTES = (HALF_ELEMS + TW1_ELEMS) * 8 + 64;
 };
 using Rt1kCfg = Rt1kCfgT<32>;
+// a * b, bit for bit cmul's 2 mul + 2 fma (radix.hpp), with the operand selection written out: the compiler forms cmul's packed pair of
+// instructions too, but builds the (-a.y, a.y) operand of the fma in two more registers first (a sign-bit xor and a copy per product);
+// here the high-half broadcast and the negation are the source modifiers of the two instructions
+//   m = (a.x b.x, a.x b.y)                          v_pk_mul_f32  op_sel / op_sel_hi: a.lo for both halves
+//   r = (fma(-a.y, b.y, m.x), fma(a.y, b.x, m.y))   v_pk_fma_f32  a.hi for both halves, b crossed, neg_lo on a
+MI_DEV cf rt1k_cmul(cf a, cf b) {
+#if MI355_RT1K_LEAN_VALU && !MI355_EXP_NO_MATH && !defined(MI355_HOST_EMU)
+  cf m, r;
+  asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[0,1]" : "=v"(m) : "v"(a), "v"(b));
+  asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]" : "=v"(r) : "v"(a), "v"(b), "v"(m));
+  return r;
+#else
+  return cmul(a, b);
+#endif
+}
 template <int T = 32> MI_DEV int rt1k_slot(int line, int pl, int u) { return u * (16 * T) + pl * T + ((line + (u >> 1)) & (T - 1)); }
 
 // producers (line, ua), (line, ub) with outputs va[p], vb[p]; consumers (cl, h) in the first half and (cl, h + 16) in the second.
@@ -780,18 +801,22 @@ __global__ void __launch_bounds__(Rt1kCfgT<T>::THREADS, 2) fft_xcd_rt1k_kernel(c
   for (int i = t; i < K::TW1_ELEMS; i += K::THREADS) tw1[i] = f.tw_b[i];
   if constexpr (N1_ == 2048) { for (int i = t; i < RtCfg::TW2_ELEMS; i += K::THREADS) tw2[i] = f.tw_a[i]; }
   if (!xcd_register(f.ctl, f.split, f.spin_limit, f.sticky_error, s_words)) return;
-  const unsigned gslot = s_words[0], rank = s_words[1], gsize = s_words[2], gidx = s_words[4], groups = s_words[5];
+  // (as wave-uniform values: the tile loops below branch on them around a workgroup barrier and build scalar bases from them)
+  const unsigned gslot = MI_UNIFORM_U32(s_words[0]), rank = MI_UNIFORM_U32(s_words[1]), gsize = MI_UNIFORM_U32(s_words[2]), gidx = MI_UNIFORM_U32(s_words[4]), groups = MI_UNIFORM_U32(s_words[5]);
   constexpr unsigned N1 = N1_, N2 = 1024, NT = N1 / T, TU = (unsigned)T;
   const bool two_slots = f.slots != 1u;
+  // slot re-use as a split barrier (kern_xcd.hpp): workgroups that own tiles (rank < NT: every one that enters a tile loop) signal their
+  // last read of W early and wait for the peers' late
+  constexpr bool SPLIT_HANDOFF = MI355_RT1K_SPLIT_HANDOFF && N1_ == 1024;
   cf* const W0 = f.wslots + (size_t)((two_slots ? 2u : 1u) * gslot) * (size_t)f.N;
   const int cl = t & (T - 1), h = t / T;    // column-side map
   const int rl = t >> 4, hh = t & 15;       // row-side map
-  const auto root = [&](unsigned m) { return cmul(f.tw_hi[m >> f.fs_shift], f.tw_lo[m & f.fs_lo_mask]); };
+  const auto root = [&](unsigned m) { return rt1k_cmul(f.tw_hi[m >> f.fs_shift], f.tw_lo[m & f.fs_lo_mask]); };
   const auto stage1 = [&](cf (&w)[32], int j2) {
     int ti = j2; MI_OPAQUE_LANE_INT(ti);     // (not loop-invariant for the optimiser: hoisted, the 31 roots would pin 62 registers)
 #pragma unroll
     for (int q = 1; q < 32; ++q) {
-      w[q] = cmul(w[q], tw1[(q - 1) * 32 + ti]);
+      w[q] = rt1k_cmul(w[q], tw1[(q - 1) * 32 + ti]);
       if (MI355_RT1K_TW_FENCE && q % MI355_RT1K_TW_FENCE == 0) MI_SCHED_FENCE();   // at most this many roots in flight (registers) at a time
     }
     fft_radix<32>(w);
@@ -842,6 +867,13 @@ __global__ void __launch_bounds__(Rt1kCfgT<T>::THREADS, 2) fft_xcd_rt1k_kernel(c
         fft_radix<32>(vb);
         cf* const po = W + tile * TU;
         const unsigned so = (unsigned)h * N2 + (unsigned)cl;
+        // the peers' reads of W in transform k - 1 end here at the latest: the first store to W follows the exchange below.  No acquire:
+        // nothing a peer wrote is read before the A | B barrier.  A timeout leaves as a whole workgroup, before any further global store.
+        if (SPLIT_HANDOFF && !two_slots && k > 0 && tile == rank) {
+          // (so == 0 names thread 0 from a register the tile's stores hold anyway)
+          // (the verdict is read as a wave-uniform value: an exit from the tile loop on a per-lane one would make everything the loop defines per-lane too)
+          if (!MI_UNIFORM_U32(xcd_wait<false>(&f.ctl->bar[gslot][1], k * gsize, f.spin_limit, f.sticky_error, &s_words[6], so == 0u))) return;
+        }
         rt1k_exchange<T>(va, vb, w, xb, cl, h, h + 16, cl, h, [&] {
           if (PF && tile + gsize < NT) load_a(tile + gsize, 0, PF);
           stage1(w, h);
@@ -879,11 +911,11 @@ __global__ void __launch_bounds__(Rt1kCfgT<T>::THREADS, 2) fft_xcd_rt1k_kernel(c
 #pragma unroll
           for (int g = 0; g < 4; ++g) {
             cf ra = root(k1 * (unsigned)(2 * hh + 256 * g));
-            cf rb = cmul(ra, one);
+            cf rb = rt1k_cmul(ra, one);
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-              va[8 * g + j] = cmul(va[8 * g + j], ra); vb[8 * g + j] = cmul(vb[8 * g + j], rb);
-              if (j < 7) { ra = cmul(ra, step); rb = cmul(rb, step); }
+              va[8 * g + j] = rt1k_cmul(va[8 * g + j], ra); vb[8 * g + j] = rt1k_cmul(vb[8 * g + j], rb);
+              if (j < 7) { ra = rt1k_cmul(ra, step); rb = rt1k_cmul(rb, step); }
             }
           }
         }
@@ -895,7 +927,7 @@ __global__ void __launch_bounds__(Rt1kCfgT<T>::THREADS, 2) fft_xcd_rt1k_kernel(c
 #pragma unroll
           for (int q = 0; q < 32; ++q) {
             cf r = ww[q];
-            if (f.scale != 1.0f) r = r * f.scale;
+            if (MI355_RT1K_LEAN_VALU || f.scale != 1.0f) r = r * f.scale;
             if constexpr (VIEW) {
               const int kk = (int)(((unsigned)(32 * q) + off + (unsigned)h) * N1 + tile * TU + (unsigned)cl);      // k = k1 + N1 k2
               cf* const pe = po + ((unsigned)(32 * q) + off) * N1 + so;
@@ -906,6 +938,9 @@ __global__ void __launch_bounds__(Rt1kCfgT<T>::THREADS, 2) fft_xcd_rt1k_kernel(c
         };
         rt1k_exchange<T>(va, vb, w, xb, rl, 2 * hh, 2 * hh + 1, cl, h, [&] {
           if (PF && tile + gsize < NT) load_rows(tile + gsize, 0, PF);
+          // last tile: every wave wrote an exchange half and passed a workgroup barrier since, so all of this workgroup's loads of W have
+          // returned (they were the operands of that write).  Reads, not stores, are signalled: no vmcnt(0) (kern_xcd.hpp).
+          if (SPLIT_HANDOFF && !two_slots && tile + gsize >= NT) xcd_arrive_reads(&f.ctl->bar[gslot][1], so == 0u);
           stage1(w, h); store(w, 0u);
         });
         stage1(w, h + 16);
@@ -913,7 +948,7 @@ __global__ void __launch_bounds__(Rt1kCfgT<T>::THREADS, 2) fft_xcd_rt1k_kernel(c
         __syncthreads();
       }
     }
-    if (!two_slots) {
+    if (!two_slots && !(SPLIT_HANDOFF && rank < NT)) {   // (a workgroup without tiles has no last read or first store to hang the split barrier on: the plain way)
       xcd_arrive(&f.ctl->bar[gslot][1]);
       if (!xcd_wait(&f.ctl->bar[gslot][1], (k + 1u) * gsize, f.spin_limit, f.sticky_error, &s_words[6])) return;
     }

@@ -122,6 +122,20 @@ MI_DEV void fourstep_apply_chain(cf (&v)[C::E], const XcdFusedArgs& a, unsigned 
 // the SAME L2 by construction (groups are formed from the XCC_ID register), so the stores are visible to them once they have left
 // the CU (vmcnt(0)), and writing W back to memory first is exactly the fabric traffic the kernel is trying not to wait for.
 // Measured: profiles/r02_xcd_handoff_release_ab.log.
+//
+// Slot re-use in one-slot mode (bar[gslot][1]) guards a write-after-read hazard only: phase A of transform k + 1 must not overwrite W
+// while a peer still reads it in phase B of transform k.  Most kernels run it as a full arrive + wait at the end of a transform.
+// fft_xcd_rt1k_kernel (N1 = 1024, MI355_RT1K_SPLIT_HANDOFF) splits it around the work it does not order:
+//   arrive (xcd_arrive_reads): in the workgroup's LAST phase-B tile, right after the exchange's write of the second half.  Every wave
+//     is then past a workgroup barrier that follows its first exchange write, whose operands ARE the W loads of that tile: all of the
+//     workgroup's reads of W have returned.  The counter signals completed reads, not stores, so there is no vmcnt(0) in front of it
+//     (the output stores still in flight are nobody's input);
+//   wait (xcd_wait<false>): in the FIRST phase-A tile of the next transform, after its loads of x and both radix-32 butterflies, before
+//     the exchange that precedes the first store to W.  Nothing a peer wrote is read behind this wait (x is the caller's, W is only
+//     written until the A | B barrier, which keeps its acquire), so it carries no acquire fence and no vmcnt(0) either.  Bounded poll,
+//     sticky error word and the workgroup-uniform early return are xcd_wait's; after a group's last transform nobody waits.
+// A workgroup without tiles (rank >= tiles) has no such places and arrives and waits the plain way at the end of the transform: the
+// counter sees one increment per workgroup and transform either way.
 #ifndef MI355_XCD_RELEASE
 #define MI355_XCD_RELEASE 0
 #endif
@@ -136,6 +150,11 @@ MI_DEV void xcd_arrive(unsigned* counter) {
     MI_ATOMIC_ADD_U32(counter, 1u);
   }
 }
+// arrive for READS of the slot (see above): the caller stands behind a workgroup barrier that every wave passed after consuming its
+// last loads of the slot — nothing to drain
+MI_DEV void xcd_arrive_reads(unsigned* counter, bool leader) {   // leader: true in exactly one thread of the workgroup
+  if (leader) MI_ATOMIC_ADD_U32(counter, 1u);
+}
 // solo mode: producer and consumer are the same workgroup — its stores are complete (vmcnt(0) + workgroup barrier) and its
 // CU's L1 is invalidated (the slot is re-used for every transform, so stale lines of the previous one may sit there)
 MI_DEV void xcd_local_handoff() {
@@ -146,19 +165,25 @@ MI_DEV void xcd_local_handoff() {
 #ifndef MI355_EXP_NO_WAIT
 #define MI355_EXP_NO_WAIT 0   /* timing-only builds: the group barriers do not wait (results wrong by construction): bounds what the waits cost */
 #endif
-MI_DEV bool xcd_wait(unsigned* counter, unsigned target, unsigned spin_limit, unsigned* sticky, unsigned* s_flag) {
-  if (threadIdx.x == 0) {
+// ACQUIRE = false: a wait that orders this workgroup's later STORES only (slot re-use): no fence, no vmcnt(0)
+template <bool ACQUIRE = true>
+MI_DEV bool xcd_wait(unsigned* counter, unsigned target, unsigned spin_limit, unsigned* sticky, unsigned* s_flag, bool leader) {   // leader: true in exactly one thread
+  if (leader) {
     unsigned ok = MI355_EXP_NO_WAIT;
     for (unsigned it = 0; it < spin_limit && !MI355_EXP_NO_WAIT; ++it) {
       if (MI_ATOMIC_LOAD_U32(counter) >= target) { ok = 1; break; }
       MI_SLEEP();
     }
-    MI_ACQUIRE_AGENT();
+    if constexpr (ACQUIRE) MI_ACQUIRE_AGENT();
     if (!ok) MI_ATOMIC_OR_U32(sticky, 2u);
     *s_flag = ok;
   }
   __syncthreads();
   return *s_flag != 0;
+}
+
+MI_DEV bool xcd_wait(unsigned* counter, unsigned target, unsigned spin_limit, unsigned* sticky, unsigned* s_flag) {
+  return xcd_wait<true>(counter, target, spin_limit, sticky, s_flag, threadIdx.x == 0);
 }
 
 // Registration: every workgroup reads its XCC id, takes a rank inside that XCD and waits (bounded) until the whole grid has
