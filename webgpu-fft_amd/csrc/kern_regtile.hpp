@@ -724,8 +724,33 @@ __global__ void __launch_bounds__(HxCfg::THREADS, MI355_HX_WAVES) fft_xcd_hx_ker
 #ifndef MI355_RT1K_TW_FENCE
 #define MI355_RT1K_TW_FENCE 8
 #endif
-#ifndef MI355_RT1K_PREFETCH
-#define MI355_RT1K_PREFETCH 0    /* loads per thread (of 64) requested one tile ahead: 0, 8, 16, 32.  32: 276 B of scratch, 174.5 vs 196.4 GPoints/s (profiles/r03_headline_rt32_ab.log) */
+// Software pipeline of the tile loads (32-line 1024 x 1024 instances without predicates; profiles/rt1k_pipeline_ab.log, one box, interleaved rounds;
+// registers from rt1k_pipeline_resource_usage_{before,after}.log: no form that was run has scratch).  Values are loads per thread of a tile's 64.
+//   MI355_RT1K_PREFETCH_B  phase B, the next tile's rows of W (16-byte loads: half as many instructions).  32: 211.0 - 212.8 against the parent's
+//                          206.1 - 207.1 GPoints/s (+2.6 %), 241 VGPRs: the default.  48 / 56 (241 / 245 VGPRs): within 0.3 % of 32.  64: 20 B of scratch, not run.
+//   MI355_RT1K_PREFETCH_A  phase A, the next tile's columns of x.  32 (all of va; 210 VGPRs alone, 241 with B): 207.0 - 207.8 alone, 211.7 - 213.8 on top
+//                          of B = 32 (median +0.6 %, ranges overlap): off by the project's rule.  Reaching into vb as well was measured and removed: 48 loads 0.5 % below
+//                          the parent, 64 spill 20 B.
+//   MI355_RT1K_PREFETCH_X  across the transform boundary: in a workgroup's last phase-B tile, loads of its first phase-A tile of the group's NEXT
+//                          transform (at most va's 32).  32: 205.6 - 206.5 alone, 211.8 - 213.7 with A = B = 32 (no gain over A + B): off.
+//   MI355_RT1K_PREFETCH    when defined sets A and B together (the form measured before the kernel's register diet: 32 spilt 276 B at 256 VGPRs
+//                          then, 174.5 vs 196.4 GPoints/s, profiles/r03_headline_rt32_ab.log).
+#ifndef MI355_RT1K_PREFETCH_A
+#ifdef MI355_RT1K_PREFETCH
+#define MI355_RT1K_PREFETCH_A MI355_RT1K_PREFETCH
+#else
+#define MI355_RT1K_PREFETCH_A 0
+#endif
+#endif
+#ifndef MI355_RT1K_PREFETCH_B
+#ifdef MI355_RT1K_PREFETCH
+#define MI355_RT1K_PREFETCH_B MI355_RT1K_PREFETCH
+#else
+#define MI355_RT1K_PREFETCH_B 32
+#endif
+#endif
+#ifndef MI355_RT1K_PREFETCH_X
+#define MI355_RT1K_PREFETCH_X 0
 #endif
 #ifndef MI355_RT1K_W_NT
 #define MI355_RT1K_W_NT 0      /* experiment: nontemporal accesses to the intermediate */
@@ -805,6 +830,13 @@ __global__ void __launch_bounds__(Rt1kCfgT<T>::THREADS, 2) fft_xcd_rt1k_kernel(c
   const unsigned gslot = MI_UNIFORM_U32(s_words[0]), rank = MI_UNIFORM_U32(s_words[1]), gsize = MI_UNIFORM_U32(s_words[2]), gidx = MI_UNIFORM_U32(s_words[4]), groups = MI_UNIFORM_U32(s_words[5]);
   constexpr unsigned N1 = N1_, N2 = 1024, NT = N1 / T, TU = (unsigned)T;
   const bool two_slots = f.slots != 1u;
+  // the software pipeline (MI355_RT1K_PREFETCH_A / _B / _X) exists in the 32-line 1024 x 1024 instances without predicates; the others compile it out
+  constexpr bool PIPE = T == 32 && !VIEW && N1_ == 1024;
+  constexpr int PFA = PIPE ? MI355_RT1K_PREFETCH_A : 0, PFB = PIPE ? MI355_RT1K_PREFETCH_B / 2 : 0, PFX = PIPE ? MI355_RT1K_PREFETCH_X : 0;
+  // inverse instances: the re/im swap of x is applied when a tile's loads are consumed, not to each load — on a load requested a tile ahead the
+  // compiler keeps the swapped copy next to the landing registers (256 VGPRs + 132 B of scratch at A = B = 32; this way 241 and 0 B)
+  constexpr bool LATE_SWAP = INV && (PFA != 0 || PFX != 0);
+  static_assert(PFA >= 0 && PFA <= 32 && PFB >= 0 && PFB <= 32 && PFX >= 0 && PFX <= 32, "at most va's 32 loads (phase B: the 32 16-byte loads) ahead");
   // slot re-use as a split barrier (kern_xcd.hpp): workgroups that own tiles (rank < NT: every one that enters a tile loop) signal their
   // last read of W early and wait for the peers' late
   constexpr bool SPLIT_HANDOFF = MI355_RT1K_SPLIT_HANDOFF && N1_ == 1024;
@@ -821,14 +853,15 @@ __global__ void __launch_bounds__(Rt1kCfgT<T>::THREADS, 2) fft_xcd_rt1k_kernel(c
     }
     fft_radix<32>(w);
   };
+  cf va[32], vb[32], w[32];   // (transform-loop scope: va carries the boundary prefetch from a transform's last phase-B tile into the next one's phase A)
   unsigned k = 0;
   for (long long tr = gidx; tr < f.num_transforms; tr += groups, ++k) {
     cf* const W = W0 + (size_t)(two_slots ? (k & 1u) : 0u) * (size_t)f.N;
     const cf* const x = f.in + tr * f.in_pitch;
-    // Software pipeline over a workgroup's tiles (MI355_RT1K_PREFETCH = P, experiment): P of the next tile's 64 loads per thread are requested
+    // Software pipeline over a workgroup's tiles (MI355_RT1K_PREFETCH_A / _B = P): P of the next tile's 64 loads per thread are requested
     // as soon as the second exchange half has left the registers that held this tile, i.e. they are in flight while both consumers'
-    // stage 1 computes and stores; the rest follows at the top of the next iteration.  Off by default: the registers they pin cost more
-    // (spills) than the overlap gains.
+    // stage 1 computes and stores; the rest follows at the top of the next iteration.  No request crosses the A | B barrier (W cannot be
+    // read before it, and xcd_arrive's vmcnt(0) would only drain it); on an early return outstanding loads are dropped, no global store follows.
     // ---- phase A: 32 adjacent columns per tile ----
     if constexpr (N1_ == 2048) {
       for (unsigned tile = rank; tile < N2 / 16; tile += gsize) {
@@ -837,9 +870,8 @@ __global__ void __launch_bounds__(Rt1kCfgT<T>::THREADS, 2) fft_xcd_rt1k_kernel(c
         rt_finish_cols(v, W, N2, tile * 16u, t, xb, tw2, [](cf (&)[64]) {});
       }
     } else {
-      cf va[32], vb[32], w[32];
       const unsigned voff = (unsigned)h * N2 + (unsigned)cl;
-      constexpr int PF = MI355_RT1K_PREFETCH;     // how many of va's 32 loads are requested one tile ahead
+      constexpr int PF = PFA;     // how many of va's 32 loads are requested one tile ahead
       const auto load_x = [&](const cf* p, unsigned row_uniform, unsigned tile) {     // element (row_uniform + h) * N2 + tile * T + cl of the line
         if constexpr (VIEW) {
           const int i = (int)((row_uniform + (unsigned)h) * N2 + tile * TU + (unsigned)cl);
@@ -847,7 +879,7 @@ __global__ void __launch_bounds__(Rt1kCfgT<T>::THREADS, 2) fft_xcd_rt1k_kernel(c
           cf xv = {0.0f, 0.0f};
           if (i >= f.v_in_lo && i < f.v_in_hi) xv = *pe;
           return cswap_if<INV>(xv);
-        } else return cswap_if<INV>(ld_stream<MI355_RT1K_NT_IN != 0>(sgpr_base(p + row_uniform * N2) + voff));
+        } else return cswap_if<INV && !LATE_SWAP>(ld_stream<MI355_RT1K_NT_IN != 0>(sgpr_base(p + row_uniform * N2) + voff));
       };
       const auto load_a = [&](unsigned tile, int q0, int q1) {
         const cf* p = x + tile * TU;
@@ -859,10 +891,16 @@ __global__ void __launch_bounds__(Rt1kCfgT<T>::THREADS, 2) fft_xcd_rt1k_kernel(c
 #pragma unroll
         for (int q = 0; q < 32; ++q) vb[q] = load_x(p, (unsigned)(32 * q + 16), tile);
       };
-      if (PF && rank < NT) load_a(rank, 0, PF);
+      // the first tile's head: past a group's first transform the boundary prefetch (phase B below) has requested PFX loads of it
+      if (PF && rank < NT && !(PFX && k > 0)) load_a(rank, 0, PF);
       for (unsigned tile = rank; tile < NT; tile += gsize) {
-        load_a(tile, PF, 32);
+        if (PFX != PF && PFX && k > 0 && tile == rank) load_a(tile, PFX, 32);
+        else load_a(tile, PF, 32);
         load_b(tile);
+        if constexpr (LATE_SWAP) {
+#pragma unroll
+          for (int q = 0; q < 32; ++q) { va[q] = cswap_if<true>(va[q]); vb[q] = cswap_if<true>(vb[q]); }
+        }
         fft_radix<32>(va);
         fft_radix<32>(vb);
         cf* const po = W + tile * TU;
@@ -891,9 +929,8 @@ __global__ void __launch_bounds__(Rt1kCfgT<T>::THREADS, 2) fft_xcd_rt1k_kernel(c
     // ---- phase B: 32 adjacent rows per tile, four-step roots on load, transposed store ----
     cf* const y = f.out + tr * f.out_pitch;
     {
-      cf va[32], vb[32], w[32];
       const unsigned lo = (unsigned)rl * N2 + 2u * (unsigned)hh;
-      constexpr int PF = MI355_RT1K_PREFETCH / 2;  // how many of the 32 16-byte loads are requested one tile ahead
+      constexpr int PF = PFB;  // how many of the 32 16-byte loads are requested one tile ahead
       const auto load_rows = [&](unsigned tile, int q0, int q1) {      // elements 2hh + 32q and 2hh + 1 + 32q of row 32 tile + rl, q = q0 .. q1 - 1
         const cf* p = W + (size_t)(tile * TU) * N2;
 #pragma unroll
@@ -938,6 +975,19 @@ __global__ void __launch_bounds__(Rt1kCfgT<T>::THREADS, 2) fft_xcd_rt1k_kernel(c
         };
         rt1k_exchange<T>(va, vb, w, xb, rl, 2 * hh, 2 * hh + 1, cl, h, [&] {
           if (PF && tile + gsize < NT) load_rows(tile + gsize, 0, PF);
+          // Boundary prefetch: in this workgroup's last tile of the transform nothing of W is left to request, so the head of its first
+          // phase-A tile of the group's NEXT transform is: rows 32 q + h, q < PFX, of columns rank * 32 + cl of that line (phase A's map:
+          // so is its voff, N1 = N2).  x depends on nothing, and the line exists only if tr + groups < num_transforms: no request
+          // otherwise.  The loads fly during both stage 1s, the output stores and the loop back-edge.  Two slots pipeline the same way (no
+          // barrier in between); with MI355_RT1K_SPLIT_HANDOFF=0 the plain arrive at the end of the transform drains them first (vmcnt(0)).
+          // In place the line tr + groups is written by nobody before this group's own phase B of it.
+          if constexpr (PFX != 0) {
+            if (tile + gsize >= NT && tr + (long long)groups < f.num_transforms) {
+              const cf* const pn = f.in + (tr + (long long)groups) * f.in_pitch + rank * TU;
+#pragma unroll
+              for (int q = 0; q < PFX; ++q) va[q] = cswap_if<INV && !LATE_SWAP>(ld_stream<MI355_RT1K_NT_IN != 0>(sgpr_base(pn + (unsigned)(32 * q) * N2) + so));
+            }
+          }
           // last tile: every wave wrote an exchange half and passed a workgroup barrier since, so all of this workgroup's loads of W have
           // returned (they were the operands of that write).  Reads, not stores, are signalled: no vmcnt(0) (kern_xcd.hpp).
           if (SPLIT_HANDOFF && !two_slots && tile + gsize >= NT) xcd_arrive_reads(&f.ctl->bar[gslot][1], so == 0u);
