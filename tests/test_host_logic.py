@@ -125,3 +125,28 @@ def test_xcd_resident_route_is_opt_in_and_needs_whole_xcds(monkeypatch):
     route, launches, work = emu.plan_only(d)
     assert route.startswith("xcd-resident[N=1024x1024,depth=4]") and launches == 2 and work >= 16 * 4 * (1 << 20)
     assert emu.plan_only(d, compute_units=250)[0].startswith("xcd-fused")      # not a multiple of 32 CUs: no resident groups
+
+
+def test_every_line_launch_carries_a_named_mode():
+    """plan.hpp LineMode: slot i[LS_MODE] (i[9]) of every ST_LINES step (kind 0) is one of the modes dispatch.hpp knows.  Planner only."""
+    import emu_harness as emu
+    from mi355fft import _abi
+    line_modes = {0: "c2c", 1: "r2c", 2: "c2r", 4: "mul", 5: "dct2", 6: "dst2", 7: "dct3", 8: "dst3", 9: "rconv", 10: "rconv-ols"}
+    conv = {"mode": "correlation", "boundary": "linear-same", "kernelCount": 2}
+    requests = [_abi.make_desc("c2c", [1024], 8, "forward", "none"), _abi.make_desc("c2c", [64, 32], 2, "inverse", "none"),
+                _abi.make_desc("c2c", [1009], 4, "forward", "none"), _abi.make_desc("r2c", [2048], 8, "forward", "none"),
+                _abi.make_desc("c2r", [2048], 8, "inverse", "none"), _abi.make_desc("dct2", [1024], 8, "forward", "none"),
+                _abi.make_desc("dst2", [1024], 8, "forward", "none"), _abi.make_desc("dct3", [1024], 8, "forward", "none"),
+                _abi.make_desc("dst3", [1024], 8, "forward", "none"),
+                _abi.make_desc("fftconv", [1024], batch=4096, conv={"kernelCount": 3}),
+                _abi.make_desc("fftconv-real", [256], batch=8, conv=dict(conv, kernelShape=[9])),
+                _abi.make_desc("fftconv-real", [100000], batch=4, conv=dict(conv, kernelShape=[129]))]
+    seen = set()
+    for desc in requests:
+        rc, text = emu.plan_dump(desc)
+        assert rc == 0, text
+        modes = [int(m.group(1).split(",")[9]) for m in re.finditer(r"^step \d+ kind=0 .* i=([-\d,]+) f=", text, re.M)]
+        assert modes, text.splitlines()[0]
+        assert all(m in line_modes for m in modes), (text.splitlines()[0], modes)
+        seen.update(modes)
+    assert seen == set(line_modes), sorted(line_modes[m] for m in set(line_modes) - seen)

@@ -64,7 +64,7 @@ struct mi355fft_buffer {
   bool owned = false;
   AliveToken alive = std::make_shared<bool>(true);
 };
-struct RecordedOp { Step step; void* ptr[5]; };
+struct RecordedOp { Step step; void* ptr[STEP_PTRS]; };
 struct mi355fft_encoder {
   mi355fft_device* dev = nullptr;
   std::vector<RecordedOp> ops;
@@ -265,7 +265,7 @@ MI_API int mi355fft_buffer_read(mi355fft_buffer* buf, uint64_t offset_bytes, voi
 
 // ---- plans -----------------------------------------------------------------------------------------
 namespace {
-bool step_needs_coresidency(const Step& s) { return s.kind == ST_XCD_RES || (s.kind == ST_XCD_FUSED && s.i[12] == 0); }
+bool step_needs_coresidency(const Step& s) { return s.kind == ST_XCD_RES || (s.kind == ST_XCD_FUSED && s.i[XS_SOLO] == 0); }
 
 // Plans `desc` for `dev` into p->ir and uploads the tables.  Steps whose workgroups synchronise with each other are only kept
 // when the runtime's occupancy answer covers the grid the planner sized for them (all of it resident at once); otherwise, and
@@ -430,7 +430,7 @@ MI_API int mi355fft_plan_exec(mi355fft_plan* plan, mi355fft_encoder* enc, const 
   for (const Step& s : plan->ir.steps) {
     RecordedOp op;
     op.step = s;
-    for (int i = 0; i < 5; ++i) op.ptr[i] = s.p[i].buf == BUF_NONE ? nullptr : base[s.p[i].buf] + s.p[i].off;
+    for (int i = 0; i < STEP_PTRS; ++i) op.ptr[i] = s.p[i].buf == BUF_NONE ? nullptr : base[s.p[i].buf] + s.p[i].off;
     enc->ops.push_back(op);
   }
   enc->deps.push_back(plan->alive);
@@ -477,10 +477,10 @@ MI_API int mi355fft_encoder_copy_buffer(mi355fft_encoder* enc, mi355fft_buffer* 
   if (bytes % 4 || src_offset % 4 || dst_offset % 4) return fail(MI355FFT_ERR_INVALID, "copyBufferToBuffer: offsets and size must be multiples of 4");
   RecordedOp op;
   op.step.kind = ST_COPY;
-  op.step.i[0] = (int64_t)bytes;
+  op.step.i[S_COUNT] = (int64_t)bytes;
   std::memset(op.ptr, 0, sizeof op.ptr);
-  op.ptr[0] = (char*)src->ptr + src_offset;
-  op.ptr[1] = (char*)dst->ptr + dst_offset;
+  op.ptr[P_SRC] = (char*)src->ptr + src_offset;
+  op.ptr[P_DST] = (char*)dst->ptr + dst_offset;
   enc->ops.push_back(op);
   enc->deps.push_back(src->alive);
   enc->deps.push_back(dst->alive);

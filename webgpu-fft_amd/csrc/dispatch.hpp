@@ -80,48 +80,48 @@ bool launch_lines_family(int id, const LineArgs& a, unsigned grid, L& l) {
       using C = LineCfg<N, R0, R1, R2, T, IC, OC, SI, SO, TW>;                           \
       if constexpr ((TW) == 4) {   /* ROW_ALT_TRIG: only the one-launch DCT / DST kernels exist for these shapes */ \
         if constexpr (!(SI)) {                                                           \
-          if (a.real_mode == 5 || a.real_mode == 6) { l.launch(fft_lines_r2c_kernel<C, true>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a); return true; } \
+          if (a.real_mode == LM_DCT2 || a.real_mode == LM_DST2) { l.launch(fft_lines_r2c_kernel<C, true>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a); return true; } \
         } else {                                                                         \
-          if (a.real_mode == 7 || a.real_mode == 8) { l.launch(fft_lines_c2r_kernel<C, true>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a); return true; } \
+          if (a.real_mode == LM_DCT3 || a.real_mode == LM_DST3) { l.launch(fft_lines_c2r_kernel<C, true>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a); return true; } \
         }                                                                                \
         return false;                                                                    \
       } else {                                                                           \
       if constexpr (!(IC) && !(OC) && !(SI) && !(SO) && (TW) == 0 && C::NSTAGES >= 2) {   \
-        if (a.real_mode == 1) {                                                          \
+        if (a.real_mode == LM_R2C) {                                                     \
           if (a.mapped) l.launch(fft_lines_r2c_kernel<C, false, true>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a); \
           else if (a.h16) l.launch(fft_lines_r2c_kernel<C, false, false, true>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a); \
           else l.launch(fft_lines_r2c_kernel<C>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a); \
           return true;                                                                   \
         }                                                                                \
-        if (a.real_mode == 5 || a.real_mode == 6) {                                      \
+        if (a.real_mode == LM_DCT2 || a.real_mode == LM_DST2) {                          \
           l.launch(fft_lines_r2c_kernel<C, true>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a); \
           return true;                                                                   \
         }                                                                                \
-        if (a.real_mode == 9) return launch_lines_rconv<C>(a, grid, l);                   \
-        if (a.real_mode == 4) {                                                          \
+        if (a.real_mode == LM_RCONV) return launch_lines_rconv<C>(a, grid, l);            \
+        if (a.real_mode == LM_MUL) {                                                     \
           if (a.mapped) l.launch(fft_lines_mul_kernel<C, true>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a); \
           else l.launch(fft_lines_mul_kernel<C>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a); \
           return true;                                                                   \
         }                                                                                \
       }                                                                                  \
       if constexpr (!(IC) && !(OC) && (SI) && (SO) && (TW) == 0) {                        \
-        if (a.real_mode == 2 && !a.mapped) {                                             \
+        if (a.real_mode == LM_C2R && !a.mapped) {                                        \
           if (a.h16) l.launch(fft_lines_c2r_kernel<C, false, false, true>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a); \
           else l.launch(fft_lines_c2r_kernel<C>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a); \
           return true;                                                                   \
         }                                                                                \
         if constexpr (C::NSTAGES >= 2) {                                                 \
-          if (a.real_mode == 2) {                                                        \
+          if (a.real_mode == LM_C2R) {                                                   \
             l.launch(fft_lines_c2r_kernel<C, false, true>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a); \
             return true;                                                                 \
           }                                                                              \
-          if (a.real_mode == 7 || a.real_mode == 8) {                                    \
+          if (a.real_mode == LM_DCT3 || a.real_mode == LM_DST3) {                        \
             l.launch(fft_lines_c2r_kernel<C, true>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a); \
             return true;                                                                 \
           }                                                                              \
         }                                                                                \
       }                                                                                  \
-      if (a.real_mode != 0) return false;                                                \
+      if (a.real_mode != LM_C2C) return false;                                           \
       if constexpr ((IC) == (OC) && (TW) == 0) {                                         \
         if (a.mapped) {                                                                  \
           l.launch(fft_lines_mapped_kernel<C>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a); \
@@ -307,46 +307,48 @@ template <class L> bool launch_stage(int radix, const StageArgs& a, unsigned gri
 // LinesFn: bool(int family, int id, const LineArgs&, unsigned grid) — supplied by the caller because the
 // per-family instantiations live in different translation units in the product build.
 template <class L, class LinesFn, class XcdFn>
-bool dispatch_step(const Step& s, void* const ptr[5], L& l, LinesFn&& lines_fn, XcdFn&& xcd_fn) {
+bool dispatch_step(const Step& s, void* const ptr[STEP_PTRS], L& l, LinesFn&& lines_fn, XcdFn&& xcd_fn) {
   switch (s.kind) {
     case ST_XCD_RES:
     case ST_XCD_FUSED: {
       XcdFusedArgs a{};
-      a.in = (const cf*)ptr[0]; a.out = (cf*)ptr[1]; a.wslots = (cf*)ptr[2]; a.ctl = (XcdCtl*)ptr[3];
-      const char* tb = (const char*)ptr[4];
-      a.tw_a = (const cf*)(tb + s.i[4]); a.tw_b = (const cf*)(tb + s.i[5]); a.tw_lo = (const cf*)(tb + s.i[6]); a.tw_hi = (const cf*)(tb + s.i[7]);
-      a.num_transforms = s.i[0]; a.N = s.i[1]; a.fs_shift = (int)s.i[2]; a.fs_lo_mask = (unsigned)s.i[3];
-      a.in_pitch = s.i[9]; a.out_pitch = s.i[10];
-      a.scale = s.f[0];
+      a.in = (const cf*)ptr[XP_IN]; a.out = (cf*)ptr[XP_OUT]; a.wslots = (cf*)ptr[XP_WSLOTS]; a.ctl = (XcdCtl*)ptr[XP_CTL];
+      const char* tb = (const char*)ptr[XP_TABLE];
+      a.tw_a = (const cf*)(tb + s.i[XS_TW_A_OFF]); a.tw_b = (const cf*)(tb + s.i[XS_TW_B_OFF]); a.tw_lo = (const cf*)(tb + s.i[XS_TW_LO_OFF]); a.tw_hi = (const cf*)(tb + s.i[XS_TW_HI_OFF]);
+      a.num_transforms = s.i[XS_TRANSFORMS]; a.N = s.i[XS_N]; a.fs_shift = (int)s.i[XS_FS_SHIFT]; a.fs_lo_mask = (unsigned)s.i[XS_FS_LO_MASK];
+      a.in_pitch = s.i[XS_IN_PITCH]; a.out_pitch = s.i[XS_OUT_PITCH];
+      a.scale = s.f[F_SCALE];
       a.sticky_error = l.sticky_error_word();
-      a.spin_limit = s.i[13] > 0 ? (unsigned)s.i[13] : 4000000u;
-      a.split = (unsigned)s.i[8]; a.slots = (unsigned)s.i[11]; a.solo = (unsigned)s.i[12];
-      a.conv_k = (unsigned)s.i[15]; a.conv_conj = (unsigned)s.i[16]; a.out_kernel_pitch = s.i[17];
-      a.mul = a.conv_k ? (const cf*)((const char*)ptr[2] + s.i[14]) : nullptr;   // the kernel spectra sit in the same workspace arena as the slots
+      a.spin_limit = s.i[XS_SPIN_LIMIT] > 0 ? (unsigned)s.i[XS_SPIN_LIMIT] : 4000000u;
+      a.split = (unsigned)s.i[XS_SPLIT]; a.slots = (unsigned)s.i[XS_SLOTS]; a.solo = (unsigned)s.i[XS_SOLO];
+      a.conv_k = (unsigned)s.i[XS_CONV_K]; a.conv_conj = (unsigned)s.i[XS_CONV_CONJ]; a.out_kernel_pitch = s.i[XS_OUT_KERNEL_PITCH];
+      a.mul = a.conv_k ? (const cf*)((const char*)ptr[XP_WSLOTS] + s.i[XS_MUL_OFF]) : nullptr;   // the kernel spectra sit in the same workspace arena as the slots
       a.v_in_lo = (int)s.imap.lo[0]; a.v_in_hi = (int)s.imap.hi[0]; a.v_out_lo = (int)s.omap.lo[0]; a.v_out_hi = (int)s.omap.hi[0];
       a.v_zlo = (int)s.omap.zlo[0]; a.v_zhi = (int)s.omap.zhi[0];   // (VIEW instances only; the planner fills the two maps)
-      a.v_split = (int)s.i[18]; a.v_shift = (int)s.i[19];              // (CONV_VIEW only)
+      a.v_split = (int)s.i[XS_V_SPLIT]; a.v_shift = (int)s.i[XS_V_SHIFT];              // (CONV_VIEW only)
       if (s.kind == ST_XCD_RES) return launch_xcd_res(s.variant, a, s.grid, l);
       return xcd_fn(s.variant, a, s.grid);
     }
     case ST_LINES: {
       LineArgs a{};
-      a.in = (const cf*)ptr[0]; a.out = (cf*)ptr[1]; a.tw = (const cf*)ptr[2]; a.tw_lo = (const cf*)ptr[3]; a.tw_hi = (const cf*)ptr[4];
-      a.num_tiles = s.i[0]; a.num_lines = s.i[1];
-      a.in_S = s.i[2]; a.in_outer_stride = s.i[3]; a.out_S = s.i[4]; a.out_outer_stride = s.i[5];
-      a.fs_shift = (int)s.i[6]; a.fs_lo_mask = (unsigned)s.i[7]; a.fs_group = s.i[8] ? s.i[8] : 1; a.real_mode = (int)s.i[9];
-      a.mapped = (int)s.i[10];
+      a.in = (const cf*)ptr[LP_IN]; a.out = (cf*)ptr[LP_OUT]; a.tw = (const cf*)ptr[LP_TW]; a.tw_lo = (const cf*)ptr[LP_TW_LO]; a.tw_hi = (const cf*)ptr[LP_TW_HI];
+      a.num_tiles = s.i[LS_TILES]; a.num_lines = s.i[LS_LINES];
+      a.in_S = s.i[LS_IN_S]; a.in_outer_stride = s.i[LS_IN_OUTER]; a.out_S = s.i[LS_OUT_S]; a.out_outer_stride = s.i[LS_OUT_OUTER];
+      a.fs_shift = (int)s.i[LS_FS_SHIFT]; a.fs_lo_mask = (unsigned)s.i[LS_FS_LO_MASK]; a.fs_group = s.i[LS_FS_GROUP] ? s.i[LS_FS_GROUP] : 1; a.real_mode = (int)s.i[LS_MODE];
+      // (LM_MUL and Bluestein's mapped launches have no four-step roots: i[LS_MUL_CONJ], i[LS_CHIRP_FLAGS] are these two slots, and the kernels read
+      // them as a.mul_conj, a.chirp_flags, the second names of the same two fields)
+      a.mapped = (int)s.i[LS_MAPPED];
       if (a.mapped) { a.imap = s.imap; a.omap = s.omap; }
-      a.h16 = (int)s.i[11];
-      a.scale = s.f[0];
-      if (a.real_mode == 9) {   // real fftconv line: p[4] (tw_hi) is the packed kernel spectrum; the HI roots sit directly behind the 1024 LO roots (one table)
-        a.v_out_lo = (int)s.i[12]; a.v_in_lo = (int)s.i[13]; a.v_in_hi = (int)s.i[14];
+      a.h16 = (int)s.i[LS_H16];
+      a.scale = s.f[F_SCALE];
+      if (a.real_mode == LM_RCONV) {   // real fftconv line: p[LP_RCONV_SPECTRUM] (tw_hi) is the packed kernel spectrum; the HI roots sit directly behind the 1024 LO roots (one table)
+        a.conj = (int)s.i[LS_CONJ]; a.rconv_split = (int)s.i[LS_RCONV_SPLIT]; a.rconv_padD = (int)s.i[LS_RCONV_PADD];
       }
-      if (a.real_mode == 10) {  // its overlap-save form: no padded domain; the block geometry in an argument block of its own (kern_lines.hpp RconvOls)
+      if (a.real_mode == LM_RCONV_OLS) {  // its overlap-save form: no padded domain; the block geometry in an argument block of its own (kern_lines.hpp RconvOls)
         RconvOlsArgs oa{};
-        a.v_out_lo = (int)s.i[12];
+        a.conj = (int)s.i[LS_CONJ];
         oa.a = a;
-        oa.o.fN = (int)s.i[13]; oa.o.plim = (int)s.i[14]; oa.o.nb = (int)s.i[15]; oa.o.L = (int)s.i[16]; oa.o.w0 = (int)s.i[17]; oa.o.pre = (int)s.i[18];
+        oa.o.fN = (int)s.i[LS_OLS_FN]; oa.o.plim = (int)s.i[LS_OLS_PLIM]; oa.o.nb = (int)s.i[LS_OLS_NB]; oa.o.L = (int)s.i[LS_OLS_L]; oa.o.w0 = (int)s.i[LS_OLS_W0]; oa.o.pre = (int)s.i[LS_OLS_PRE];
         return launch_lines_rconv_ols(s.variant, oa, s.grid, l);
       }
       const LineKernelMeta& m = line_kernel_registry()[(size_t)s.variant];
@@ -355,126 +357,126 @@ bool dispatch_step(const Step& s, void* const ptr[5], L& l, LinesFn&& lines_fn, 
     case ST_TRIG_PRE:
     case ST_TRIG_POST: {
       TrigArgs a{};
-      a.x = (const float*)ptr[0]; a.z = (cf*)ptr[1]; a.y = (float*)ptr[2];
-      a.lines = s.i[0]; a.N = s.i[1]; a.L = s.i[2]; a.S = s.i[3]; a.kind = (int)s.i[4]; a.scale = s.f[0]; a.stride = s.i[5] ? s.i[5] : 1;
-      if (a.kind >= 8 && a.stride > 1) {
+      a.x = (const float*)ptr[TGP_X]; a.z = (cf*)ptr[TGP_Z]; a.y = (float*)ptr[TGP_Y];
+      a.lines = s.i[TG_LINES]; a.N = s.i[TG_N]; a.L = s.i[TG_L]; a.S = s.i[TG_S]; a.kind = (int)s.i[TG_KIND]; a.scale = s.f[F_SCALE]; a.stride = s.i[TG_STRIDE] ? s.i[TG_STRIDE] : 1;
+      if (a.kind >= TK_REAL && a.stride > 1) {
         if (s.kind == ST_TRIG_PRE) l.launch(trig_real_pre_tiled_kernel, s.grid, 256u, 0u, a); else l.launch(trig_real_post_tiled_kernel, s.grid, 256u, 0u, a);
-      } else if (a.kind >= 8) {
+      } else if (a.kind >= TK_REAL) {
         if (s.kind == ST_TRIG_PRE) l.launch(trig_real_pre_kernel, s.grid, 256u, 0u, a); else l.launch(trig_real_post_kernel, s.grid, 256u, 0u, a);
       } else if (s.kind == ST_TRIG_PRE) l.launch(trig_pre_kernel, s.grid, 256u, 0u, a); else l.launch(trig_post_kernel, s.grid, 256u, 0u, a);
       return true;
     }
     case ST_LINES_MIXED: {
       MixedArgs a{};
-      a.in = (const cf*)ptr[0]; a.out = (cf*)ptr[1]; a.tw = (const cf*)ptr[2];
-      a.lines = s.i[0]; a.N = (int)s.i[1]; a.S = s.i[2]; a.T = (int)s.i[3]; a.nst = (int)s.i[4];
-      a.swap_in = a.swap_out = (int)s.i[5];
-      a.scale = s.f[0];
+      a.in = (const cf*)ptr[P_SRC]; a.out = (cf*)ptr[P_DST]; a.tw = (const cf*)ptr[P_TW];
+      a.lines = s.i[MX_LINES]; a.N = (int)s.i[MX_N]; a.S = s.i[MX_S]; a.T = (int)s.i[MX_T]; a.nst = (int)s.i[MX_NST];
+      a.swap_in = a.swap_out = (int)s.i[MX_SWAP];
+      a.scale = s.f[F_SCALE];
       if (s.variant >= 1000) return launch_line_reg(s.variant - 1000, a, s.grid, l);   // 2^13 .. 2^15 in one workgroup's registers (kern_line_reg.hpp)
       if (s.variant > 0) return launch_mixedct(s.variant - 1, a, s.grid, l);   // compile-time plan: nothing else to pass
       {
         const auto rcp = [](unsigned d) { return d > 1 ? (unsigned)((0x100000000ull + d - 1) / d) : 0u; };
         unsigned nsp = 1;
         for (int k = 0; k < a.nst; ++k) {
-          a.radix[k] = (int)(s.i[8 + k] >> 32); a.tw_off[k] = (int)(s.i[8 + k] & 0xffffffff);
+          a.radix[k] = (int)(s.i[MX_RADIX0 + k] >> 32); a.tw_off[k] = (int)(s.i[MX_RADIX0 + k] & 0xffffffff);
           a.rcp_nb[k] = rcp((unsigned)(a.N / a.radix[k])); a.rcp_nsp[k] = rcp(nsp);
           nsp *= (unsigned)a.radix[k];
         }
       }
-      a.lds_bytes = (int)s.i[6]; a.tw_total = (int)s.i[19];
-      l.launch(fft_lines_mixed_kernel, s.grid, (unsigned)s.i[7], (unsigned)(a.lds_bytes + MIXED_MAX_T * 8 + a.tw_total * 8), a);
+      a.lds_bytes = (int)s.i[MX_LDS_BYTES]; a.tw_total = (int)s.i[MX_TW_TOTAL];
+      l.launch(fft_lines_mixed_kernel, s.grid, (unsigned)s.i[MX_THREADS], (unsigned)(a.lds_bytes + MIXED_MAX_T * 8 + a.tw_total * 8), a);
       return true;
     }
     case ST_STAGE: {
       StageArgs a{};
-      a.in = (const cf*)ptr[0]; a.out = (cf*)ptr[1]; a.tw = (const cf*)ptr[2];
-      a.total = s.i[0]; a.N = s.i[1]; a.S = s.i[2]; a.Nsp = s.i[3]; a.swap_in = (int)s.i[4]; a.swap_out = (int)s.i[5];
-      a.scale = s.f[0];
+      a.in = (const cf*)ptr[P_SRC]; a.out = (cf*)ptr[P_DST]; a.tw = (const cf*)ptr[P_TW];
+      a.total = s.i[SG_TOTAL]; a.N = s.i[SG_N]; a.S = s.i[SG_S]; a.Nsp = s.i[SG_NSP]; a.swap_in = (int)s.i[SG_SWAP_IN]; a.swap_out = (int)s.i[SG_SWAP_OUT];
+      a.scale = s.f[F_SCALE];
       return launch_stage(s.variant, a, s.grid, l);
     }
     case ST_R2C_POST: {
       R2cPostArgs a{};
-      a.z = (const cf*)ptr[0]; a.x = (cf*)ptr[1]; a.tw_lo = (const cf*)ptr[2]; a.tw_hi = (const cf*)ptr[3];
-      a.H = s.i[0]; a.batch = s.i[1]; a.x_line_stride = s.i[2]; a.scale = s.f[0]; a.shift = (int)s.i[3]; a.mask = (unsigned)s.i[4];
+      a.z = (const cf*)ptr[P_SRC]; a.x = (cf*)ptr[P_DST]; a.tw_lo = (const cf*)ptr[RSP_TW_LO]; a.tw_hi = (const cf*)ptr[RSP_TW_HI];
+      a.H = s.i[RS_H]; a.batch = s.i[RS_BATCH]; a.x_line_stride = s.i[RS_LINE_STRIDE]; a.scale = s.f[F_SCALE]; a.shift = (int)s.i[RS_SHIFT]; a.mask = (unsigned)s.i[RS_MASK];
       l.launch(r2c_post_kernel, s.grid, 256u, 0u, a);
       return true;
     }
     case ST_C2R_PRE: {
       C2rPreArgs a{};
-      a.x = (const cf*)ptr[0]; a.z = (cf*)ptr[1]; a.tw_lo = (const cf*)ptr[2]; a.tw_hi = (const cf*)ptr[3];
-      a.H = s.i[0]; a.batch = s.i[1]; a.x_line_stride = s.i[2]; a.shift = (int)s.i[3]; a.mask = (unsigned)s.i[4];
+      a.x = (const cf*)ptr[P_SRC]; a.z = (cf*)ptr[P_DST]; a.tw_lo = (const cf*)ptr[RSP_TW_LO]; a.tw_hi = (const cf*)ptr[RSP_TW_HI];
+      a.H = s.i[RS_H]; a.batch = s.i[RS_BATCH]; a.x_line_stride = s.i[RS_LINE_STRIDE]; a.shift = (int)s.i[RS_SHIFT]; a.mask = (unsigned)s.i[RS_MASK];
       l.launch(c2r_pre_kernel, s.grid, 256u, 0u, a);
       return true;
     }
     case ST_REAL_TO_COMPLEX:
-      l.launch(real_to_complex_kernel, s.grid, 256u, 0u, (const float*)ptr[0], (cf*)ptr[1], (long long)s.i[0]);
+      l.launch(real_to_complex_kernel, s.grid, 256u, 0u, (const float*)ptr[P_SRC], (cf*)ptr[P_DST], (long long)s.i[S_COUNT]);
       return true;
     case ST_COMPLEX_TO_REAL:
-      l.launch(complex_to_real_kernel, s.grid, 256u, 0u, (const cf*)ptr[0], (float*)ptr[1], (long long)s.i[0], s.f[0]);
+      l.launch(complex_to_real_kernel, s.grid, 256u, 0u, (const cf*)ptr[P_SRC], (float*)ptr[P_DST], (long long)s.i[S_COUNT], s.f[F_SCALE]);
       return true;
     case ST_PACK_HALF:
-      l.launch(pack_half_kernel, s.grid, 256u, 0u, (const cf*)ptr[0], (cf*)ptr[1], (long long)s.i[0], (long long)s.i[1], (long long)s.i[2],
-               (long long)s.i[3], s.f[0]);
+      l.launch(pack_half_kernel, s.grid, 256u, 0u, (const cf*)ptr[P_SRC], (cf*)ptr[P_DST], (long long)s.i[PH_N], (long long)s.i[PH_P], (long long)s.i[PH_BATCH],
+               (long long)s.i[PH_PACKED_STRIDE], s.f[F_SCALE]);
       return true;
     case ST_UNPACK_HERM:
-      l.launch(unpack_hermitian_kernel, s.grid, 256u, 0u, (const cf*)ptr[0], (cf*)ptr[1], (long long)s.i[0], (long long)s.i[1],
-               (long long)s.i[2], (long long)s.i[3]);
+      l.launch(unpack_hermitian_kernel, s.grid, 256u, 0u, (const cf*)ptr[P_SRC], (cf*)ptr[P_DST], (long long)s.i[PH_N], (long long)s.i[PH_P],
+               (long long)s.i[PH_BATCH], (long long)s.i[PH_PACKED_STRIDE]);
       return true;
     case ST_POINTWISE:
-      l.launch(pointwise_mul_kernel, s.grid, 256u, 0u, (const cf*)ptr[0], (cf*)ptr[1], (const cf*)ptr[2], (long long)s.i[0], (long long)s.i[1],
-               (int)s.i[2], s.f[0]);
+      l.launch(pointwise_mul_kernel, s.grid, 256u, 0u, (const cf*)ptr[P_SRC], (cf*)ptr[P_DST], (const cf*)ptr[PWP_KERNEL], (long long)s.i[PW_L], (long long)s.i[PW_TOTAL],
+               (int)s.i[PW_CONJ], s.f[F_SCALE]);
       return true;
     case ST_GATHER:
     case ST_SCATTER: {
       StridedArgs a{};
-      a.src = ptr[0]; a.dst = ptr[1];
-      a.total = s.i[0]; a.per = s.i[1]; a.rank = (int)s.i[2];
-      a.phys_offset = s.i[3]; a.phys_batch_stride = s.i[4]; a.dense_offset = s.i[5]; a.dense_batch_stride = s.i[6];
+      a.src = ptr[P_SRC]; a.dst = ptr[P_DST];
+      a.total = s.i[GS_TOTAL]; a.per = s.i[GS_PER]; a.rank = (int)s.i[GS_RANK];
+      a.phys_offset = s.i[GS_PHYS_OFFSET]; a.phys_batch_stride = s.i[GS_PHYS_BATCH_STRIDE]; a.dense_offset = s.i[GS_DENSE_OFFSET]; a.dense_batch_stride = s.i[GS_DENSE_BATCH_STRIDE];
       for (int d = 0; d < 8; ++d) { a.shape[d] = s.shape[d] ? s.shape[d] : 1; a.phys_stride[d] = s.sa[d]; a.dense_stride[d] = s.sb[d]; }
-      const bool real = s.i[7] != 0;     // element type: 0 complex, 1 real (r2c input / c2r output sides)
+      const bool real = s.i[GS_REAL] != 0;     // element type: 0 complex, 1 real (r2c input / c2r output sides)
       if (s.kind == ST_GATHER) { if (real) l.launch(strided_copy_kernel<true, float>, s.grid, 256u, 0u, a); else l.launch(strided_copy_kernel<true, cf>, s.grid, 256u, 0u, a); }
       else { if (real) l.launch(strided_copy_kernel<false, float>, s.grid, 256u, 0u, a); else l.launch(strided_copy_kernel<false, cf>, s.grid, 256u, 0u, a); }
       return true;
     }
     case ST_FFTCONV_FUSED: {
       FusedConvArgs a{};
-      a.in = (const cf*)ptr[0]; a.kern = (const cf*)ptr[1]; a.out = (cf*)ptr[2]; a.tw = (const cf*)ptr[3];
-      a.batch = s.i[0]; a.K = (int)s.i[1]; a.kern_len = (int)s.i[2]; a.conj_kernel = (int)s.i[3];
-      a.in_offset = s.i[4]; a.in_batch_stride = s.i[5]; a.in_stride = s.i[6];
-      a.out_offset = s.i[7]; a.out_kernel_stride = s.i[8]; a.out_batch_stride = s.i[9]; a.out_stride = s.i[10];
-      a.scale = s.f[0];
+      a.in = (const cf*)ptr[FCP_IN]; a.kern = (const cf*)ptr[FCP_KERN]; a.out = (cf*)ptr[FCP_OUT]; a.tw = (const cf*)ptr[FCP_TW];
+      a.batch = s.i[FC_BATCH]; a.K = (int)s.i[FC_K]; a.kern_len = (int)s.i[FC_KERN_LEN]; a.conj_kernel = (int)s.i[FC_CONJ];
+      a.in_offset = s.i[FC_IN_OFFSET]; a.in_batch_stride = s.i[FC_IN_BATCH_STRIDE]; a.in_stride = s.i[FC_IN_STRIDE];
+      a.out_offset = s.i[FC_OUT_OFFSET]; a.out_kernel_stride = s.i[FC_OUT_KERNEL_STRIDE]; a.out_batch_stride = s.i[FC_OUT_BATCH_STRIDE]; a.out_stride = s.i[FC_OUT_STRIDE];
+      a.scale = s.f[F_SCALE];
       return launch_fftconv_fused(s.variant, a, s.grid, l);
     }
     case ST_CHIRP_PRE:
     case ST_CHIRP_POST: {
       ChirpArgs a{};
-      a.in = (const cf*)ptr[0]; a.out = (cf*)ptr[1]; a.chirp = (const cf*)ptr[2];
-      a.N = s.i[0]; a.M = s.i[1]; a.lines = s.i[2]; a.swap_in = (int)s.i[3]; a.swap_out = (int)s.i[4]; a.scale = s.f[0];
+      a.in = (const cf*)ptr[P_SRC]; a.out = (cf*)ptr[P_DST]; a.chirp = (const cf*)ptr[CHP_CHIRP];
+      a.N = s.i[CH_N]; a.M = s.i[CH_M]; a.lines = s.i[CH_LINES]; a.swap_in = (int)s.i[CH_SWAP_IN]; a.swap_out = (int)s.i[CH_SWAP_OUT]; a.scale = s.f[F_SCALE];
       if (s.kind == ST_CHIRP_PRE) l.launch(bluestein_pre_kernel, s.grid, 256u, 0u, a);
       else l.launch(bluestein_post_kernel, s.grid, 256u, 0u, a);
       return true;
     }
     case ST_ZERO_OUTSIDE: {
       ZeroOutsideArgs a{};
-      a.data = ptr[0]; a.total = s.i[0]; a.per = s.i[1]; a.rank = (int)s.i[2];
+      a.data = ptr[P_DATA]; a.total = s.i[ZO_TOTAL]; a.per = s.i[ZO_PER]; a.rank = (int)s.i[ZO_RANK];
       for (int d = 0; d < 8; ++d) { a.shape[d] = s.shape[d] ? s.shape[d] : 1; a.start[d] = s.sa[d]; a.end[d] = d < a.rank ? s.sb[d] : 1; }
-      if (s.i[3]) l.launch(zero_outside_kernel<float>, s.grid, 256u, 0u, a); else l.launch(zero_outside_kernel<cf>, s.grid, 256u, 0u, a);
+      if (s.i[ZO_REAL]) l.launch(zero_outside_kernel<float>, s.grid, 256u, 0u, a); else l.launch(zero_outside_kernel<cf>, s.grid, 256u, 0u, a);
       return true;
     }
     case ST_ZERO:
-      l.launch(zero_kernel, s.grid, 256u, 0u, (float*)ptr[0], (long long)s.i[0]);
+      l.launch(zero_kernel, s.grid, 256u, 0u, (float*)ptr[P_DATA], (long long)s.i[S_COUNT]);
       return true;
     case ST_SCALE:
-      l.launch(scale_kernel, s.grid, 256u, 0u, (float*)ptr[0], (long long)s.i[0], s.f[0]);
+      l.launch(scale_kernel, s.grid, 256u, 0u, (float*)ptr[P_DATA], (long long)s.i[S_COUNT], s.f[F_SCALE]);
       return true;
     case ST_COPY:
-      if (ptr[0] != ptr[1]) l.copy(ptr[1], ptr[0], (size_t)s.i[0]);
+      if (ptr[P_SRC] != ptr[P_DST]) l.copy(ptr[P_DST], ptr[P_SRC], (size_t)s.i[S_COUNT]);
       return true;
     case ST_F16_TO_F32:
-      l.launch(f16_to_f32_kernel, s.grid, 256u, 0u, (const _Float16*)ptr[0], (float*)ptr[1], (long long)s.i[0]);
+      l.launch(f16_to_f32_kernel, s.grid, 256u, 0u, (const _Float16*)ptr[P_SRC], (float*)ptr[P_DST], (long long)s.i[S_COUNT]);
       return true;
     case ST_F32_TO_F16:
-      l.launch(f32_to_f16_kernel, s.grid, 256u, 0u, (const float*)ptr[0], (_Float16*)ptr[1], (long long)s.i[0]);
+      l.launch(f32_to_f16_kernel, s.grid, 256u, 0u, (const float*)ptr[P_SRC], (_Float16*)ptr[P_DST], (long long)s.i[S_COUNT]);
       return true;
   }
   return false;

@@ -97,13 +97,22 @@ struct LineArgs {
   long long in_S, in_outer_stride;
   long long out_S, out_outer_stride;
   float scale;
-  int fs_shift;
-  unsigned fs_lo_mask;
-  int real_mode;         // 4: fft_lines_mul_kernel (tw_lo = kernel spectrum, fs_shift != 0: conjugate it);  1: fft_lines_r2c_kernel (real line read as complex pairs, split fused behind the last stage); 2: fft_lines_c2r_kernel
-                         // 9: fft_lines_rconv_kernel (real fftconv line: r2c, product, c2r in one launch; tw_hi = the packed kernel spectrum, H + 1 bins, and the HI roots sit behind the
-                         //    1024 LO roots at tw_lo + 1024; v_in_lo = split, v_in_hi = padD of the padded-domain index map, v_out_lo != 0: conjugate the spectrum)
+  union { int fs_shift; int mul_conj; };                  // (LM_MUL has no four-step roots: second names)
+  union { unsigned fs_lo_mask; unsigned chirp_flags; };
+  int real_mode;         // LineMode (plan.hpp): which kernel of this file the launch is, and what the fields below mean to it
+                         //   LM_MUL: fft_lines_mul_kernel (tw_lo = kernel spectrum, mul_conj != 0: conjugate it; mapped: chirp_flags holds the LINES_CHIRP bits, tw_hi the chirp)
+                         //   LM_R2C: fft_lines_r2c_kernel (real line read as complex pairs, split fused behind the last stage);  LM_C2R: fft_lines_c2r_kernel
+                         //   LM_DCT2 / LM_DST2, LM_DCT3 / LM_DST3: the TRIG forms of those two
+                         //   LM_RCONV: fft_lines_rconv_kernel (real fftconv line: r2c, product, c2r in one launch; tw_hi = the packed kernel spectrum, H + 1 bins, and the HI
+                         //     roots sit behind the 1024 LO roots at tw_lo + 1024; rconv_split, rconv_padD: the padded-domain index map, conj != 0: conjugate the spectrum)
+                         //   LM_RCONV_OLS: fft_lines_rconv_ols_kernel (the same on overlap-save blocks: RconvOlsArgs)
   long long fs_group;    // TWID_FOURSTEP_IN: lines per group (line index inside the group = G % fs_group); COL_RAGGED: tiles per group
-  int v_in_lo, v_in_hi, v_out_lo, v_out_hi, v_zlo, v_zhi;   // VIEW instantiations of stage_read / stage_compute_write (kern_xcd.hpp fused kernels): rank-1 ranges of a four-step line
+  // VIEW instantiations of stage_read / stage_compute_write (kern_xcd.hpp fused kernels): rank-1 ranges of a four-step line.  The real fftconv
+  // line kernels have no view and keep their own three scalars in the first three (second names)
+  union { int v_in_lo; int rconv_split; };
+  union { int v_in_hi; int rconv_padD; };
+  union { int v_out_lo; int conj; };
+  int v_out_hi, v_zlo, v_zhi;
   int mapped;            // fft_lines_mapped_kernel: both sides go through imap / omap (in / out are the buffers' bases)
   SideMap imap, omap;
   int h16;               // f16-storage: in / out hold binary16 elements (the H16 instances of the dense ROW kernels)
@@ -218,10 +227,16 @@ MI_DEV void fourstep_in_roots(cf (&fsw)[C::E], const LineArgs& a, long long tile
   }
 }
 
+// options of a stage's global side (stage_read: the first stage's loads; stage_compute_write: the last stage's stores), OR-ed into one
+// template argument.  SO_NT: nontemporal accesses; SO_H16: binary16 elements; the others are described at the two functions
+enum : unsigned { SO_NT = 1, SO_KEEP_IN_LDS = 2, SO_MUL = 4, SO_VIEW = 8, SO_H16 = 16 };
+
 // VIEW (column-mapped first stage of a fused four-step kernel): element idx * in_S + (column of the line) of the transform is read inside
 // [v_in_lo, v_in_hi) and is 0 elsewhere (rank-1 ioView.input / zeroPad.read)
-template <class C, int S, bool NT = false, bool VIEW = false, bool H16 = false>
+template <class C, int S, unsigned OPT = 0>
 MI_DEV void stage_read(cf (&v)[C::E], const LineArgs& a, long long tile, int t, const cf* lds) {
+  constexpr bool NT = OPT & SO_NT, VIEW = OPT & SO_VIEW, H16 = OPT & SO_H16;
+  static_assert(!(OPT & (SO_KEEP_IN_LDS | SO_MUL)), "store options on a read");
   using I = StageInfo<C, S>;
   using EL = typename GlobalElem<H16>::T;
   int line, u; thread_map<C, S>(t, line, u);
@@ -269,10 +284,11 @@ MI_DEV void stage_read(cf (&v)[C::E], const LineArgs& a, long long tile, int t, 
 
 // KEEP_IN_LDS: the last stage leaves the finished lines in LDS (same layout as the exchanges) instead of storing them to
 // global memory — for kernels that post-process a whole line before it leaves the workgroup (kern_xcd_real.hpp)
-// MUL: the finished outputs are multiplied by the spectrum a.tw_lo[k] (conjugated when a.fs_shift != 0) on their way out — the
+// MUL: the finished outputs are multiplied by the spectrum a.tw_lo[k] (conjugated when a.mul_conj != 0) on their way out — the
 // pointwise product of fftconv folded into the last stage's register store (fft_lines_mul_kernel)
-template <class C, int S, bool NT = false, bool KEEP_IN_LDS = false, bool MUL = false, bool VIEW = false, bool H16 = false>
+template <class C, int S, unsigned OPT = 0>
 MI_DEV void stage_compute_write(cf (&v)[C::E], const LineArgs& a, long long tile, int t, cf* lds, const cf* tw_lds, const cf* lo_lds) {
+  constexpr bool NT = OPT & SO_NT, KEEP_IN_LDS = OPT & SO_KEEP_IN_LDS, MUL = OPT & SO_MUL, VIEW = OPT & SO_VIEW, H16 = OPT & SO_H16;
   using I = StageInfo<C, S>;
   using EL = typename GlobalElem<H16>::T;
   constexpr bool TO_GLOBAL = I::LAST && !KEEP_IN_LDS;
@@ -341,6 +357,26 @@ MI_DEV void stage_compute_write(cf (&v)[C::E], const LineArgs& a, long long tile
   }
 }
 
+// Stages 0 .. NSTAGES-1 of a tile whose first-stage inputs are in v, for kernels that work on whole finished lines: the last stage leaves
+// them in LDS (the layout of the exchanges) and a workgroup barrier follows.  The ladders whose last stage stores to global memory are
+// written out in their kernels: their device code changes with a function around them (profiles/step_contract_ir_asm_diff.log)
+template <class C>
+MI_DEV void stages_keep_in_lds(cf (&v)[C::E], const LineArgs& a, long long tile, int t, cf* lds, const cf* tw_lds) {
+  static_assert(C::NSTAGES >= 2, "a one-stage line has no LDS buffer");
+  stage_compute_write<C, 0>(v, a, tile, t, lds, tw_lds, nullptr);
+  __syncthreads();
+  stage_read<C, 1>(v, a, tile, t, lds);
+  __syncthreads();
+  stage_compute_write<C, 1, SO_KEEP_IN_LDS>(v, a, tile, t, lds, tw_lds, nullptr);
+  if constexpr (C::NSTAGES == 3) {
+    __syncthreads();
+    stage_read<C, 2>(v, a, tile, t, lds);
+    __syncthreads();
+    stage_compute_write<C, 2, SO_KEEP_IN_LDS>(v, a, tile, t, lds, tw_lds, nullptr);
+  }
+  __syncthreads();
+}
+
 // H16: both sides binary16 (f16-storage plans whose whole route is this one dense launch)
 template <class C, bool H16 = false>
 __global__ void __launch_bounds__(C::THREADS) fft_lines_kernel(const LineArgs a) {
@@ -349,6 +385,7 @@ __global__ void __launch_bounds__(C::THREADS) fft_lines_kernel(const LineArgs a)
   cf* tw_lds = lds + C::DATA_ELEMS;
   cf* lo_lds = tw_lds + C::TW_LDS_ELEMS;
   const int t = threadIdx.x;
+  constexpr unsigned IO = (C::STREAM_NT ? SO_NT : 0) | (H16 ? SO_H16 : 0);   // the global sides: stage 0's loads, the last stage's stores
 
   if constexpr (C::PREFETCH) {
     // (tables first, then the loads: issuing the first tile's loads ahead of the table staging makes every wave of the workgroup
@@ -360,15 +397,15 @@ __global__ void __launch_bounds__(C::THREADS) fft_lines_kernel(const LineArgs a)
     __syncthreads();
     cf v[C::E], vn[C::E];
     long long tile = blockIdx.x;
-    if (tile < a.num_tiles) stage_read<C, 0, C::STREAM_NT, false, H16>(v, a, tile, t, lds);
+    if (tile < a.num_tiles) stage_read<C, 0, IO>(v, a, tile, t, lds);
     for (; tile < a.num_tiles; tile += gridDim.x) {
       const long long next = tile + gridDim.x;
-      if (next < a.num_tiles) stage_read<C, 0, C::STREAM_NT, false, H16>(vn, a, next, t, lds);      // in flight while this tile is computed and stored
+      if (next < a.num_tiles) stage_read<C, 0, IO>(vn, a, next, t, lds);      // in flight while this tile is computed and stored
       stage_compute_write<C, 0>(v, a, tile, t, lds, tw_lds, lo_lds);
       lines_sync<C>();
       stage_read<C, 1>(v, a, tile, t, lds);
       lines_sync<C>();
-      stage_compute_write<C, 1, C::STREAM_NT, false, false, false, H16>(v, a, tile, t, lds, tw_lds, lo_lds);
+      stage_compute_write<C, 1, IO>(v, a, tile, t, lds, tw_lds, lo_lds);
 #pragma unroll
       for (int e = 0; e < C::E; ++e) v[e] = vn[e];
     }
@@ -389,27 +426,26 @@ __global__ void __launch_bounds__(C::THREADS) fft_lines_kernel(const LineArgs a)
   const bool fs_hoist = C::TWID == TWID_FOURSTEP_IN && ((long long)gridDim.x * C::T) % a.fs_group == 0;
   if constexpr (C::TWID == TWID_FOURSTEP_IN) { if (fs_hoist) fourstep_in_roots<C>(fsw, a, blockIdx.x, t); }
 
-  constexpr bool SNT = C::STREAM_NT;
   for (long long tile = blockIdx.x; tile < a.num_tiles; tile += gridDim.x) {
     cf v[C::E];
-    stage_read<C, 0, SNT, false, H16>(v, a, tile, t, lds);
+    stage_read<C, 0, IO>(v, a, tile, t, lds);
     if constexpr (C::TWID == TWID_FOURSTEP_IN) {
       if (!fs_hoist) fourstep_in_roots<C>(fsw, a, tile, t);
 #pragma unroll
       for (int e = 0; e < C::E; ++e) v[e] = cmul(v[e], fsw[e]);
     }
-    stage_compute_write<C, 0, SNT, false, false, false, H16>(v, a, tile, t, lds, tw_lds, lo_lds);     // (NT only matters where a stage stores to memory)
+    stage_compute_write<C, 0, IO>(v, a, tile, t, lds, tw_lds, lo_lds);     // (NT only matters where a stage stores to memory)
     if constexpr (C::NSTAGES >= 2) {
       lines_sync<C>();
       stage_read<C, 1>(v, a, tile, t, lds);
       lines_sync<C>();
-      stage_compute_write<C, 1, SNT, false, false, false, H16>(v, a, tile, t, lds, tw_lds, lo_lds);
+      stage_compute_write<C, 1, IO>(v, a, tile, t, lds, tw_lds, lo_lds);
     }
     if constexpr (C::NSTAGES == 3) {
       lines_sync<C>();
       stage_read<C, 2>(v, a, tile, t, lds);
       lines_sync<C>();
-      stage_compute_write<C, 2, SNT, false, false, false, H16>(v, a, tile, t, lds, tw_lds, lo_lds);
+      stage_compute_write<C, 2, IO>(v, a, tile, t, lds, tw_lds, lo_lds);
     }
   }
 }
@@ -484,24 +520,13 @@ __global__ void __launch_bounds__(C::THREADS) fft_lines_mapped_kernel(const Line
         for (int q = 0; q < C::N; ++q) {
           if (q < slo || q >= shi) continue;
           cf r = cswap_if<C::SWAP_OUT>(v[q] * a.scale);
-          if (a.fs_lo_mask & 1u) { r = cmul(r, a.tw_hi[q]); if (a.fs_lo_mask & 2u) r = r.yx; }   // Bluestein: chirp on the way out
+          if (a.chirp_flags & LINES_CHIRP) { r = cmul(r, a.tw_hi[q]); if (a.chirp_flags & LINES_CHIRP_SWAP) r = r.yx; }   // Bluestein: chirp on the way out
           if (zero || q < zlo || q >= zhi) r = cf{0.0f, 0.0f};
           a.out[base + (long long)q * so] = r;
         }
       }
     } else {
-      stage_compute_write<C, 0>(v, a, tile, t, lds, tw_lds, nullptr);
-      __syncthreads();
-      stage_read<C, 1>(v, a, tile, t, lds);
-      __syncthreads();
-      stage_compute_write<C, 1, false, true>(v, a, tile, t, lds, tw_lds, nullptr);
-      if constexpr (C::NSTAGES == 3) {
-        __syncthreads();
-        stage_read<C, 2>(v, a, tile, t, lds);
-        __syncthreads();
-        stage_compute_write<C, 2, false, true>(v, a, tile, t, lds, tw_lds, nullptr);
-      }
-      __syncthreads();
+      stages_keep_in_lds<C>(v, a, tile, t, lds, tw_lds);
       // store pass: a thread stays on one line (its box test and base are computed once), lanes run along the side that is
       // contiguous in LDS and, for dense targets, in memory
       int line, u;
@@ -511,7 +536,7 @@ __global__ void __launch_bounds__(C::THREADS) fft_lines_mapped_kernel(const Line
         for (int idx = u; idx < C::N; idx += C::TPL) {
           if (idx < slo || idx >= shi) continue;
           cf r = cswap_if<C::SWAP_OUT>(lds[lds_index<C>(line, idx)] * a.scale);
-          if (a.fs_lo_mask & 1u) { r = cmul(r, a.tw_hi[idx]); if (a.fs_lo_mask & 2u) r = r.yx; }   // Bluestein: chirp on the way out
+          if (a.chirp_flags & LINES_CHIRP) { r = cmul(r, a.tw_hi[idx]); if (a.chirp_flags & LINES_CHIRP_SWAP) r = r.yx; }   // Bluestein: chirp on the way out
           if (zero || idx < zlo || idx >= zhi) r = cf{0.0f, 0.0f};
           a.out[base + (long long)idx * so] = r;
         }
@@ -527,7 +552,7 @@ __global__ void __launch_bounds__(C::THREADS) fft_lines_mapped_kernel(const Line
 // 4 B read + 4 B written per real point where the two-launch route moves 12.  a.out lines have H+1 bins (a.out_outer_stride);
 // roots e^{-2 pi i k/N} = tw_hi[k >> fs_shift] * tw_lo[k & fs_lo_mask].
 //
-// TRIG (r02; dct_fft.js DCT-II / DST-II): the same kernel as a whole DCT-II (a.real_mode == 5) or DST-II (6) of real
+// TRIG (r02; dct_fft.js DCT-II / DST-II): the same kernel as a whole DCT-II (a.real_mode == LM_DCT2) or DST-II (LM_DST2) of real
 // lines of length N = 2H — Makhoul's permutation v[n] = x[2n], v[N-1-n] = x[2n+1] (DST-II: odd samples negated) is applied while
 // the line is staged into the LDS line buffer (pair loads from memory, float stores into LDS), the half-length FFT and the split
 // give V = r2c(v), and each bin leaves as two real outputs y[k] = Re t, y[N-k] = -Im t, t = e^{-i pi k/2N} V[k] (DST-II: the
@@ -566,7 +591,7 @@ __global__ void __launch_bounds__(C::THREADS, C::THREADS == 256 && C::T == 1 && 
     __syncthreads();
   }
   constexpr int H = C::N, PER = H / 2 + 1, NREAL = 2 * H;
-  const bool sine = TRIG && a.real_mode == 6;
+  const bool sine = TRIG && a.real_mode == LM_DST2;
   for (long long tile = blockIdx.x; tile < a.num_tiles; tile += gridDim.x) {
     cf v[C::E];
     if constexpr (TRIG) {
@@ -617,20 +642,9 @@ __global__ void __launch_bounds__(C::THREADS, C::THREADS == 256 && C::T == 1 && 
         }
       }
     } else {
-      stage_read<C, 0, false, false, H16>(v, a, tile, t, lds);
+      stage_read<C, 0, H16 ? SO_H16 : 0>(v, a, tile, t, lds);
     }
-    stage_compute_write<C, 0>(v, a, tile, t, lds, tw_lds, nullptr);
-    __syncthreads();
-    stage_read<C, 1>(v, a, tile, t, lds);
-    __syncthreads();
-    stage_compute_write<C, 1, false, true>(v, a, tile, t, lds, tw_lds, nullptr);
-    if constexpr (C::NSTAGES == 3) {
-      __syncthreads();
-      stage_read<C, 2>(v, a, tile, t, lds);
-      __syncthreads();
-      stage_compute_write<C, 2, false, true>(v, a, tile, t, lds, tw_lds, nullptr);
-    }
-    __syncthreads();
+    stages_keep_in_lds<C>(v, a, tile, t, lds, tw_lds);
     const long long G0 = tile * C::T;
     const int live = (int)((a.num_lines - G0) < (long long)C::T ? (a.num_lines - G0) : (long long)C::T);
     // MAPPED: a thread stays on one line (its box test and base are computed once); otherwise the pairs are dealt out flat
@@ -808,7 +822,7 @@ __global__ void __launch_bounds__(C::THREADS, C::THREADS == 256 && C::T == 1 && 
 }
 
 // fftconv, first half (src/kernels/fft_conv.js:3-66 pointwise product): forward FFT of complex lines whose
-// outputs are multiplied by the kernel spectrum a.tw_lo[k] (its conjugate when a.fs_shift != 0: correlation) as they are stored —
+// outputs are multiplied by the kernel spectrum a.tw_lo[k] (its conjugate when a.mul_conj != 0: correlation) as they are stored —
 // the separate pointwise pass (8 B read + 8 B written per point) disappears.  One spectrum for every line.
 // MAPPED (r02): the data lines are read through a.imap (strided lanes, the zero-padded embed of the linear modes, zeroPad.read) —
 // fft_lines_mapped_kernel's first-stage loads — so that no gather / embed pass runs ahead of the product.
@@ -836,7 +850,7 @@ __global__ void __launch_bounds__(C::THREADS) fft_lines_mul_kernel(const LineArg
 #pragma unroll
       for (int q = 0; q < IL::R; ++q) {
         cf h = a.tw_lo[u + b * C::TPL + q * IL::NSP];      // last stage: output index = j + q * Ns_prev, j = u + b * TPL
-        if (a.fs_shift) h.y = -h.y;
+        if (a.mul_conj) h.y = -h.y;
         hk[b * IL::R + q] = h;
       }
     }
@@ -860,7 +874,7 @@ __global__ void __launch_bounds__(C::THREADS) fft_lines_mul_kernel(const LineArg
           if (ok && idx >= lo && idx < hi) {
             x = a.in[base + (long long)idx * sa];
             // Bluestein (plan.cpp emit_bluestein): the chirp a.tw_hi[n] rides the load (bit 1: the swap that turns the route into an inverse)
-            if (a.fs_lo_mask & 1u) { if (a.fs_lo_mask & 2u) x = x.yx; x = cmul(x, a.tw_hi[idx]); }
+            if (a.chirp_flags & LINES_CHIRP) { if (a.chirp_flags & LINES_CHIRP_SWAP) x = x.yx; x = cmul(x, a.tw_hi[idx]); }
           }
           v[b * I0::R + q] = x;
         }
@@ -873,13 +887,13 @@ __global__ void __launch_bounds__(C::THREADS) fft_lines_mul_kernel(const LineArg
     stage_read<C, 1>(v, a, tile, t, lds);
     lines_sync<C>();
     if constexpr (C::NSTAGES == 2) {
-      stage_compute_write<C, 1, false, false, true>(v, a, tile, t, lds, tw_lds, hk);
+      stage_compute_write<C, 1, SO_MUL>(v, a, tile, t, lds, tw_lds, hk);
     } else {
       stage_compute_write<C, 1>(v, a, tile, t, lds, tw_lds, nullptr);
       lines_sync<C>();
       stage_read<C, 2>(v, a, tile, t, lds);
       lines_sync<C>();
-      stage_compute_write<C, 2, false, false, true>(v, a, tile, t, lds, tw_lds, hk);
+      stage_compute_write<C, 2, SO_MUL>(v, a, tile, t, lds, tw_lds, hk);
     }
   }
 }
@@ -917,8 +931,8 @@ __global__ void __launch_bounds__(C::THREADS, C::THREADS == 256 && C::T == 1 ? 2
   static_assert((H / 2) % C::TPL == 0 && NP % PB == 0, "the pairs of a line are dealt out in whole strides");
   using I0 = StageInfo<C, 0>;
   const int pl = t / C::TPL, pu = t % C::TPL;   // pair step and store sweep: a thread stays on one line
-  const int split = a.v_in_lo, padD = a.v_in_hi;
-  const bool conj = a.v_out_lo != 0;
+  const int split = a.rconv_split, padD = a.rconv_padD;
+  const bool conj = a.conj != 0;
   const float* xin = reinterpret_cast<const float*>(a.in);
   float* y = reinterpret_cast<float*>(a.out);
   for (long long tile = blockIdx.x; tile < a.num_tiles; tile += gridDim.x) {
@@ -979,12 +993,12 @@ __global__ void __launch_bounds__(C::THREADS, C::THREADS == 256 && C::T == 1 ? 2
     __syncthreads();
     stage_read<C, 1>(v, a, tile, t, lds);
     __syncthreads();
-    stage_compute_write<C, 1, false, true>(v, a, tile, t, lds, tw_lds, nullptr);
+    stage_compute_write<C, 1, SO_KEEP_IN_LDS>(v, a, tile, t, lds, tw_lds, nullptr);
     if constexpr (C::NSTAGES == 3) {
       __syncthreads();
       stage_read<C, 2>(v, a, tile, t, lds);
       __syncthreads();
-      stage_compute_write<C, 2, false, true>(v, a, tile, t, lds, tw_lds, nullptr);
+      stage_compute_write<C, 2, SO_KEEP_IN_LDS>(v, a, tile, t, lds, tw_lds, nullptr);
     }
     __syncthreads();
     {
@@ -1048,12 +1062,12 @@ __global__ void __launch_bounds__(C::THREADS, C::THREADS == 256 && C::T == 1 ? 2
     __syncthreads();
     stage_read<C, 1>(v, a, tile, t, lds);
     __syncthreads();
-    stage_compute_write<C, 1, false, true>(v, a, tile, t, lds, tw_lds, nullptr);
+    stage_compute_write<C, 1, SO_KEEP_IN_LDS>(v, a, tile, t, lds, tw_lds, nullptr);
     if constexpr (C::NSTAGES == 3) {
       __syncthreads();
       stage_read<C, 2>(v, a, tile, t, lds);
       __syncthreads();
-      stage_compute_write<C, 2, false, true>(v, a, tile, t, lds, tw_lds, nullptr);
+      stage_compute_write<C, 2, SO_KEEP_IN_LDS>(v, a, tile, t, lds, tw_lds, nullptr);
     }
     __syncthreads();
     {
@@ -1115,7 +1129,7 @@ __global__ void __launch_bounds__(C::THREADS, C::THREADS == 256 && C::T == 1 ? 2
   static_assert((H / 2) % C::TPL == 0 && NP % PB == 0, "the pairs of a line are dealt out in whole strides");
   using I0 = StageInfo<C, 0>;
   const int pl = t / C::TPL, pu = t % C::TPL;   // pair step and store sweep: a thread stays on one line
-  const bool conj = a.v_out_lo != 0;
+  const bool conj = a.conj != 0;
   const float* xin = reinterpret_cast<const float*>(a.in);
   float* y = reinterpret_cast<float*>(a.out);
   for (long long tile = blockIdx.x; tile < a.num_tiles; tile += gridDim.x) {
@@ -1179,12 +1193,12 @@ __global__ void __launch_bounds__(C::THREADS, C::THREADS == 256 && C::T == 1 ? 2
     __syncthreads();
     stage_read<C, 1>(v, a, tile, t, lds);
     __syncthreads();
-    stage_compute_write<C, 1, false, true>(v, a, tile, t, lds, tw_lds, nullptr);
+    stage_compute_write<C, 1, SO_KEEP_IN_LDS>(v, a, tile, t, lds, tw_lds, nullptr);
     if constexpr (C::NSTAGES == 3) {
       __syncthreads();
       stage_read<C, 2>(v, a, tile, t, lds);
       __syncthreads();
-      stage_compute_write<C, 2, false, true>(v, a, tile, t, lds, tw_lds, nullptr);
+      stage_compute_write<C, 2, SO_KEEP_IN_LDS>(v, a, tile, t, lds, tw_lds, nullptr);
     }
     __syncthreads();
     {
@@ -1248,12 +1262,12 @@ __global__ void __launch_bounds__(C::THREADS, C::THREADS == 256 && C::T == 1 ? 2
     __syncthreads();
     stage_read<C, 1>(v, a, tile, t, lds);
     __syncthreads();
-    stage_compute_write<C, 1, false, true>(v, a, tile, t, lds, tw_lds, nullptr);
+    stage_compute_write<C, 1, SO_KEEP_IN_LDS>(v, a, tile, t, lds, tw_lds, nullptr);
     if constexpr (C::NSTAGES == 3) {
       __syncthreads();
       stage_read<C, 2>(v, a, tile, t, lds);
       __syncthreads();
-      stage_compute_write<C, 2, false, true>(v, a, tile, t, lds, tw_lds, nullptr);
+      stage_compute_write<C, 2, SO_KEEP_IN_LDS>(v, a, tile, t, lds, tw_lds, nullptr);
     }
     __syncthreads();
     {
@@ -1289,7 +1303,7 @@ __global__ void __launch_bounds__(C::THREADS, C::THREADS == 256 && C::T == 1 ? 2
 // in the first-stage loads for single-stage lines), and the unnormalised inverse of length H then lands x[2n] + i x[2n+1], i.e.
 // the real line, through the ordinary last-stage store.  C is the INVERSE ROW configuration (the swap trick of the c2c kernels).
 //
-// TRIG (r02; DCT-III / DST-III, the inverses of the kernel above; a.real_mode == 7 / 8): the bins V[k] = (X[k] - i X[N-k]) e^{+i pi k/2N}/2
+// TRIG (r02; DCT-III / DST-III, the inverses of the kernel above; a.real_mode == LM_DCT3 / LM_DST3): the bins V[k] = (X[k] - i X[N-k]) e^{+i pi k/2N}/2
 // are formed from the REAL input line while the pre-split reads them (DST-III: the line reversed), and the finished real line is
 // un-permuted on its way out of the LDS line buffer: y[2n] = v[n], y[2n+1] = v[N-1-n] (DST-III: odd samples negated).
 //
@@ -1342,7 +1356,7 @@ __global__ void __launch_bounds__(C::THREADS, C::THREADS == 256 && C::T == 1 ? M
   }
   constexpr int H = C::N;
   [[maybe_unused]] constexpr int NREAL = 2 * H;
-  [[maybe_unused]] const bool sine = TRIG && a.real_mode == 8;
+  [[maybe_unused]] const bool sine = TRIG && a.real_mode == LM_DST3;
   using I0 = StageInfo<C, 0>;
   // raw copy of the packed lines (2048 <= H <= 8192; see the head of the tile loop): TPL threads per line, lane ru of line rl takes bins ru + TPL i
   constexpr bool RAW = !TRIG && !MAPPED && MI355_C2R_RAW_COPY && C::NSTAGES >= 2 && H >= MI355_C2R_RAW_COPY_H && H <= MI355_C2R_RAW_COPY_HMAX;
@@ -1582,18 +1596,19 @@ __global__ void __launch_bounds__(C::THREADS, C::THREADS == 256 && C::T == 1 ? M
         }
       }
     }
-    stage_compute_write<C, 0, false, false, false, false, H16>(v, a, tile, t, lds, tw_lds, nullptr);
+    constexpr unsigned IO = H16 ? SO_H16 : 0, KEEP = TRIG || MAPPED ? SO_KEEP_IN_LDS : 0;   // the last stage's store
+    stage_compute_write<C, 0, IO>(v, a, tile, t, lds, tw_lds, nullptr);
     if constexpr (C::NSTAGES >= 2) {
       lines_sync<C>();
       stage_read<C, 1>(v, a, tile, t, lds);
       lines_sync<C>();
-      stage_compute_write<C, 1, false, (TRIG || MAPPED) && C::NSTAGES == 2, false, false, H16>(v, a, tile, t, lds, tw_lds, nullptr);
+      stage_compute_write<C, 1, (C::NSTAGES == 2 ? KEEP : 0) | IO>(v, a, tile, t, lds, tw_lds, nullptr);
     }
     if constexpr (C::NSTAGES == 3) {
       lines_sync<C>();
       stage_read<C, 2>(v, a, tile, t, lds);
       lines_sync<C>();
-      stage_compute_write<C, 2, false, TRIG || MAPPED, false, false, H16>(v, a, tile, t, lds, tw_lds, nullptr);
+      stage_compute_write<C, 2, KEEP | IO>(v, a, tile, t, lds, tw_lds, nullptr);
     }
     if constexpr (MAPPED) {
       // the finished line sits in LDS as swapped pairs (x[2n+1], x[2n]); a thread stays on one line and walks it through omap

@@ -266,7 +266,7 @@ __global__ void __launch_bounds__(RtCfg::THREADS) fft_xcd_rt_kernel(const XcdFus
       for (unsigned tile = rank; tile < N2 / 16; tile += gsize) {
         aa.in = x; aa.out = W;
         cf v[CA::E];
-        stage_read<CA, 0, RT_NT_IN>(v, aa, tile, t, lds);
+        stage_read<CA, 0, RT_NT_IN ? SO_NT : 0>(v, aa, tile, t, lds);
         stage_compute_write<CA, 0>(v, aa, tile, t, lds, tw_a, nullptr);
         __syncthreads();
         stage_read<CA, 1>(v, aa, tile, t, lds);
@@ -342,13 +342,8 @@ __global__ void __launch_bounds__(RtCfg::THREADS) fft_xcd_rt_r2c_kernel(const Xc
       aa.in = x; aa.out = W;
       for (unsigned tile = rank; tile < (N2 / 2) / 16; tile += gsize) {
         cf v[CA::E];
-        stage_read<CA, 0, RT_NT_IN>(v, aa, tile, t, xb);
-        stage_compute_write<CA, 0>(v, aa, tile, t, xb, tw_a, nullptr);
-        __syncthreads();
-        stage_read<CA, 1>(v, aa, tile, t, xb);
-        __syncthreads();
-        stage_compute_write<CA, 1, false, true>(v, aa, tile, t, xb, tw_a, nullptr);
-        __syncthreads();
+        stage_read<CA, 0, RT_NT_IN ? SO_NT : 0>(v, aa, tile, t, xb);
+        stages_keep_in_lds<CA>(v, aa, tile, t, xb, tw_a);
         cf* const wt = W + tile * 32u;
         for (int p = t; p < (int)ROWS * 16; p += RtCfg::THREADS) {
           const int k1 = p >> 4, c = p & 15;
@@ -501,12 +496,7 @@ __global__ void __launch_bounds__(RtCfg::THREADS) fft_xcd_rt_c2r_kernel(const Xc
             else v[q] = X[lo - step];
           }
         }
-        stage_compute_write<CA, 0>(v, aa, tile, t, xb, tw_a, nullptr);
-        __syncthreads();
-        stage_read<CA, 1>(v, aa, tile, t, xb);
-        __syncthreads();
-        stage_compute_write<CA, 1, false, true>(v, aa, tile, t, xb, tw_a, nullptr);      // finished columns stay in LDS: [k1][16]
-        __syncthreads();
+        stages_keep_in_lds<CA>(v, aa, tile, t, xb, tw_a);      // finished columns stay in LDS: [k1][16]
         // adjacent results k1 = 2i, 2i + 1 of column n2: four-step roots, packed as a + i b at n2 and conj(a) + i conj(b) at N2 - n2
         for (int p = t; p < (N1 / 2) * 16; p += RtCfg::THREADS) {
           const int i = p >> 4, c = p & 15;

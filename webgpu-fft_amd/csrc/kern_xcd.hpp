@@ -293,6 +293,7 @@ __global__ void __launch_bounds__(CA::THREADS) fft_xcd_fused_kernel(const XcdFus
   // GPoints/s at N = 2^20.)
   const bool two_slots = f.slots != 1u && !f.solo;
   cf* const W0 = f.wslots + (size_t)((two_slots ? 2u : 1u) * gslot) * (size_t)f.N;
+  constexpr unsigned W_ST = MI355_XCD_W_NT_ST != 0 ? SO_NT : 0, OUT_NT = PairOf<CB>::NT ? SO_NT : 0;   // stores to the workspace slot / of the output
   unsigned k = 0;
   for (long long tr = gidx; tr < f.num_transforms; tr += groups, ++k) {
     cf* const W = W0 + (size_t)(two_slots ? (k & 1u) : 0u) * (size_t)f.N;
@@ -303,19 +304,19 @@ __global__ void __launch_bounds__(CA::THREADS) fft_xcd_fused_kernel(const XcdFus
       if (tile - (i % PairOf<CA>::C) >= aa.num_tiles) break;
       if (tile >= aa.num_tiles) continue;
       cf v[CA::E];
-      stage_read<CA, 0, PairOf<CA>::NT && !VIEW, VIEW>(v, aa, tile, t, lds);       // x streams past the L2
+      stage_read<CA, 0, (PairOf<CA>::NT && !VIEW ? SO_NT : 0) | (VIEW ? SO_VIEW : 0)>(v, aa, tile, t, lds);       // x streams past the L2
       stage_compute_write<CA, 0>(v, aa, tile, t, lds, tw_a, nullptr);
       if constexpr (CA::NSTAGES >= 2) {
         __syncthreads();
         stage_read<CA, 1>(v, aa, tile, t, lds);
         __syncthreads();
-        stage_compute_write<CA, 1, MI355_XCD_W_NT_ST != 0>(v, aa, tile, t, lds, tw_a, nullptr);
+        stage_compute_write<CA, 1, W_ST>(v, aa, tile, t, lds, tw_a, nullptr);
       }
       if constexpr (CA::NSTAGES == 3) {
         __syncthreads();
         stage_read<CA, 2>(v, aa, tile, t, lds);
         __syncthreads();
-        stage_compute_write<CA, 2, MI355_XCD_W_NT_ST != 0>(v, aa, tile, t, lds, tw_a, nullptr);
+        stage_compute_write<CA, 2, W_ST>(v, aa, tile, t, lds, tw_a, nullptr);
       }
       __syncthreads();   // LDS is re-used by the next tile
     }
@@ -331,23 +332,23 @@ __global__ void __launch_bounds__(CA::THREADS) fft_xcd_fused_kernel(const XcdFus
       if (tile - (i % PairOf<CB>::C) >= ab.num_tiles) break;
       if (tile >= ab.num_tiles) continue;
       cf v[CB::E];
-      stage_read<CB, 0, MI355_XCD_W_NT_LD != 0>(v, ab, tile, t, lds);
+      stage_read<CB, 0, MI355_XCD_W_NT_LD != 0 ? SO_NT : 0>(v, ab, tile, t, lds);
       if constexpr (!TWO_D) {
         int line, u; thread_map<CB, 0>(t, line, u);
         fourstep_apply_chain<CB>(v, f, (unsigned)(tile * CB::T + line), u);
       }
-      stage_compute_write<CB, 0, PairOf<CB>::NT>(v, ab, tile, t, lds, tw_b, nullptr);
+      stage_compute_write<CB, 0, OUT_NT>(v, ab, tile, t, lds, tw_b, nullptr);
       if constexpr (CB::NSTAGES >= 2) {
         __syncthreads();
         stage_read<CB, 1>(v, ab, tile, t, lds);
         __syncthreads();
-        stage_compute_write<CB, 1, PairOf<CB>::NT, false, false, VIEW && CB::NSTAGES == 2>(v, ab, tile, t, lds, tw_b, nullptr);   // output streams past the L2
+        stage_compute_write<CB, 1, OUT_NT | (VIEW && CB::NSTAGES == 2 ? SO_VIEW : 0)>(v, ab, tile, t, lds, tw_b, nullptr);   // output streams past the L2
       }
       if constexpr (CB::NSTAGES == 3) {
         __syncthreads();
         stage_read<CB, 2>(v, ab, tile, t, lds);
         __syncthreads();
-        stage_compute_write<CB, 2, PairOf<CB>::NT, false, false, VIEW>(v, ab, tile, t, lds, tw_b, nullptr);
+        stage_compute_write<CB, 2, OUT_NT | (VIEW ? SO_VIEW : 0)>(v, ab, tile, t, lds, tw_b, nullptr);
       }
       __syncthreads();
     }

@@ -71,19 +71,8 @@ __global__ void __launch_bounds__(CA::THREADS) fft_xcd_r2c_kernel(const XcdFused
       if (tile - (i % PairOf<CA>::C) >= aa.num_tiles) break;
       if (tile >= aa.num_tiles) continue;
       cf v[CA::E];
-      stage_read<CA, 0, PairOf<CA, false>::NT>(v, aa, tile, t, lds);
-      stage_compute_write<CA, 0>(v, aa, tile, t, lds, tw_a, nullptr);
-      __syncthreads();
-      stage_read<CA, 1>(v, aa, tile, t, lds);
-      __syncthreads();
-      stage_compute_write<CA, 1, false, true>(v, aa, tile, t, lds, tw_a, nullptr);
-      if constexpr (CA::NSTAGES == 3) {
-        __syncthreads();
-        stage_read<CA, 2>(v, aa, tile, t, lds);
-        __syncthreads();
-        stage_compute_write<CA, 2, false, true>(v, aa, tile, t, lds, tw_a, nullptr);
-      }
-      __syncthreads();
+      stage_read<CA, 0, PairOf<CA, false>::NT ? SO_NT : 0>(v, aa, tile, t, lds);
+      stages_keep_in_lds<CA>(v, aa, tile, t, lds, tw_a);
       // Z[k1][c] sits at lds[k1*T + c]; one lane per (k1, c) writes the two separated values as one 16-byte store:
       // T consecutive lanes cover 2T consecutive complex columns of row k1
       cf* const wt = W + tile * (2 * CA::T);
@@ -306,16 +295,17 @@ __global__ void __launch_bounds__(CA::THREADS) fft_xcd_c2r_kernel(const XcdFused
           MI_SCHED_FENCE();
         }
       }
-      stage_compute_write<CB, 0, PairOf<CB, false>::NT>(v, ab, tile, t, lds, tw_b, nullptr);
+      constexpr unsigned OUT_NT = PairOf<CB, false>::NT ? SO_NT : 0;
+      stage_compute_write<CB, 0, OUT_NT>(v, ab, tile, t, lds, tw_b, nullptr);
       __syncthreads();
       stage_read<CB, 1>(v, ab, tile, t, lds);
       __syncthreads();
-      stage_compute_write<CB, 1, PairOf<CB, false>::NT>(v, ab, tile, t, lds, tw_b, nullptr);
+      stage_compute_write<CB, 1, OUT_NT>(v, ab, tile, t, lds, tw_b, nullptr);
       if constexpr (CB::NSTAGES == 3) {
         __syncthreads();
         stage_read<CB, 2>(v, ab, tile, t, lds);
         __syncthreads();
-        stage_compute_write<CB, 2, PairOf<CB, false>::NT>(v, ab, tile, t, lds, tw_b, nullptr);
+        stage_compute_write<CB, 2, OUT_NT>(v, ab, tile, t, lds, tw_b, nullptr);
       }
       __syncthreads();
     }

@@ -258,7 +258,7 @@ struct Builder {
   unsigned oneshot_grid(int64_t items) const { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(items, MAX_BLOCKS)); }
   Step& push(StepKind k) { ir.steps.emplace_back(); ir.steps.back().kind = k; return ir.steps.back(); }
   // clears `scalars` 32-bit words at ptr
-  Step& zero(PtrRef ptr, int64_t scalars) { Step& z = push(ST_ZERO); z.p[0] = ptr; z.i[0] = scalars; z.grid = generic_grid(scalars); return z; }
+  Step& zero(PtrRef ptr, int64_t scalars) { Step& z = push(ST_ZERO); z.p[P_DATA] = ptr; z.i[S_COUNT] = scalars; z.grid = generic_grid(scalars); return z; }
 
   // stage-2 roots of the register-tile passes (kern_regtile.hpp): e^{-2 pi i q2 j2/2048}, rows q2 = 1..31, j2 = 0..63 fastest
   PtrRef regtile_table() {
@@ -281,13 +281,13 @@ struct Builder {
     return add_table(t);
   }
 
-  // e^{-2 pi i k/M} for k < count as HI[k >> 10] * LO[k & 1023]: tables into slots p[2] (LO), p[3] (HI), i[3] shift, i[4] mask
+  // e^{-2 pi i k/M} for k < count as HI[k >> 10] * LO[k & 1023]: tables into slots p[RSP_TW_LO], p[RSP_TW_HI], i[RS_SHIFT], i[RS_MASK]
   void split_roots(Step& st, int64_t M, int64_t count) {
     std::vector<float2h> lo(1024), hi((size_t)((count + 1023) >> 10));
     for (int64_t l = 0; l < 1024; ++l) lo[(size_t)l] = root_of_unity(l, M);
     for (size_t h = 0; h < hi.size(); ++h) hi[h] = root_of_unity((int64_t)h << 10, M);
     const PtrRef plo = add_table(lo), phi = add_table(hi);   // add_table may reallocate ir.steps? no: tables live in ir.table
-    st.p[2] = plo; st.p[3] = phi; st.i[3] = 10; st.i[4] = 1023;
+    st.p[RSP_TW_LO] = plo; st.p[RSP_TW_HI] = phi; st.i[RS_SHIFT] = 10; st.i[RS_MASK] = 1023;
   }
 
   // the real fftconv line kernels' roots e^{-2 pi i k/P} = HI[k >> 10] LO[k & 1023], k <= P/2: the HI factors directly behind the 1024 LO factors
@@ -313,6 +313,20 @@ struct Builder {
     if (tpw == 0 && plain_c2c && !m.in_col && !m.out_col && m.twid == 0 && m.N <= 1024) tpw = 1;   // (the r2c / c2r / product variants measured better resident)
     if (tpw > 0) return (unsigned)std::max<int64_t>(1, std::min<int64_t>((tiles + tpw - 1) / tpw, MAX_BLOCKS));
     return (unsigned)std::max<int64_t>(1, std::min<int64_t>(tiles, per_cu * opt.compute_units));
+  }
+  // One ST_LINES launch of kernel `m` over `lines` lines with its own stage tables: each side as (S, outer stride), LM_C2C, dense.  `oneshot`:
+  // a plain c2c launch that may take lines_grid's one-shot grid.  `tiles` where it is not lines / T rounded up (exact column tiles, per-group
+  // tiles on COL_RAGGED).  The caller adds the slots of its mode.
+  struct LineSide { int64_t S, outer; };
+  Step& push_lines(const LineKernelMeta& m, PtrRef src, PtrRef dst, int64_t lines, LineSide in, LineSide out, float scale, bool oneshot = false, int64_t tiles = -1) {
+    Step& st = push(ST_LINES);
+    st.variant = m.id;
+    st.p[LP_IN] = src; st.p[LP_OUT] = dst; st.p[LP_TW] = line_tables(m);
+    if (tiles < 0) tiles = (lines + m.T - 1) / m.T;
+    st.i[LS_TILES] = tiles; st.i[LS_LINES] = lines; st.i[LS_IN_S] = in.S; st.i[LS_IN_OUTER] = in.outer; st.i[LS_OUT_S] = out.S; st.i[LS_OUT_OUTER] = out.outer;
+    st.f[F_SCALE] = scale;
+    st.grid = lines_grid(m, tiles, oneshot);
+    return st;
   }
 
   // batched 1-D FFT along an axis of a dense array: `lines` = S*outer lines of length N, element stride S.
@@ -377,15 +391,15 @@ struct Builder {
     x.hi = add_table(hi);
   }
   // the ST_ZERO of the control block (shared mode) and the launch with the fields every fused emitter fills (dispatch.hpp
-  // ST_XCD_FUSED); the caller adds the scale, pitches other than N (i[9] in, i[10] out) and its own fields
+  // ST_XCD_FUSED); the caller adds the scale, pitches other than N (i[XS_IN_PITCH], i[XS_OUT_PITCH]) and its own fields
   Step& push_xcd(StepKind kind, int variant, const XcdLaunch& x, PtrRef src, PtrRef dst, int64_t transforms, int64_t N) {
     if (!x.solo) zero(x.ctl, XCD_CTL_ZERO_FLOATS).grid = 1;   // (8 KiB: one workgroup)
     Step& st = push(kind);
     st.variant = variant;
-    st.p[0] = src; st.p[1] = dst; st.p[2] = x.wslots; st.p[3] = x.ctl; st.p[4] = PtrRef(BUF_TABLE, 0);
-    st.i[0] = transforms; st.i[1] = N; st.i[2] = x.shift; st.i[3] = ((int64_t)1 << x.shift) - 1;
-    st.i[4] = x.ta.off; st.i[5] = x.tb.off; st.i[6] = x.lo.off; st.i[7] = x.hi.off; st.i[8] = x.split; st.i[9] = N; st.i[10] = N;
-    st.i[11] = x.slots; st.i[12] = x.solo ? 1 : 0; st.i[13] = opt.xcd_spin_limit;
+    st.p[XP_IN] = src; st.p[XP_OUT] = dst; st.p[XP_WSLOTS] = x.wslots; st.p[XP_CTL] = x.ctl; st.p[XP_TABLE] = PtrRef(BUF_TABLE, 0);
+    st.i[XS_TRANSFORMS] = transforms; st.i[XS_N] = N; st.i[XS_FS_SHIFT] = x.shift; st.i[XS_FS_LO_MASK] = ((int64_t)1 << x.shift) - 1;
+    st.i[XS_TW_A_OFF] = x.ta.off; st.i[XS_TW_B_OFF] = x.tb.off; st.i[XS_TW_LO_OFF] = x.lo.off; st.i[XS_TW_HI_OFF] = x.hi.off; st.i[XS_SPLIT] = x.split; st.i[XS_IN_PITCH] = N; st.i[XS_OUT_PITCH] = N;
+    st.i[XS_SLOTS] = x.slots; st.i[XS_SOLO] = x.solo ? 1 : 0; st.i[XS_SPIN_LIMIT] = opt.xcd_spin_limit;
     st.grid = (unsigned)x.grid;
     return st;
   }
@@ -416,7 +430,7 @@ struct Builder {
     x.tb = line_tables(mb);
     x.lo = x.hi = add_table(std::vector<float2h>(1, float2h{1, 0}));   // no four-step roots (shift 0)
     Step& st = push_xcd(ST_XCD_FUSED, xm->id, x, src, dst, planes, N);
-    st.f[0] = scale;
+    st.f[F_SCALE] = scale;
     ir.route += std::string(solo ? "xcd-2d-solo[" : "xcd-2d[") + std::to_string(N0) + "x" + std::to_string(N1) + "] ";
     return true;
   }
@@ -443,8 +457,8 @@ struct Builder {
     x.ta = rt && xm->N1 == 2048 ? x.tb : line_tables(ma);
     xcd_roots(x, N);
     Step& st = push_xcd(ST_XCD_FUSED, xm->id, x, src, dst, lines, N);
-    st.i[9] = c2r ? N / 2 + 1 : N / 2; st.i[10] = c2r ? N / 2 : N / 2 + 1;        // pitches in complex elements
-    st.f[0] = scale;
+    st.i[XS_IN_PITCH] = c2r ? N / 2 + 1 : N / 2; st.i[XS_OUT_PITCH] = c2r ? N / 2 : N / 2 + 1;        // pitches in complex elements
+    st.f[F_SCALE] = scale;
     ir.route += std::string(c2r ? "xcd-c2r" : "xcd-r2c") + (solo ? "-solo" : rt ? "-rt" : "") + "[N=" + std::to_string(xm->N1) + "x" + std::to_string(xm->N2) + "] ";
     return true;
   }
@@ -452,7 +466,7 @@ struct Builder {
   // r2c of dense real lines of length N = 2H, H a power of two in 64..max_line: the ROW line kernel of length H with the split
   // fused behind its last stage (one launch instead of FFT + r2c_post_kernel)
   // (c2r: the mirror — the pre-split rides the first-stage loads of the INVERSE line kernel, any power-of-two half length >= 2)
-  // trig = 5 / 6: the same launch as a whole DCT-II / DST-II of the real lines (kern_lines.hpp fft_lines_r2c_kernel<C, TRIG>)
+  // trig = LM_DCT2 / LM_DST2 (c2r: LM_DCT3 / LM_DST3; 0: none): the same launch as a whole DCT-II / DST-II of the real lines (kern_lines.hpp fft_lines_r2c_kernel<C, TRIG>)
   // im / om (optional, both or none): the launch reads its input side through im and writes through om (fft_lines_r2c_kernel /
   // fft_lines_c2r_kernel <.., MAPPED>; the real side's map counts floats, the packed side's complex bins)
   const LineKernelMeta* lines_r2c_kernel(int64_t N, bool c2r, bool mapped) const {
@@ -478,20 +492,16 @@ struct Builder {
     for (size_t h = 0; h < hi.size(); ++h) hi[h] = root_of_unity((int64_t)h << 10, N);
     // trig: the DCT phases e^{-i pi m/2N} = e^{-2 pi i m/4N}, m = 0..N/2, f64-built, directly behind the 1024 LO roots (one table)
     if (trig) for (int64_t mm = 0; mm <= H; ++mm) lo.push_back(root_of_unity(mm, 4 * N));
-    Step& st = push(ST_LINES);
-    st.variant = m->id;
-    st.p[0] = src; st.p[1] = dst; st.p[2] = line_tables(*m); st.p[3] = add_table(lo); st.p[4] = add_table(hi);
-    const int64_t tiles = (lines + m->T - 1) / m->T;
-    st.i[0] = tiles; st.i[1] = lines; st.i[2] = 1; st.i[3] = c2r ? H + 1 : H; st.i[4] = 1; st.i[5] = c2r ? H : H + 1; st.i[6] = 10; st.i[7] = 1023;
-    st.i[9] = trig ? trig : (c2r ? 2 : 1);
-    st.f[0] = scale;
-    st.grid = lines_grid(*m, tiles);
+    Step& st = push_lines(*m, src, dst, lines, {1, c2r ? H + 1 : H}, {1, c2r ? H : H + 1}, scale);
+    st.p[LP_TW_LO] = add_table(lo); st.p[LP_TW_HI] = add_table(hi);
+    st.i[LS_FS_SHIFT] = 10; st.i[LS_FS_LO_MASK] = 1023;
+    st.i[LS_MODE] = trig ? trig : (c2r ? LM_C2R : LM_R2C);
     if (im) {
-      st.i[10] = 1; st.imap = *im; st.omap = *om; st.imap.ax = st.omap.ax = 0;
+      st.i[LS_MAPPED] = 1; st.imap = *im; st.omap = *om; st.imap.ax = st.omap.ax = 0;
       ir.route += std::string(c2r ? "lines-c2r-mapped[N=" : "lines-r2c-mapped[N=") + std::to_string(N) + "] ";
       return true;
     }
-    ir.route += std::string(trig == 5 ? "lines-dct2[N=" : trig == 6 ? "lines-dst2[N=" : trig == 7 ? "lines-dct3[N=" : trig == 8 ? "lines-dst3[N=" : c2r ? "lines-c2r[N=" : "lines-r2c[N=") + std::to_string(N) + "] ";
+    ir.route += std::string(trig == LM_DCT2 ? "lines-dct2[N=" : trig == LM_DST2 ? "lines-dst2[N=" : trig == LM_DCT3 ? "lines-dct3[N=" : trig == LM_DST3 ? "lines-dst3[N=" : c2r ? "lines-c2r[N=" : "lines-r2c[N=") + std::to_string(N) + "] ";
     return true;
   }
 
@@ -509,9 +519,9 @@ struct Builder {
     int rc = emit_axis(in, z, H, 1, lines, false, 1.0f, err);
     if (rc) return rc;
     Step& st = push(ST_R2C_POST);
-    st.p[0] = z; st.p[1] = out;
+    st.p[P_SRC] = z; st.p[P_DST] = out;
     split_roots(st, N, H / 2 + 1);
-    st.i[0] = H; st.i[1] = lines; st.i[2] = P; st.f[0] = scale;
+    st.i[RS_H] = H; st.i[RS_BATCH] = lines; st.i[RS_LINE_STRIDE] = P; st.f[F_SCALE] = scale;
     st.grid = oneshot_grid(split_items(lines, H));      // items of 512 bin pairs (r2c_post_kernel)
     ir.route += "r2c-split ";
     return MI355FFT_OK;
@@ -524,9 +534,9 @@ struct Builder {
     const int64_t H = N / 2, P = H + 1;
     PtrRef z = alloc_work((uint64_t)lines * H * 8);
     Step& st = push(ST_C2R_PRE);
-    st.p[0] = packed; st.p[1] = z;
+    st.p[P_SRC] = packed; st.p[P_DST] = z;
     split_roots(st, N, H / 2 + 1);
-    st.i[0] = H; st.i[1] = lines; st.i[2] = P;
+    st.i[RS_H] = H; st.i[RS_BATCH] = lines; st.i[RS_LINE_STRIDE] = P;
     st.grid = oneshot_grid(split_items(lines, H));      // items of 512 bin pairs (c2r_pre_kernel)
     // unnormalised inverse of length H lands x[2n] + i x[2n+1]: exactly the real output, read as complex
     int rc = emit_axis(z, out, H, 1, lines, true, scale, err);
@@ -552,8 +562,8 @@ struct Builder {
     x.tb = line_tables(mr);
     xcd_roots(x, N);
     Step& st = push_xcd(ST_XCD_FUSED, xm->id, x, in.plus(im.offset * 8), out.plus(om.offset * 8), lines, N);
-    st.i[9] = im.batch_stride; st.i[10] = om.batch_stride;
-    st.f[0] = scale;
+    st.i[XS_IN_PITCH] = im.batch_stride; st.i[XS_OUT_PITCH] = om.batch_stride;
+    st.f[F_SCALE] = scale;
     st.imap = im; st.omap = om;
     ir.route += "xcd-fused-view[N=" + std::to_string(xm->N1) + "x" + std::to_string(xm->N2) + "] ";
     return true;
@@ -562,13 +572,7 @@ struct Builder {
     if (opt.force_generic || !is_pow2(N) || N < 2 || N > opt.max_line || (opt.xcd_fused == 2 && N == 4096)) return false;
     const LineKernelMeta* m = find_line_kernel((int)N, false, false, inverse, inverse, 0);
     if (!m) return false;
-    Step& st = push(ST_LINES);
-    st.variant = m->id;
-    st.p[0] = src; st.p[1] = dst; st.p[2] = line_tables(*m);
-    const int64_t tiles = (lines + m->T - 1) / m->T;
-    st.i[0] = tiles; st.i[1] = lines; st.i[2] = 1; st.i[3] = in_pitch; st.i[4] = 1; st.i[5] = out_pitch;
-    st.f[0] = scale;
-    st.grid = lines_grid(*m, tiles, true);
+    push_lines(*m, src, dst, lines, {1, in_pitch}, {1, out_pitch}, scale, true);
     ir.route += "lines[N=" + std::to_string(N) + ",pitch=" + std::to_string(in_pitch) + "/" + std::to_string(out_pitch) + "] ";
     return true;
   }
@@ -599,15 +603,10 @@ struct Builder {
     const bool col = S > 1;
     const LineKernelMeta* m = find_line_kernel((int)N, col, col, inverse, inverse, 0);
     if (!m) return MI355FFT_ERR_UNSUPPORTED;
-    const int64_t lines = S * outer, tiles = (lines + m->T - 1) / m->T;
     im.ax = om.ax = ax;
-    Step& st = push(ST_LINES);
-    st.variant = m->id;
-    st.p[0] = src; st.p[1] = dst; st.p[2] = line_tables(*m);
-    st.i[0] = tiles; st.i[1] = lines; st.i[2] = S; st.i[3] = S * N; st.i[4] = S; st.i[5] = S * N; st.i[10] = 1;
-    st.f[0] = scale;
+    Step& st = push_lines(*m, src, dst, S * outer, {S, S * N}, {S, S * N}, scale);
+    st.i[LS_MAPPED] = 1;
     st.imap = im; st.omap = om;
-    st.grid = lines_grid(*m, tiles);
     ir.route += std::string(col ? "columns-mapped[N=" : "lines-mapped[N=") + std::to_string(N) + (col ? ",S=" + std::to_string(S) : "") + "] ";
     return MI355FFT_OK;
   }
@@ -617,8 +616,8 @@ struct Builder {
     // work buffers taken inside one axis transform are temporaries: released on every exit
     struct Scope { uint64_t& top; uint64_t mark; ~Scope() { top = mark; } } scope{work_top, work_top};
     if (N == 1) {
-      if (!src.same(dst)) { Step& c = push(ST_COPY); c.p[0] = src; c.p[1] = dst; c.i[0] = lines * 8; }
-      if (scale != 1.0f) { Step& s = push(ST_SCALE); s.p[0] = dst; s.i[0] = lines * 2; s.f[0] = scale; s.grid = generic_grid(lines * 2); }
+      if (!src.same(dst)) { Step& c = push(ST_COPY); c.p[P_SRC] = src; c.p[P_DST] = dst; c.i[S_COUNT] = lines * 8; }
+      if (scale != 1.0f) { Step& s = push(ST_SCALE); s.p[P_DATA] = dst; s.i[S_COUNT] = lines * 2; s.f[F_SCALE] = scale; s.grid = generic_grid(lines * 2); }
       return MI355FFT_OK;
     }
     const bool p2 = is_pow2(N);
@@ -636,10 +635,10 @@ struct Builder {
       for (int64_t h = 0; h < N / 1024; ++h) t.push_back(root_of_unity(h << 10, N));
       Step& st = push(ST_LINES_MIXED);
       st.variant = 1000 + lg;
-      st.p[0] = src; st.p[1] = dst; st.p[2] = add_table(t);
-      st.i[0] = lines; st.i[1] = N; st.i[2] = 1; st.i[3] = 1; st.i[4] = 3;
-      st.i[5] = inverse ? 1 : 0; st.i[7] = N / 64;
-      st.f[0] = scale;
+      st.p[P_SRC] = src; st.p[P_DST] = dst; st.p[P_TW] = add_table(t);
+      st.i[MX_LINES] = lines; st.i[MX_N] = N; st.i[MX_S] = 1; st.i[MX_T] = 1; st.i[MX_NST] = 3;
+      st.i[MX_SWAP] = inverse ? 1 : 0; st.i[MX_THREADS] = N / 64;
+      st.f[F_SCALE] = scale;
       const int64_t per_cu = N == 32768 ? 1 : (N == 16384 ? 2 : (N == 8192 ? 4 : 8));
       st.grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(lines, (int64_t)opt.compute_units * per_cu));
       ir.route += (N == 32768 ? std::string("line32k[N=32768] ") : "line-reg[N=" + std::to_string(N) + "] ");
@@ -648,13 +647,7 @@ struct Builder {
     if (!opt.force_generic && S == 1 && p2 && N <= opt.max_line && !(opt.xcd_fused == 2 && N == 4096)) {   // xcd_fused == 2: emulation tests
       const LineKernelMeta* m = find_line_kernel((int)N, false, false, inverse, inverse, 0);
       if (m) {
-        Step& st = push(ST_LINES);
-        st.variant = m->id;
-        st.p[0] = src; st.p[1] = dst; st.p[2] = line_tables(*m);
-        const int64_t tiles = (lines + m->T - 1) / m->T;
-        st.i[0] = tiles; st.i[1] = lines; st.i[2] = 1; st.i[3] = N; st.i[4] = 1; st.i[5] = N;
-        st.f[0] = scale;
-        st.grid = lines_grid(*m, tiles, true);
+        push_lines(*m, src, dst, lines, {1, N}, {1, N}, scale, true);
         ir.route += "lines[N=" + std::to_string(N) + "] ";
         return MI355FFT_OK;
       }
@@ -666,26 +659,15 @@ struct Builder {
       // an axis with stride S > 1 (N-D transforms): T adjacent lines form a column tile
       const LineKernelMeta* m = find_line_kernel((int)N, true, true, inverse, inverse, 0);
       if (m && S % m->T == 0) {
-        Step& st = push(ST_LINES);
-        st.variant = m->id;
-        st.p[0] = src; st.p[1] = dst; st.p[2] = line_tables(*m);
-        const int64_t tiles = lines / m->T;
-        st.i[0] = tiles; st.i[1] = lines; st.i[2] = S; st.i[3] = S * N; st.i[4] = S; st.i[5] = S * N;
-        st.f[0] = scale;
-        st.grid = lines_grid(*m, tiles);
+        push_lines(*m, src, dst, lines, {S, S * N}, {S, S * N}, scale, false, lines / m->T);
         ir.route += "columns[N=" + std::to_string(N) + ",S=" + std::to_string(S) + "] ";
         return MI355FFT_OK;
       }
       // S not a multiple of the tile width (the packed axis 0 of an N-D r2c: S = N0/2 + 1): per-group tiles, ragged last one
       const LineKernelMeta* mr = find_line_kernel((int)N, true, true, inverse, inverse, 3);
       if (mr && S >= mr->T) {
-        Step& st = push(ST_LINES);
-        st.variant = mr->id;
-        st.p[0] = src; st.p[1] = dst; st.p[2] = line_tables(*mr);
-        const int64_t tpg = (S + mr->T - 1) / mr->T, tiles = outer * tpg;
-        st.i[0] = tiles; st.i[1] = lines; st.i[2] = S; st.i[3] = S * N; st.i[4] = S; st.i[5] = S * N; st.i[8] = tpg;
-        st.f[0] = scale;
-        st.grid = lines_grid(*mr, tiles);
+        const int64_t tpg = (S + mr->T - 1) / mr->T;
+        push_lines(*mr, src, dst, lines, {S, S * N}, {S, S * N}, scale, false, outer * tpg).i[LS_FS_GROUP] = tpg;
         ir.route += "columns-ragged[N=" + std::to_string(N) + ",S=" + std::to_string(S) + "] ";
         return MI355FFT_OK;
       }
@@ -700,7 +682,7 @@ struct Builder {
       xcd_roots(x, N);
       const int variant = (inverse ? 1 : 0) + (opt.xcd_res == 2 || opt.xcd_res == 4 ? 2 : 0) + (opt.xcd_res >= 3 && !inverse ? 4 : 0);   // 3: stamps, 4: stamps on the skeleton
       Step& st = push_xcd(ST_XCD_RES, variant, x, src, dst, lines, N);
-      st.f[0] = scale;
+      st.f[F_SCALE] = scale;
       ir.route += "xcd-resident[N=1024x1024,depth=" + std::to_string(opt.xcd_res_depth) + (opt.xcd_res == 2 || opt.xcd_res == 4 ? ",skeleton" : "") + (opt.xcd_res >= 3 ? ",stamps" : "") + "] ";
       return MI355FFT_OK;
     }
@@ -742,10 +724,10 @@ struct Builder {
         x.ta = a_rt ? x.tb : xm->kind == XK_RT1K_2048 ? regtile_table() : line_tables(ma);
         xcd_roots(x, N);
         Step& st = push_xcd(ST_XCD_FUSED, xm->id, x, src, dst, lines, N);
-        if (lane_in_pitch) st.i[9] = lane_in_pitch;
-        if (lane_out_pitch) st.i[10] = lane_out_pitch;
+        if (lane_in_pitch) st.i[XS_IN_PITCH] = lane_in_pitch;
+        if (lane_out_pitch) st.i[XS_OUT_PITCH] = lane_out_pitch;
         if (lane_in_pitch || lane_out_pitch) lane_used = true;
-        st.f[0] = scale;
+        st.f[F_SCALE] = scale;
         ir.route += std::string(solo ? "xcd-solo" : xcd_c2c_route(xm->kind)) + "[N=" + std::to_string(xm->N1) + "x" + std::to_string(xm->N2) + "] ";
         return MI355FFT_OK;
       }
@@ -770,23 +752,23 @@ struct Builder {
           if (opt.only_pass != 2) {
           Step& a = push(ST_LINES);
           a.variant = ma->id;
-          a.p[0] = src.plus(t0 * N * 8); a.p[1] = w; a.p[2] = ta;
-          a.i[0] = c * N2 / ma->T; a.i[1] = c * N2; a.i[2] = N2; a.i[3] = N; a.i[4] = N2; a.i[5] = N;
-          a.f[0] = 1.0f;
-          a.grid = lines_grid(*ma, a.i[0]);
+          a.p[LP_IN] = src.plus(t0 * N * 8); a.p[LP_OUT] = w; a.p[LP_TW] = ta;
+          a.i[LS_TILES] = c * N2 / ma->T; a.i[LS_LINES] = c * N2; a.i[LS_IN_S] = N2; a.i[LS_IN_OUTER] = N; a.i[LS_OUT_S] = N2; a.i[LS_OUT_OUTER] = N;
+          a.f[F_SCALE] = 1.0f;
+          a.grid = lines_grid(*ma, a.i[LS_TILES]);
           }
           if (opt.only_pass == 1) continue;
           Step& b = push(ST_LINES);
           b.variant = mb->id;
-          b.p[0] = w; b.p[1] = dst.plus(t0 * N * 8); b.p[2] = tb; b.p[3] = tlo; b.p[4] = thi;
-          b.i[0] = c * N1 / mb->T; b.i[1] = c * N1; b.i[2] = 1; b.i[3] = N2; b.i[4] = N1; b.i[5] = N; b.i[6] = 10; b.i[7] = 1023;
-          b.f[0] = scale;
-          b.grid = lines_grid(*mb, b.i[0]);
+          b.p[LP_IN] = w; b.p[LP_OUT] = dst.plus(t0 * N * 8); b.p[LP_TW] = tb; b.p[LP_TW_LO] = tlo; b.p[LP_TW_HI] = thi;
+          b.i[LS_TILES] = c * N1 / mb->T; b.i[LS_LINES] = c * N1; b.i[LS_IN_S] = 1; b.i[LS_IN_OUTER] = N2; b.i[LS_OUT_S] = N1; b.i[LS_OUT_OUTER] = N; b.i[LS_FS_SHIFT] = 10; b.i[LS_FS_LO_MASK] = 1023;
+          b.f[F_SCALE] = scale;
+          b.grid = lines_grid(*mb, b.i[LS_TILES]);
           // four-step roots e^{-2 pi i k1 n2/N} enter at pass B's loads; with a grid that is a multiple of the
           // tiles per transform every workgroup keeps the same rows k1 and computes its roots once per launch
           const int64_t tpt = N1 / mb->T;
           if ((int64_t)b.grid >= tpt) b.grid = (unsigned)((b.grid / tpt) * tpt);
-          b.i[8] = N1;
+          b.i[LS_FS_GROUP] = N1;
         }
         ir.route += "two-pass[N=" + std::to_string(N1) + "x" + std::to_string(N2) + ",chunk=" + std::to_string(chunk) + "] ";
         return MI355FFT_OK;
@@ -815,10 +797,10 @@ struct Builder {
           nsp *= R;
         }
         st.variant = cm->id + 1;
-        st.p[0] = src; st.p[1] = dst; st.p[2] = add_table(t);
-        st.i[0] = lines; st.i[1] = N; st.i[2] = 1; st.i[3] = cm->T; st.i[4] = (int64_t)cm->radices.size();
-        st.i[5] = inverse ? 1 : 0; st.i[7] = cm->threads;
-        st.f[0] = scale;
+        st.p[P_SRC] = src; st.p[P_DST] = dst; st.p[P_TW] = add_table(t);
+        st.i[MX_LINES] = lines; st.i[MX_N] = N; st.i[MX_S] = 1; st.i[MX_T] = cm->T; st.i[MX_NST] = (int64_t)cm->radices.size();
+        st.i[MX_SWAP] = inverse ? 1 : 0; st.i[MX_THREADS] = cm->threads;
+        st.f[F_SCALE] = scale;
         const int64_t tiles = (lines + cm->T - 1) / cm->T;
         const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>((160 * 1024) / (cm->lds_bytes + 1024), 2048 / cm->threads), 8));
         st.grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(tiles, (int64_t)opt.compute_units * per_cu));
@@ -836,7 +818,7 @@ struct Builder {
       int64_t nsp = 1;
       for (int s = 0; s < ns; ++s) {
         const int R = radices[s];
-        st.i[8 + s] = ((int64_t)R << 32) | (int64_t)t.size();       // radix, table offset (elements)
+        st.i[MX_RADIX0 + s] = ((int64_t)R << 32) | (int64_t)t.size();       // radix, table offset (elements)
         const size_t off = t.size();
         t.resize(off + (size_t)(R * nsp));
         for (int q = 0; q < R; ++q) for (int64_t k = 0; k < nsp; ++k) t[off + (size_t)(q * nsp + k)] = root_of_unity(q * k, nsp * R);
@@ -851,10 +833,10 @@ struct Builder {
       else { T = 1; threads = std::max<int64_t>(64, std::min<int64_t>(256, ((N / 8 + 63) / 64) * 64)); }
       const int64_t lds_bytes = 2 * T * (N + (N >> 5) + 1) * 8;          // kern_mixed.hpp mixed_pitch
       const int64_t tw_lds = (int64_t)t.size() * 8 <= 16 * 1024 ? (int64_t)t.size() : 0;
-      st.p[0] = src; st.p[1] = dst; st.p[2] = add_table(t);
-      st.i[0] = lines; st.i[1] = N; st.i[2] = S; st.i[3] = T; st.i[4] = ns;
-      st.i[5] = inverse ? 1 : 0; st.i[6] = lds_bytes; st.i[7] = threads; st.i[19] = tw_lds;
-      st.f[0] = scale;
+      st.p[P_SRC] = src; st.p[P_DST] = dst; st.p[P_TW] = add_table(t);
+      st.i[MX_LINES] = lines; st.i[MX_N] = N; st.i[MX_S] = S; st.i[MX_T] = T; st.i[MX_NST] = ns;
+      st.i[MX_SWAP] = inverse ? 1 : 0; st.i[MX_LDS_BYTES] = lds_bytes; st.i[MX_THREADS] = threads; st.i[MX_TW_TOTAL] = tw_lds;
+      st.f[F_SCALE] = scale;
       const int64_t tiles = (lines + T - 1) / T;
       const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>((160 * 1024) / (lds_bytes + tw_lds * 8 + 1024), 2048 / threads), 8));
       st.grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(tiles, (int64_t)opt.compute_units * per_cu));
@@ -877,11 +859,11 @@ struct Builder {
       } else t.push_back(float2h{1, 0});
       Step& st = push(ST_STAGE);
       st.variant = R;
-      st.p[0] = cur; st.p[1] = to; st.p[2] = add_table(t);
-      st.i[0] = lines * (N / R); st.i[1] = N; st.i[2] = S; st.i[3] = nsp;
-      st.i[4] = (inverse && s == 0) ? 1 : 0; st.i[5] = (inverse && last) ? 1 : 0;
-      st.f[0] = last ? scale : 1.0f;
-      st.grid = generic_grid(st.i[0]);
+      st.p[P_SRC] = cur; st.p[P_DST] = to; st.p[P_TW] = add_table(t);
+      st.i[SG_TOTAL] = lines * (N / R); st.i[SG_N] = N; st.i[SG_S] = S; st.i[SG_NSP] = nsp;
+      st.i[SG_SWAP_IN] = (inverse && s == 0) ? 1 : 0; st.i[SG_SWAP_OUT] = (inverse && last) ? 1 : 0;
+      st.f[F_SCALE] = last ? scale : 1.0f;
+      st.grid = generic_grid(st.i[SG_TOTAL]);
       cur = to;
       nsp *= R;
     }
@@ -917,10 +899,10 @@ struct Builder {
     if (S > 1) {
       tr = alloc_work((uint64_t)lines * N * 8);
       Step& g = push(ST_GATHER);     // transpose [outer][N][S] -> [outer][S][N]
-      g.p[0] = src; g.p[1] = tr;
-      g.i[0] = lines * N; g.i[1] = S * N; g.i[2] = 2; g.i[3] = 0; g.i[4] = S * N; g.i[5] = 0; g.i[6] = S * N;
+      g.p[P_SRC] = src; g.p[P_DST] = tr;
+      g.i[GS_TOTAL] = lines * N; g.i[GS_PER] = S * N; g.i[GS_RANK] = 2; g.i[GS_PHYS_OFFSET] = 0; g.i[GS_PHYS_BATCH_STRIDE] = S * N; g.i[GS_DENSE_OFFSET] = 0; g.i[GS_DENSE_BATCH_STRIDE] = S * N;
       g.shape[0] = N; g.shape[1] = S; g.sa[0] = S; g.sa[1] = 1; g.sb[0] = 1; g.sb[1] = N;
-      g.grid = generic_grid(g.i[0]);
+      g.grid = generic_grid(g.i[GS_TOTAL]);
       lin_src = tr; lin_dst = tr;
     }
     const PtrRef y = alloc_work((uint64_t)lines * M * 8);
@@ -938,50 +920,42 @@ struct Builder {
         SideMap win = dense_map(one, 1);          // N live points of an M-point line, lines N apart
         win.hi[0] = (int)N; win.batch_stride = N; win.ax = 0;
         const SideMap full = dense_map(one, 1);
-        const int64_t flags = 1 | (inverse ? 2 : 0);
-        Step& f = push(ST_LINES);
-        f.variant = mf->id;
-        f.p[0] = lin_src; f.p[1] = y; f.p[2] = line_tables(*mf); f.p[3] = tb; f.p[4] = tchirp;
-        int64_t tiles = (lines + mf->T - 1) / mf->T;
-        f.i[0] = tiles; f.i[1] = lines; f.i[2] = 1; f.i[3] = M; f.i[4] = 1; f.i[5] = M; f.i[6] = 0; f.i[7] = flags; f.i[9] = 4; f.i[10] = 1;
-        f.f[0] = 1.0f;
+        const int64_t flags = LINES_CHIRP | (inverse ? LINES_CHIRP_SWAP : 0);
+        Step& f = push_lines(*mf, lin_src, y, lines, {1, M}, {1, M}, 1.0f);
+        f.p[LP_MUL_SPECTRUM] = tb; f.p[LP_CHIRP] = tchirp;
+        f.i[LS_MUL_CONJ] = 0; f.i[LS_CHIRP_FLAGS] = flags; f.i[LS_MODE] = LM_MUL; f.i[LS_MAPPED] = 1;
         f.imap = win; f.omap = full;
-        f.grid = lines_grid(*mf, tiles);
-        Step& g = push(ST_LINES);
-        g.variant = mi->id;
-        g.p[0] = y; g.p[1] = lin_dst; g.p[2] = line_tables(*mi); g.p[4] = tchirp;
-        tiles = (lines + mi->T - 1) / mi->T;
-        g.i[0] = tiles; g.i[1] = lines; g.i[2] = 1; g.i[3] = M; g.i[4] = 1; g.i[5] = M; g.i[7] = flags; g.i[10] = 1;
-        g.f[0] = (float)((double)scale / (double)M);
+        Step& g = push_lines(*mi, y, lin_dst, lines, {1, M}, {1, M}, (float)((double)scale / (double)M));
+        g.p[LP_CHIRP] = tchirp;
+        g.i[LS_CHIRP_FLAGS] = flags; g.i[LS_MAPPED] = 1;
         g.imap = full; g.omap = win;
-        g.grid = lines_grid(*mi, tiles);
         ir.route += "bluestein-lines[N=" + std::to_string(N) + ",M=" + std::to_string(M) + "] ";
         return MI355FFT_OK;
       }
     }
     Step& pre = push(ST_CHIRP_PRE);
-    pre.p[0] = lin_src; pre.p[1] = y; pre.p[2] = tchirp;
-    pre.i[0] = N; pre.i[1] = M; pre.i[2] = lines; pre.i[3] = inverse ? 1 : 0; pre.i[4] = 0;
+    pre.p[P_SRC] = lin_src; pre.p[P_DST] = y; pre.p[CHP_CHIRP] = tchirp;
+    pre.i[CH_N] = N; pre.i[CH_M] = M; pre.i[CH_LINES] = lines; pre.i[CH_SWAP_IN] = inverse ? 1 : 0; pre.i[CH_SWAP_OUT] = 0;
     pre.grid = generic_grid(lines * M);
     int rc = emit_axis(y, y, M, 1, lines, false, 1.0f, err);
     if (rc) return rc;
     Step& pm = push(ST_POINTWISE);
-    pm.p[0] = y; pm.p[1] = y; pm.p[2] = tb;
-    pm.i[0] = M; pm.i[1] = lines * M; pm.i[2] = 0; pm.f[0] = 1.0f;
+    pm.p[P_SRC] = y; pm.p[P_DST] = y; pm.p[PWP_KERNEL] = tb;
+    pm.i[PW_L] = M; pm.i[PW_TOTAL] = lines * M; pm.i[PW_CONJ] = 0; pm.f[F_SCALE] = 1.0f;
     pm.grid = generic_grid(lines * M);
     rc = emit_axis(y, y, M, 1, lines, true, 1.0f, err);
     if (rc) return rc;
     Step& post = push(ST_CHIRP_POST);
-    post.p[0] = y; post.p[1] = lin_dst; post.p[2] = tchirp;
-    post.i[0] = N; post.i[1] = M; post.i[2] = lines; post.i[3] = 0; post.i[4] = inverse ? 1 : 0;
-    post.f[0] = (float)((double)scale / (double)M);
+    post.p[P_SRC] = y; post.p[P_DST] = lin_dst; post.p[CHP_CHIRP] = tchirp;
+    post.i[CH_N] = N; post.i[CH_M] = M; post.i[CH_LINES] = lines; post.i[CH_SWAP_IN] = 0; post.i[CH_SWAP_OUT] = inverse ? 1 : 0;
+    post.f[F_SCALE] = (float)((double)scale / (double)M);
     post.grid = generic_grid(lines * N);
     if (S > 1) {
       Step& sc = push(ST_SCATTER);   // back to [outer][N][S]
-      sc.p[0] = tr; sc.p[1] = dst;
-      sc.i[0] = lines * N; sc.i[1] = S * N; sc.i[2] = 2; sc.i[3] = 0; sc.i[4] = S * N; sc.i[5] = 0; sc.i[6] = S * N;
+      sc.p[P_SRC] = tr; sc.p[P_DST] = dst;
+      sc.i[GS_TOTAL] = lines * N; sc.i[GS_PER] = S * N; sc.i[GS_RANK] = 2; sc.i[GS_PHYS_OFFSET] = 0; sc.i[GS_PHYS_BATCH_STRIDE] = S * N; sc.i[GS_DENSE_OFFSET] = 0; sc.i[GS_DENSE_BATCH_STRIDE] = S * N;
       sc.shape[0] = N; sc.shape[1] = S; sc.sa[0] = S; sc.sa[1] = 1; sc.sb[0] = 1; sc.sb[1] = N;
-      sc.grid = generic_grid(sc.i[0]);
+      sc.grid = generic_grid(sc.i[GS_TOTAL]);
     }
     ir.route += "bluestein[N=" + std::to_string(N) + ",M=" + std::to_string(M) + "] ";
     return MI355FFT_OK;
@@ -1072,11 +1046,11 @@ struct Builder {
                     const int64_t* dense_shape, const int64_t* dense_sub_offset, int64_t dense_batch_stride, int64_t extra_phys_offset,
                     bool real_elements = false) {
     Step& st = push(gather ? ST_GATHER : ST_SCATTER);
-    st.i[7] = real_elements ? 1 : 0;
-    st.p[0] = gather ? phys : dense;
-    st.p[1] = gather ? dense : phys;
+    st.i[GS_REAL] = real_elements ? 1 : 0;
+    st.p[P_SRC] = gather ? phys : dense;
+    st.p[P_DST] = gather ? dense : phys;
     const int64_t per = prodv(shape, rank);
-    st.i[0] = batch * per; st.i[1] = per; st.i[2] = rank;
+    st.i[GS_TOTAL] = batch * per; st.i[GS_PER] = per; st.i[GS_RANK] = rank;
     int64_t dstride = 1, doff = 0, pstride = 1;
     for (int d = 0; d < rank; ++d) {
       st.shape[d] = shape[d];
@@ -1086,11 +1060,11 @@ struct Builder {
       dstride *= dense_shape[d];
       pstride *= shape[d];
     }
-    st.i[3] = (lay.strided ? lay.offset_elements : 0) + extra_phys_offset;
-    st.i[4] = (lay.strided && lay.batch_stride_elements > 0) ? lay.batch_stride_elements : per;
-    st.i[5] = doff;
-    st.i[6] = dense_batch_stride;
-    st.grid = generic_grid(st.i[0]);
+    st.i[GS_PHYS_OFFSET] = (lay.strided ? lay.offset_elements : 0) + extra_phys_offset;
+    st.i[GS_PHYS_BATCH_STRIDE] = (lay.strided && lay.batch_stride_elements > 0) ? lay.batch_stride_elements : per;
+    st.i[GS_DENSE_OFFSET] = doff;
+    st.i[GS_DENSE_BATCH_STRIDE] = dense_batch_stride;
+    st.grid = generic_grid(st.i[GS_TOTAL]);
   }
 };
 
@@ -1139,11 +1113,11 @@ bool view_region(const mi355fft_io_view& v, const int64_t* lshape, int rank, int
 
 void emit_zero_outside(Builder& b, PtrRef data, const mi355fft_zero_range& z, const int64_t* shape, int rank, int64_t batch, bool real = false) {
   Step& st = b.push(ST_ZERO_OUTSIDE);
-  st.p[0] = data; st.i[3] = real ? 1 : 0;
+  st.p[P_DATA] = data; st.i[ZO_REAL] = real ? 1 : 0;
   const int64_t per = prodv(shape, rank);
-  st.i[0] = per * batch; st.i[1] = per; st.i[2] = rank;
+  st.i[ZO_TOTAL] = per * batch; st.i[ZO_PER] = per; st.i[ZO_RANK] = rank;
   for (int i = 0; i < rank; ++i) { st.shape[i] = shape[i]; st.sa[i] = z.start[i]; st.sb[i] = z.end[i]; }
-  st.grid = b.generic_grid(st.i[0]);
+  st.grid = b.generic_grid(st.i[ZO_TOTAL]);
 }
 
 int validate_views(const mi355fft_plan_desc& d, std::string& err, const int64_t* read_shape = nullptr, const int64_t* write_shape = nullptr) {
@@ -1246,7 +1220,7 @@ PtrRef stage_side_input(const mi355fft_plan_desc& d, Builder& b, PtrRef in, cons
     b.emit_strided(true, in, src, d.input, lshape, rank, d.batch, lshape, nullptr, n, 0, real);
     b.ir.route += "gather ";
   } else if (!d.in_place) {
-    Step& c = b.push(ST_COPY); c.p[0] = in; c.p[1] = src; c.i[0] = n * d.batch * elem;
+    Step& c = b.push(ST_COPY); c.p[P_SRC] = in; c.p[P_DST] = src; c.i[S_COUNT] = n * d.batch * elem;
   }
   if (d.zero_read.enabled) { emit_zero_outside(b, src, d.zero_read, lshape, rank, d.batch, real); b.ir.route += "zero-read "; }
   return src;
@@ -1422,11 +1396,11 @@ int build_r2c(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
   } else {
     PtrRef full = b.alloc_work((uint64_t)lines * N * 8);
     Step& e = b.push(ST_REAL_TO_COMPLEX);
-    e.p[0] = in; e.p[1] = full; e.i[0] = lines * N; e.grid = b.generic_grid(lines * N);
+    e.p[P_SRC] = in; e.p[P_DST] = full; e.i[S_COUNT] = lines * N; e.grid = b.generic_grid(lines * N);
     int rc = b.emit_axis(full, full, N, 1, lines, false, 1.0f, err);
     if (rc) return rc;
     Step& p = b.push(ST_PACK_HALF);
-    p.p[0] = full; p.p[1] = out; p.i[0] = N; p.i[1] = P; p.i[2] = lines; p.i[3] = P; p.f[0] = scale;
+    p.p[P_SRC] = full; p.p[P_DST] = out; p.i[PH_N] = N; p.i[PH_P] = P; p.i[PH_BATCH] = lines; p.i[PH_PACKED_STRIDE] = P; p.f[F_SCALE] = scale;
     p.grid = b.generic_grid(lines * P);
     b.ir.route += "r2c-full ";
   }
@@ -1498,12 +1472,12 @@ int build_c2r(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
   } else {
     PtrRef full = b.alloc_work((uint64_t)lines * N * 8);
     Step& u = b.push(ST_UNPACK_HERM);
-    u.p[0] = packed; u.p[1] = full; u.i[0] = N; u.i[1] = P; u.i[2] = lines; u.i[3] = P;
+    u.p[P_SRC] = packed; u.p[P_DST] = full; u.i[PH_N] = N; u.i[PH_P] = P; u.i[PH_BATCH] = lines; u.i[PH_PACKED_STRIDE] = P;
     u.grid = b.generic_grid(lines * N);
     int rc = b.emit_axis(full, full, N, 1, lines, true, 1.0f, err);
     if (rc) return rc;
     Step& r = b.push(ST_COMPLEX_TO_REAL);
-    r.p[0] = full; r.p[1] = out; r.i[0] = lines * N; r.f[0] = scale;
+    r.p[P_SRC] = full; r.p[P_DST] = out; r.i[S_COUNT] = lines * N; r.f[F_SCALE] = scale;
     r.grid = b.generic_grid(lines * N);
     b.ir.route += "c2r-full ";
   }
@@ -1523,14 +1497,14 @@ int build_trig(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
   const bool fwd = d.direction == MI355FFT_FORWARD;
   int kind;
   switch (d.type) {                                     // dct_fft.js:48-57
-    case MI355FFT_DCT1: kind = 0; break;
-    case MI355FFT_DCT2: kind = fwd ? 1 : 2; break;
-    case MI355FFT_DCT3: kind = fwd ? 2 : 1; break;
-    case MI355FFT_DCT4: kind = 3; break;
-    case MI355FFT_DST1: kind = 4; break;
-    case MI355FFT_DST2: kind = fwd ? 5 : 6; break;
-    case MI355FFT_DST3: kind = fwd ? 6 : 5; break;
-    default: kind = 7; break;
+    case MI355FFT_DCT1: kind = TK_DCT1; break;
+    case MI355FFT_DCT2: kind = fwd ? TK_DCT2_FWD : TK_DCT2_INV; break;
+    case MI355FFT_DCT3: kind = fwd ? TK_DCT2_INV : TK_DCT2_FWD; break;
+    case MI355FFT_DCT4: kind = TK_DCT4; break;
+    case MI355FFT_DST1: kind = TK_DST1; break;
+    case MI355FFT_DST2: kind = fwd ? TK_DST2_FWD : TK_DST2_INV; break;
+    case MI355FFT_DST3: kind = fwd ? TK_DST2_INV : TK_DST2_FWD; break;
+    default: kind = TK_DST4; break;
   }
   const int64_t n = prodv(d.shape, rank);
   const float scale = (float)scale_factor(d.normalize, !fwd, (double)n);
@@ -1541,33 +1515,34 @@ int build_trig(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
   int general_axes = 0;
   for (int a = 0; a < rank; ++a) {
     const int64_t N = d.shape[a], lines = d.batch * (n / N);
-    const int64_t L = kind == 0 ? 2 * (N - 1) : (kind == 4 ? 2 * (N + 1) : 2 * N);
+    const int64_t L = kind == TK_DCT1 ? 2 * (N - 1) : (kind == TK_DST1 ? 2 * (N + 1) : 2 * N);
     const uint64_t mark = b.work_top;
-    if (b.opt.trig_real && !b.opt.force_generic && N >= 4 && (N % 2 == 0 || kind == 0 || kind == 4)) {
+    if (b.opt.trig_real && !b.opt.force_generic && N >= 4 && (N % 2 == 0 || kind == TK_DCT1 || kind == TK_DST1)) {
       // dense lines: a real FFT of length N behind Makhoul's permutation (dct2/dst2 and their inverses), a complex FFT of
-      // length N/2 (dct4/dst4), or the r2c of the real even/odd extension (dct1/dst1) -- kern_trig.hpp kinds 8..15
-      const bool tfwd = kind == 1 || kind == 5, tinv = kind == 2 || kind == 6, quarter = kind == 3 || kind == 7;
-      const int rkind = tfwd ? (kind == 1 ? 8 : 9) : tinv ? (kind == 2 ? 10 : 11) : quarter ? (kind == 3 ? 12 : 13) : (kind == 0 ? 14 : 15);
+      // length N/2 (dct4/dst4), or the r2c of the real even/odd extension (dct1/dst1) -- kern_trig.hpp kinds TK_REAL..
+      const bool tfwd = kind == TK_DCT2_FWD || kind == TK_DST2_FWD, tinv = kind == TK_DCT2_INV || kind == TK_DST2_INV, quarter = kind == TK_DCT4 || kind == TK_DST4;
+      const int rkind = tfwd ? (kind == TK_DCT2_FWD ? TK_REAL_DCT2_FWD : TK_REAL_DST2_FWD) : tinv ? (kind == TK_DCT2_INV ? TK_REAL_DCT2_INV : TK_REAL_DST2_INV)
+                      : quarter ? (kind == TK_DCT4 ? TK_REAL_DCT4 : TK_REAL_DST4) : (kind == TK_DCT1 ? TK_REAL_DCT1 : TK_REAL_DST1);
       // DCT-II / DST-II of dense lines whose half length is a line-kernel size: permutation, real FFT and phase in ONE launch
-      if (tfwd && S == 1 && b.opt.trig_fused && b.emit_lines_r2c(cur, dst, N, lines, a == rank - 1 ? scale : 1.0f, false, kind == 1 ? 5 : 6)) {
+      if (tfwd && S == 1 && b.opt.trig_fused && b.emit_lines_r2c(cur, dst, N, lines, a == rank - 1 ? scale : 1.0f, false, kind == TK_DCT2_FWD ? LM_DCT2 : LM_DST2)) {
         cur = dst;
         S *= N;
         continue;
       }
       // DCT-III / DST-III the same way on the c2r line kernel (bins formed from the real line in the pre-split, un-permutation
       // in the store); needs the LDS line buffer: half lengths of 64 and more
-      if (tinv && S == 1 && N >= 128 && b.opt.trig_fused && b.emit_lines_r2c(cur, dst, N, lines, a == rank - 1 ? scale : 1.0f, true, kind == 2 ? 7 : 8)) {
+      if (tinv && S == 1 && N >= 128 && b.opt.trig_fused && b.emit_lines_r2c(cur, dst, N, lines, a == rank - 1 ? scale : 1.0f, true, kind == TK_DCT2_INV ? LM_DCT3 : LM_DST3)) {
         cur = dst;
         S *= N;
         continue;
       }
-      const int64_t M = quarter ? N / 2 : (kind == 0 || kind == 4 ? L : N);     // length of the FFT in the middle
+      const int64_t M = quarter ? N / 2 : (kind == TK_DCT1 || kind == TK_DST1 ? L : N);     // length of the FFT in the middle
       const int64_t P = quarter ? M : M / 2 + 1;                                  // complex elements per line
       const PtrRef v = quarter ? PtrRef() : b.alloc_work((uint64_t)lines * M * 4), V = b.alloc_work((uint64_t)lines * P * 8);
       const float last = a == rank - 1 ? scale : 1.0f;
       Step& pre = b.push(ST_TRIG_PRE);
-      pre.p[0] = cur; pre.p[1] = V; pre.p[2] = quarter ? dst : v;
-      pre.i[0] = lines; pre.i[1] = N; pre.i[2] = P; pre.i[3] = M; pre.i[4] = rkind; pre.i[5] = S;
+      pre.p[TGP_X] = cur; pre.p[TGP_Z] = V; pre.p[TGP_Y] = quarter ? dst : v;
+      pre.i[TG_LINES] = lines; pre.i[TG_N] = N; pre.i[TG_REAL_P] = P; pre.i[TG_REAL_M] = M; pre.i[TG_KIND] = rkind; pre.i[TG_STRIDE] = S;
       // S > 1 (axes >= 1): 32 x 32 tiles through LDS, one workgroup per tile
       const auto tiled_grid = [&](int64_t per) { return b.oneshot_grid((lines / S) * ((S + 31) / 32) * ((per + 31) / 32)); };   // one workgroup per tile
       pre.grid = S > 1 ? tiled_grid(tinv || quarter ? P : M) : b.oneshot_grid((lines * (tinv || quarter ? P : M) + 255) / 256);   // streaming pass: one-shot grid (r02)
@@ -1576,9 +1551,9 @@ int build_trig(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
                    : tinv ? b.emit_c2r_even(V, v, M, lines, 1.0f, err) : b.emit_r2c_even(v, V, M, lines, 1.0f, err);
       if (rc) return rc;
       Step& post = b.push(ST_TRIG_POST);
-      post.p[0] = quarter ? cur : v; post.p[1] = V; post.p[2] = dst;
-      post.i[0] = lines; post.i[1] = N; post.i[2] = P; post.i[3] = M; post.i[4] = rkind; post.i[5] = S;
-      post.f[0] = last;
+      post.p[TGP_X] = quarter ? cur : v; post.p[TGP_Z] = V; post.p[TGP_Y] = dst;
+      post.i[TG_LINES] = lines; post.i[TG_N] = N; post.i[TG_REAL_P] = P; post.i[TG_REAL_M] = M; post.i[TG_KIND] = rkind; post.i[TG_STRIDE] = S;
+      post.f[F_SCALE] = last;
       post.grid = S > 1 ? tiled_grid(tfwd || quarter ? P : N) : b.oneshot_grid((lines * (tfwd || quarter ? P : N) + 255) / 256);
       b.work_top = mark;
       cur = dst;
@@ -1588,15 +1563,15 @@ int build_trig(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
     const PtrRef z = b.alloc_work((uint64_t)lines * L * 8);
     ++general_axes;
     Step& pre = b.push(ST_TRIG_PRE);
-    pre.p[0] = cur; pre.p[1] = z; pre.p[2] = dst;
-    pre.i[0] = lines; pre.i[1] = N; pre.i[2] = L; pre.i[3] = S; pre.i[4] = kind;
+    pre.p[TGP_X] = cur; pre.p[TGP_Z] = z; pre.p[TGP_Y] = dst;
+    pre.i[TG_LINES] = lines; pre.i[TG_N] = N; pre.i[TG_L] = L; pre.i[TG_S] = S; pre.i[TG_KIND] = kind;
     pre.grid = b.generic_grid(lines * L);
-    const int rc = b.emit_axis(z, z, L, 1, lines, kind == 2 || kind == 6, 1.0f, err);
+    const int rc = b.emit_axis(z, z, L, 1, lines, kind == TK_DCT2_INV || kind == TK_DST2_INV, 1.0f, err);
     if (rc) return rc;
     Step& post = b.push(ST_TRIG_POST);
-    post.p[0] = cur; post.p[1] = z; post.p[2] = dst;
-    post.i[0] = lines; post.i[1] = N; post.i[2] = L; post.i[3] = S; post.i[4] = kind;
-    post.f[0] = a == rank - 1 ? scale : 1.0f;
+    post.p[TGP_X] = cur; post.p[TGP_Z] = z; post.p[TGP_Y] = dst;
+    post.i[TG_LINES] = lines; post.i[TG_N] = N; post.i[TG_L] = L; post.i[TG_S] = S; post.i[TG_KIND] = kind;
+    post.f[F_SCALE] = a == rank - 1 ? scale : 1.0f;
     post.grid = b.generic_grid(lines * N);
     b.work_top = mark;         // the complex lines are a per-axis temporary
     cur = dst;
@@ -1745,7 +1720,7 @@ void conv_staged_crop(Builder& b, const mi355fft_plan_desc& d, const ConvGeom& g
 // ---- re-basing a finished plan onto workspace staging (f16-storage, rconv-widened) ----
 Step convert_step(StepKind kind, PtrRef src, PtrRef dst, int64_t count, unsigned grid) {
   Step c;
-  c.kind = kind; c.p[0] = src; c.p[1] = dst; c.i[0] = count; c.grid = grid;
+  c.kind = kind; c.p[P_SRC] = src; c.p[P_DST] = dst; c.i[S_COUNT] = count; c.grid = grid;
   return c;
 }
 // Every reference to the caller's input / output / kernel buffer moves to the workspace offset given for it; the converter steps
@@ -1794,13 +1769,13 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
       for (int q = 1; q < cm->R1; ++q) for (int k = 0; k < cm->R0; ++k) tw.push_back(root_of_unity((int64_t)q * k, fN));
       Step& st = b.push(ST_FFTCONV_FUSED);
       st.variant = cm->id;
-      st.p[0] = in; st.p[1] = kern; st.p[2] = out; st.p[3] = b.add_table(tw);
-      st.i[0] = B; st.i[1] = K; st.i[2] = ks[0]; st.i[3] = g.corr ? 1 : 0;
-      st.i[4] = d.input.strided ? d.input.offset_elements : 0;
-      st.i[5] = (d.input.strided && d.input.batch_stride_elements > 0) ? d.input.batch_stride_elements : inN;
-      st.i[6] = d.input.strided ? d.input.strides[0] : 1;
-      st.i[7] = g.lane0; st.i[8] = g.lane_k; st.i[9] = g.lane_b; st.i[10] = d.output.strided ? d.output.strides[0] : 1;
-      st.f[0] = (float)(1.0 / (double)fN);
+      st.p[FCP_IN] = in; st.p[FCP_KERN] = kern; st.p[FCP_OUT] = out; st.p[FCP_TW] = b.add_table(tw);
+      st.i[FC_BATCH] = B; st.i[FC_K] = K; st.i[FC_KERN_LEN] = ks[0]; st.i[FC_CONJ] = g.corr ? 1 : 0;
+      st.i[FC_IN_OFFSET] = d.input.strided ? d.input.offset_elements : 0;
+      st.i[FC_IN_BATCH_STRIDE] = (d.input.strided && d.input.batch_stride_elements > 0) ? d.input.batch_stride_elements : inN;
+      st.i[FC_IN_STRIDE] = d.input.strided ? d.input.strides[0] : 1;
+      st.i[FC_OUT_OFFSET] = g.lane0; st.i[FC_OUT_KERNEL_STRIDE] = g.lane_k; st.i[FC_OUT_BATCH_STRIDE] = g.lane_b; st.i[FC_OUT_STRIDE] = d.output.strided ? d.output.strides[0] : 1;
+      st.f[F_SCALE] = (float)(1.0 / (double)fN);
       st.grid = (unsigned)std::min<int64_t>(B, (int64_t)b.opt.compute_units * 4);
       b.ir.route += "fftconv-fused[N=" + std::to_string(fN) + ",K=" + std::to_string(K) + ",TL=" + std::to_string(cm->TL) + "] ";
       return MI355FFT_OK;
@@ -1847,19 +1822,19 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
       x.ta = x.tb = b.line_tables(make_meta(0, 1024, 32, 32, 1, 32, true, true, false, false, 0));
       b.xcd_roots(x, fN);
       Step& st = b.push_xcd(ST_XCD_FUSED, xm->id, x, in, view ? out.plus(-g.ooff[0] * 8) : out, B, fN);
-      st.i[10] = g.lane_b;                    // between data lines
-      st.i[17] = g.lane_k;                    // between the kernels of one data line
-      st.i[14] = kf.off - x.wslots.off; st.i[15] = K; st.i[16] = g.corr ? 1 : 0;
-      st.f[0] = (float)(1.0 / (double)fN);
+      st.i[XS_OUT_PITCH] = g.lane_b;                    // between data lines
+      st.i[XS_OUT_KERNEL_PITCH] = g.lane_k;                    // between the kernels of one data line
+      st.i[XS_MUL_OFF] = kf.off - x.wslots.off; st.i[XS_CONV_K] = K; st.i[XS_CONV_CONJ] = g.corr ? 1 : 0;
+      st.f[F_SCALE] = (float)(1.0 / (double)fN);
       if (view) {
-        st.i[9] = inN;                        // the data lines keep their own length: nothing is embedded
+        st.i[XS_IN_PITCH] = inN;                        // the data lines keep their own length: nothing is embedded
         // the launch addresses both sides itself (the pitches above, `out - ooff` as its pointer): its maps carry the ranges
         // only and stay dense over the domain
         st.imap = conv_load_map(d, g, fs, rank);
         st.omap = conv_store_map(d, g, fs, rank, 0);
         st.omap.offset = 0;
         st.imap.batch_stride = st.omap.batch_stride = fN;
-        st.i[18] = g.split; st.i[19] = g.padD;
+        st.i[XS_V_SPLIT] = g.split; st.i[XS_V_SHIFT] = g.padD;
         b.ir.route += "fftconv-pipeline-view[N=1024x1024,K=" + std::to_string(K) + "] ";
       } else b.ir.route += "fftconv-pipeline[N=1024x1024,K=" + std::to_string(K) + "] ";
       return MI355FFT_OK;
@@ -1873,7 +1848,7 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
   if (!fuse_in) {
     if (embed) b.zero(xf, B * fN * 2);
     if (embed || d.input.strided) b.emit_strided(true, in, xf, d.input, d.shape, rank, B, fs, zero, fN, 0);
-    else if (d.zero_read.enabled) { Step& c = b.push(ST_COPY); c.p[0] = in; c.p[1] = xf; c.i[0] = B * fN * 8; }
+    else if (d.zero_read.enabled) { Step& c = b.push(ST_COPY); c.p[P_SRC] = in; c.p[P_DST] = xf; c.i[S_COUNT] = B * fN * 8; }
     if (d.zero_read.enabled) { emit_zero_outside(b, xf, d.zero_read, fs, rank, B); b.ir.route += "zero-read "; }
   }
   const bool staged = side_in && !fuse_in;
@@ -1900,18 +1875,18 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
     if (mul_m) {
       Step& st = b.push(ST_LINES);
       st.variant = mul_m->id;
-      st.p[0] = staged ? xf : in; st.p[1] = y; st.p[2] = mul_tables; st.p[3] = kf.plus(k * fN * 8);
+      st.p[LP_IN] = staged ? xf : in; st.p[LP_OUT] = y; st.p[LP_TW] = mul_tables; st.p[LP_MUL_SPECTRUM] = kf.plus(k * fN * 8);
       const int64_t tiles = (B + mul_m->T - 1) / mul_m->T;
-      st.i[0] = tiles; st.i[1] = B; st.i[2] = 1; st.i[3] = fN; st.i[4] = 1; st.i[5] = fN;
-      st.i[6] = g.corr ? 1 : 0; st.i[9] = 4;
-      st.f[0] = 1.0f;
+      st.i[LS_TILES] = tiles; st.i[LS_LINES] = B; st.i[LS_IN_S] = 1; st.i[LS_IN_OUTER] = fN; st.i[LS_OUT_S] = 1; st.i[LS_OUT_OUTER] = fN;
+      st.i[LS_MUL_CONJ] = g.corr ? 1 : 0; st.i[LS_MODE] = LM_MUL;
+      st.f[F_SCALE] = 1.0f;
       st.grid = b.lines_grid(*mul_m, tiles);
-      if (fuse_in) { st.i[10] = 1; st.imap = xmap; st.imap.ax = 0; st.omap = Builder::dense_map(fs, rank); }
+      if (fuse_in) { st.i[LS_MAPPED] = 1; st.imap = xmap; st.imap.ax = 0; st.omap = Builder::dense_map(fs, rank); }
       if (k == 0) b.ir.route += std::string(fuse_in ? "lines-mul-mapped[N=" : "lines-mul[N=") + std::to_string(fN) + "] ";
     } else {
       Step& pm = b.push(ST_POINTWISE);
-      pm.p[0] = xf; pm.p[1] = y; pm.p[2] = kf.plus(k * fN * 8);
-      pm.i[0] = fN; pm.i[1] = B * fN; pm.i[2] = g.corr ? 1 : 0; pm.f[0] = 1.0f;
+      pm.p[P_SRC] = xf; pm.p[P_DST] = y; pm.p[PWP_KERNEL] = kf.plus(k * fN * 8);
+      pm.i[PW_L] = fN; pm.i[PW_TOTAL] = B * fN; pm.i[PW_CONJ] = g.corr ? 1 : 0; pm.f[F_SCALE] = 1.0f;
       pm.grid = b.generic_grid(B * fN);
     }
     if (fuse_out) {
@@ -1994,11 +1969,11 @@ int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err
       for (int64_t k = 0; k < K; ++k) {
         Step& st = b.push(ST_LINES);
         st.variant = om->id;
-        st.p[0] = in; st.p[1] = out; st.p[2] = tables; st.p[3] = proots; st.p[4] = G.plus(k * (H + 1) * 8);
-        st.i[0] = tiles; st.i[1] = lines; st.i[2] = 1; st.i[3] = H; st.i[4] = 1; st.i[5] = H; st.i[6] = 10; st.i[7] = 1023;
-        st.i[9] = 10; st.i[10] = 1; st.i[12] = corr ? 1 : 0;
-        st.i[13] = lfN; st.i[14] = corr ? d.shape[0] : lfN; st.i[15] = nb; st.i[16] = L; st.i[17] = corr ? pre - (M - 1) : pre; st.i[18] = pre;
-        st.f[0] = (float)(1.0 / (double)P);
+        st.p[LP_IN] = in; st.p[LP_OUT] = out; st.p[LP_TW] = tables; st.p[LP_TW_LO] = proots; st.p[LP_RCONV_SPECTRUM] = G.plus(k * (H + 1) * 8);
+        st.i[LS_TILES] = tiles; st.i[LS_LINES] = lines; st.i[LS_IN_S] = 1; st.i[LS_IN_OUTER] = H; st.i[LS_OUT_S] = 1; st.i[LS_OUT_OUTER] = H; st.i[LS_FS_SHIFT] = 10; st.i[LS_FS_LO_MASK] = 1023;
+        st.i[LS_MODE] = LM_RCONV_OLS; st.i[LS_MAPPED] = 1; st.i[LS_CONJ] = corr ? 1 : 0;
+        st.i[LS_OLS_FN] = lfN; st.i[LS_OLS_PLIM] = corr ? d.shape[0] : lfN; st.i[LS_OLS_NB] = nb; st.i[LS_OLS_L] = L; st.i[LS_OLS_W0] = corr ? pre - (M - 1) : pre; st.i[LS_OLS_PRE] = pre;
+        st.f[F_SCALE] = (float)(1.0 / (double)P);
         st.imap = xm; st.omap = conv_store_map(d, g, fs, 1, k);
         st.grid = b.lines_grid(*om, tiles);
       }
@@ -2032,10 +2007,10 @@ int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err
     for (int64_t k = 0; k < K; ++k) {
       Step& st = b.push(ST_LINES);
       st.variant = rm->id;
-      st.p[0] = in; st.p[1] = out; st.p[2] = tables; st.p[3] = proots; st.p[4] = G.plus(k * (H + 1) * 8);
-      st.i[0] = tiles; st.i[1] = B; st.i[2] = 1; st.i[3] = H; st.i[4] = 1; st.i[5] = H; st.i[6] = 10; st.i[7] = 1023;
-      st.i[9] = 9; st.i[10] = 1; st.i[12] = corr ? 1 : 0; st.i[13] = g.split; st.i[14] = g.padD;
-      st.f[0] = (float)(1.0 / (double)P);
+      st.p[LP_IN] = in; st.p[LP_OUT] = out; st.p[LP_TW] = tables; st.p[LP_TW_LO] = proots; st.p[LP_RCONV_SPECTRUM] = G.plus(k * (H + 1) * 8);
+      st.i[LS_TILES] = tiles; st.i[LS_LINES] = B; st.i[LS_IN_S] = 1; st.i[LS_IN_OUTER] = H; st.i[LS_OUT_S] = 1; st.i[LS_OUT_OUTER] = H; st.i[LS_FS_SHIFT] = 10; st.i[LS_FS_LO_MASK] = 1023;
+      st.i[LS_MODE] = LM_RCONV; st.i[LS_MAPPED] = 1; st.i[LS_CONJ] = corr ? 1 : 0; st.i[LS_RCONV_SPLIT] = g.split; st.i[LS_RCONV_PADD] = g.padD;
+      st.f[F_SCALE] = (float)(1.0 / (double)P);
       st.imap = xm; st.omap = conv_store_map(d, g, fs, 1, k);
       st.grid = b.lines_grid(*rm, tiles);
     }
@@ -2094,7 +2069,7 @@ int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err
       if (emb) {
         b.zero(xr, count * fN);
         b.emit_strided(true, src, xr, dense, shp, rank, count, fs, zero, fN, 0, true);
-      } else { Step& c = b.push(ST_COPY); c.p[0] = src; c.p[1] = xr; c.i[0] = count * fN * 4; }
+      } else { Step& c = b.push(ST_COPY); c.p[P_SRC] = src; c.p[P_DST] = xr; c.i[S_COUNT] = count * fN * 4; }
       if (zr) {
         emit_zero_outside(b, xr, g.padded(*zr), fs, rank, count, true);
         b.ir.route += "zero-read ";
@@ -2115,8 +2090,8 @@ int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err
   const float inv_n = (float)(1.0 / (double)fN);
   for (int64_t k = 0; k < K; ++k) {
     Step& pm = b.push(ST_POINTWISE);
-    pm.p[0] = xf; pm.p[1] = y; pm.p[2] = kf.plus(k * pN * 8);
-    pm.i[0] = pN; pm.i[1] = B * pN; pm.i[2] = corr ? 1 : 0; pm.f[0] = 1.0f;
+    pm.p[P_SRC] = xf; pm.p[P_DST] = y; pm.p[PWP_KERNEL] = kf.plus(k * pN * 8);
+    pm.i[PW_L] = pN; pm.i[PW_TOTAL] = B * pN; pm.i[PW_CONJ] = corr ? 1 : 0; pm.f[F_SCALE] = 1.0f;
     pm.grid = b.generic_grid(B * pN);
     if (rank > 1 && (rc = b.emit_nd(y, y, ps, rank, B, true, 1.0f, err, 1))) return rc;
     const PtrRef dst = direct_out ? out.plus(g.lane_offset(k) * 4) : yr;
@@ -2149,12 +2124,12 @@ int validate_f16_storage(const mi355fft_plan_desc& d, std::string& err) {
 bool fuse_f16_storage(PlanIR& ir) {
   if (ir.steps.size() != 1) return false;
   Step& s = ir.steps[0];
-  if (s.kind != ST_LINES || s.i[10] != 0 || s.i[9] < 0 || s.i[9] > 2) return false;
-  if (!s.p[0].same(PtrRef(BUF_INPUT, 0)) || !s.p[1].same(PtrRef(BUF_OUTPUT, 0))) return false;
+  if (s.kind != ST_LINES || s.i[LS_MAPPED] != 0 || s.i[LS_MODE] < LM_C2C || s.i[LS_MODE] > LM_C2R) return false;
+  if (!s.p[LP_IN].same(PtrRef(BUF_INPUT, 0)) || !s.p[LP_OUT].same(PtrRef(BUF_OUTPUT, 0))) return false;
   const LineKernelMeta& m = line_kernel_registry()[(size_t)s.variant];
   if (m.in_col || m.out_col || m.twid != 0 || m.swap_in != m.swap_out) return false;
-  if (s.i[9] == 0 && (s.i[2] != 1 || s.i[4] != 1 || s.i[3] != m.N || s.i[5] != m.N)) return false;   // c2c: dense lines, no pitches
-  s.i[11] = 1;
+  if (s.i[LS_MODE] == LM_C2C && (s.i[LS_IN_S] != 1 || s.i[LS_OUT_S] != 1 || s.i[LS_IN_OUTER] != m.N || s.i[LS_OUT_OUTER] != m.N)) return false;   // c2c: dense lines, no pitches
+  s.i[LS_H16] = 1;
   ir.route += "f16 ";
   return true;
 }

@@ -105,15 +105,142 @@ enum StepKind : int {
   ST_F16_TO_F32, ST_F32_TO_F16   // f16-storage plans: i[0] scalars widened / rounded to nearest even (kern_f16.hpp)
 };
 
-// One recorded launch, pointers still symbolic.  Scalar fields are kind-specific (see dispatch.hpp).
+// ---- the step contract: what the planner (plan.cpp) writes into a Step's p[] / i[] / f[] slots and the dispatcher (dispatch.hpp) reads.
+// One enum of slot names per step kind; two names with one value mark a slot that means different things per mode.  Names of i[] slots
+// carry their kind's prefix (LS_, XS_, TG_, ...), names of p[] slots that prefix with a P (LP_, XP_, TGP_, ...; P_ where kinds share them).
+constexpr int STEP_PTRS = 5, STEP_INTS = 20, STEP_FLOATS = 2;
+
+// every kind: f[F_SCALE]; the kinds with one source and one destination (or one array worked on in place) and a count in i[S_COUNT]:
+// ST_ZERO / ST_SCALE (32-bit words), ST_COPY (bytes), ST_REAL_TO_COMPLEX / ST_COMPLEX_TO_REAL / ST_F16_TO_F32 / ST_F32_TO_F16 (elements)
+enum StepSlot { P_SRC = 0, P_DATA = 0, P_DST = 1, P_TW = 2, S_COUNT = 0, F_SCALE = 0 };
+static_assert(P_TW < STEP_PTRS && S_COUNT < STEP_INTS && F_SCALE < STEP_FLOATS, "shared slots");
+
+// what a line-kernel launch computes (LineArgs::real_mode, Step::i[LS_MODE])
+enum LineMode : int {
+  LM_C2C = 0,
+  LM_R2C = 1,         // r2c: the split behind the last stage (fft_lines_r2c_kernel)
+  LM_C2R = 2,         // c2r: the pre-split in the first-stage loads (fft_lines_c2r_kernel)
+  LM_MUL = 4,         // c2c times a spectrum in the last store (fft_lines_mul_kernel): fftconv products, Bluestein's forward launch
+  LM_DCT2 = 5, LM_DST2 = 6,   // one-launch DCT-II / DST-II on the r2c kernel
+  LM_DCT3 = 7, LM_DST3 = 8,   // one-launch DCT-III / DST-III on the c2r kernel
+  LM_RCONV = 9,       // real fftconv line: r2c, product and c2r in one launch (fft_lines_rconv_kernel)
+  LM_RCONV_OLS = 10   // its overlap-save form (fft_lines_rconv_ols_kernel)
+};
+// Bluestein's two mapped launches: bits of i[LS_CHIRP_FLAGS] (LineArgs::fs_lo_mask)
+enum : unsigned { LINES_CHIRP = 1, LINES_CHIRP_SWAP = 2 };   // multiply by the chirp in p[LP_CHIRP]; inverse transform: the chirp's conjugate
+
+// ST_LINES
+enum LinesSlot {
+  LS_TILES = 0, LS_LINES, LS_IN_S, LS_IN_OUTER, LS_OUT_S, LS_OUT_OUTER,
+  LS_FS_SHIFT = 6, LS_MUL_CONJ = 6,          // four-step roots: HI[m >> shift]; LM_MUL: multiply by the spectrum's conjugate
+  LS_FS_LO_MASK = 7, LS_CHIRP_FLAGS = 7,     // ... LO[m & mask]; mapped LM_C2C / LM_MUL of Bluestein: LINES_CHIRP bits
+  LS_FS_GROUP = 8,                           // PASS_B: rows per transform; COL_RAGGED: tiles per group (0 reads as 1)
+  LS_MODE = 9,                               // LineMode
+  LS_MAPPED = 10,                            // sides through Step::imap / omap
+  LS_H16 = 11,                               // binary16 sides (f16-storage)
+  LS_CONJ = 12,                              // LM_RCONV, LM_RCONV_OLS: correlation
+  LS_RCONV_SPLIT = 13, LS_OLS_FN = 13,       // LM_RCONV: ConvGeom split / padD;  LM_RCONV_OLS: the block geometry (kern_lines.hpp RconvOls)
+  LS_RCONV_PADD = 14, LS_OLS_PLIM = 14,
+  LS_OLS_NB = 15, LS_OLS_L = 16, LS_OLS_W0 = 17, LS_OLS_PRE = 18,
+  LS_LAST = LS_OLS_PRE
+};
+static_assert(LS_LAST < STEP_INTS, "ST_LINES slots");
+enum LinesPtr {
+  LP_IN = 0, LP_OUT = 1, LP_TW = 2,
+  LP_TW_LO = 3, LP_MUL_SPECTRUM = 3,         // four-step / split LO roots (LM_RCONV*: LO and HI in one table); LM_MUL: the spectrum multiplied in
+  LP_TW_HI = 4, LP_CHIRP = 4, LP_RCONV_SPECTRUM = 4,   // HI roots; Bluestein: the chirp; LM_RCONV*: the packed kernel spectrum
+  LP_LAST = LP_RCONV_SPECTRUM
+};
+static_assert(LP_LAST < STEP_PTRS, "ST_LINES pointers");
+
+// ST_XCD_FUSED / ST_XCD_RES
+enum XcdSlot {
+  XS_TRANSFORMS = 0, XS_N, XS_FS_SHIFT, XS_FS_LO_MASK,
+  XS_TW_A_OFF, XS_TW_B_OFF, XS_TW_LO_OFF, XS_TW_HI_OFF,     // byte offsets into p[XP_TABLE]
+  XS_SPLIT = 8, XS_IN_PITCH, XS_OUT_PITCH, XS_SLOTS, XS_SOLO, XS_SPIN_LIMIT,
+  XS_MUL_OFF = 14, XS_CONV_K, XS_CONV_CONJ, XS_OUT_KERNEL_PITCH,   // fftconv pipeline (CONV, CONV_VIEW): spectra at p[XP_WSLOTS] + offset
+  XS_V_SPLIT = 18, XS_V_SHIFT = 19,                                  // CONV_VIEW only
+  XS_LAST = XS_V_SHIFT
+};
+static_assert(XS_LAST < STEP_INTS, "ST_XCD_* slots");
+enum XcdPtr { XP_IN = 0, XP_OUT, XP_WSLOTS, XP_CTL, XP_TABLE, XP_LAST = XP_TABLE };
+static_assert(XP_LAST < STEP_PTRS, "ST_XCD_* pointers");
+
+// ST_LINES_MIXED (p: P_SRC, P_DST, P_TW)
+enum MixedSlot {
+  MX_LINES = 0, MX_N, MX_S, MX_T, MX_NST, MX_SWAP, MX_LDS_BYTES, MX_THREADS,
+  MX_RADIX0 = 8,        // run-time plans: (radix << 32 | table offset) per stage, i[MX_RADIX0 + k]
+  MX_TW_TOTAL = 19,     // table elements staged in LDS (0: read through the caches)
+  MX_LAST = MX_TW_TOTAL
+};
+static_assert(MX_LAST < STEP_INTS, "ST_LINES_MIXED slots");
+
+// ST_STAGE (p: P_SRC, P_DST, P_TW)
+enum StageSlot { SG_TOTAL = 0, SG_N, SG_S, SG_NSP, SG_SWAP_IN, SG_SWAP_OUT, SG_LAST = SG_SWAP_OUT };
+static_assert(SG_LAST < STEP_INTS, "ST_STAGE slots");
+
+// ST_TRIG_PRE / ST_TRIG_POST (kern_trig.hpp TrigArgs).  The real-FFT kinds (>= TK_REAL) put the packed line length P and the FFT
+// length M where the general kinds have L and S, and the axis stride behind the kind
+enum TrigSlot { TG_LINES = 0, TG_N, TG_L = 2, TG_REAL_P = 2, TG_S = 3, TG_REAL_M = 3, TG_KIND, TG_STRIDE, TG_LAST = TG_STRIDE };
+static_assert(TG_LAST < STEP_INTS, "ST_TRIG_* slots");
+enum TrigPtr { TGP_X = 0, TGP_Z, TGP_Y, TGP_LAST = TGP_Y };
+static_assert(TGP_LAST < STEP_PTRS, "ST_TRIG_* pointers");
+// i[TG_KIND]: the table at the top of kern_trig.hpp.  The kernels there compare a.kind as a number (kind < 10, kind >= 14, kind & 1 for the
+// sine kinds): the values and their order are part of the contract, a new kind goes behind the last
+enum TrigKind : int {
+  TK_DCT1 = 0, TK_DCT2_FWD, TK_DCT2_INV, TK_DCT4, TK_DST1, TK_DST2_FWD, TK_DST2_INV, TK_DST4,
+  TK_REAL = 8,          // from here on: through a real (or half-length complex) FFT of dense or tiled lines
+  TK_REAL_DCT2_FWD = 8, TK_REAL_DST2_FWD, TK_REAL_DCT2_INV, TK_REAL_DST2_INV, TK_REAL_DCT4, TK_REAL_DST4, TK_REAL_DCT1, TK_REAL_DST1
+};
+
+// ST_GATHER / ST_SCATTER (p: P_SRC, P_DST; kern_generic.hpp StridedArgs)
+enum StridedSlot { GS_TOTAL = 0, GS_PER, GS_RANK, GS_PHYS_OFFSET, GS_PHYS_BATCH_STRIDE, GS_DENSE_OFFSET, GS_DENSE_BATCH_STRIDE, GS_REAL, GS_LAST = GS_REAL };
+static_assert(GS_LAST < STEP_INTS, "ST_GATHER / ST_SCATTER slots");
+
+// ST_ZERO_OUTSIDE (p: P_DATA)
+enum ZeroOutsideSlot { ZO_TOTAL = 0, ZO_PER, ZO_RANK, ZO_REAL, ZO_LAST = ZO_REAL };
+static_assert(ZO_LAST < STEP_INTS, "ST_ZERO_OUTSIDE slots");
+
+// ST_FFTCONV_FUSED (kern_fftconv.hpp FusedConvArgs)
+enum FusedConvSlot {
+  FC_BATCH = 0, FC_K, FC_KERN_LEN, FC_CONJ, FC_IN_OFFSET, FC_IN_BATCH_STRIDE, FC_IN_STRIDE,
+  FC_OUT_OFFSET, FC_OUT_KERNEL_STRIDE, FC_OUT_BATCH_STRIDE, FC_OUT_STRIDE, FC_LAST = FC_OUT_STRIDE
+};
+static_assert(FC_LAST < STEP_INTS, "ST_FFTCONV_FUSED slots");
+enum FusedConvPtr { FCP_IN = 0, FCP_KERN, FCP_OUT, FCP_TW, FCP_LAST = FCP_TW };
+static_assert(FCP_LAST < STEP_PTRS, "ST_FFTCONV_FUSED pointers");
+
+// ST_R2C_POST / ST_C2R_PRE (p: P_SRC, P_DST, then the split roots)
+enum SplitSlot { RS_H = 0, RS_BATCH, RS_LINE_STRIDE, RS_SHIFT, RS_MASK, RS_LAST = RS_MASK };
+static_assert(RS_LAST < STEP_INTS, "ST_R2C_POST / ST_C2R_PRE slots");
+enum SplitPtr { RSP_TW_LO = 2, RSP_TW_HI = 3, RSP_LAST = RSP_TW_HI };
+static_assert(RSP_LAST < STEP_PTRS, "ST_R2C_POST / ST_C2R_PRE pointers");
+
+// ST_PACK_HALF / ST_UNPACK_HERM (p: P_SRC, P_DST)
+enum PackSlot { PH_N = 0, PH_P, PH_BATCH, PH_PACKED_STRIDE, PH_LAST = PH_PACKED_STRIDE };
+static_assert(PH_LAST < STEP_INTS, "ST_PACK_HALF / ST_UNPACK_HERM slots");
+
+// ST_POINTWISE (p: P_SRC, P_DST, PWP_KERNEL)
+enum PointwiseSlot { PW_L = 0, PW_TOTAL, PW_CONJ, PW_LAST = PW_CONJ };
+static_assert(PW_LAST < STEP_INTS, "ST_POINTWISE slots");
+enum PointwisePtr { PWP_KERNEL = 2, PWP_LAST = PWP_KERNEL };
+static_assert(PWP_LAST < STEP_PTRS, "ST_POINTWISE pointers");
+
+// ST_CHIRP_PRE / ST_CHIRP_POST (p: P_SRC, P_DST, CHP_CHIRP)
+enum ChirpSlot { CH_N = 0, CH_M, CH_LINES, CH_SWAP_IN, CH_SWAP_OUT, CH_LAST = CH_SWAP_OUT };
+static_assert(CH_LAST < STEP_INTS, "ST_CHIRP_* slots");
+enum ChirpPtr { CHP_CHIRP = 2, CHP_LAST = CHP_CHIRP };
+static_assert(CHP_LAST < STEP_PTRS, "ST_CHIRP_* pointers");
+
+// One recorded launch, pointers still symbolic.  Scalar fields are kind-specific: the slot enums above.
 struct Step {
   StepKind kind;
   int variant = 0;           // ST_LINES: registry id; ST_STAGE: radix
-  PtrRef p[5];               // kind-specific pointer slots
-  int64_t i[20] = {0};     // kind-specific integers
-  float f[2] = {1.0f, 1.0f}; // kind-specific floats
+  PtrRef p[STEP_PTRS];       // kind-specific pointer slots
+  int64_t i[STEP_INTS] = {0};     // kind-specific integers
+  float f[STEP_FLOATS] = {1.0f, 1.0f}; // kind-specific floats
   int64_t shape[8] = {0}, sa[8] = {0}, sb[8] = {0};  // ST_GATHER / ST_SCATTER
-  SideMap imap, omap;        // ST_LINES with i[10] != 0: mapped sides (kern_lines.hpp fft_lines_mapped_kernel)
+  SideMap imap, omap;        // ST_LINES with i[LS_MAPPED] != 0: mapped sides (kern_lines.hpp fft_lines_mapped_kernel)
   unsigned grid = 1;
 };
 
