@@ -88,8 +88,12 @@ struct XcdFusedArgs {
 };
 
 // roots for one PASS_B tile, generated per tile: anchors by exact table lookup every 8th element, the 7 in between by
-// multiplying with the per-thread step e^{-2 pi i (N2/R0) k1/N} (error <= 8 roundings; the hoisted form of
-// kern_lines.hpp would need 64 VGPRs per row tile, and a workgroup owns two)
+// multiplying with the per-thread step e^{-2 pi i (N2/R0) k1/N} (the hoisted form of kern_lines.hpp would need 64 VGPRs per
+// row tile, and a workgroup owns two).  Error of a root, in units of 2^-24: anchors rms 0.6, max 2 (two table roundings and a
+// product); the step's own error enters element j of a chain j times with one sign, so the chain's last element is at rms 3.5 - 4.3,
+// max 12 - 16, all roots rms 2.2 - 2.6; over the roots of ONE row k1 rms up to 5.5 - 7.6.  The outputs of that row are the worst
+// class (one residue of k) of tests/test_*_accuracy.py: 4 - 5.5 times the f32 oracle's error against float64 where the route's
+// mean is 2.0 - 2.2 times and two-pass is flat at 2 (profiles/accuracy_ladder.log).
 template <class C>
 MI_DEV void fourstep_apply_chain(cf (&v)[C::E], const XcdFusedArgs& a, unsigned k1, int u) {
   using I = StageInfo<C, 0>;
