@@ -10,8 +10,8 @@ Two builds of the planner plan alike when their snapshots are equal:
     python tools/plan_snapshot.py --compare parent.txt branch.txt
 
 Without MI355_EMU_LIB the library is built from this tree (tests/emu/Makefile).  --full writes the dumps themselves.  --env NAME=VALUE
-adds a planner switch to every environment (a build that does not know the switch plans as ever): MI355FFT_RCONV_OLS=0 on both sides
-compares a planner with the overlap-save route switched off against one without it.
+adds a planner switch to every environment (a build that does not know the switch plans as ever): MI355FFT_RCONV_OLS=0 or MI355FFT_CONV_OLS=0
+on both sides compares a planner with that overlap-save route switched off against one without it.
 """
 import argparse
 import hashlib
@@ -174,13 +174,17 @@ def conv_corpus(real):
     add([64, 32], [5, 3], "linear-same", K=1, sin=True)          # real: lanes outside the line route
     add([1000], None, "circular", K=1, sout=True)
     add([256], precision="f16-storage")
-    # real: long lines with short kernels (overlap-save by default: MI355FFT_RCONV_OLS; its 0 restores pad[..] rconv[K] and, above 2^22, Bluestein)
-    if real:
-        add([1 << 20], [1024], "linear-same", K=1, batch=8)
-        add([100000], [129], "linear-same", K=2, batch=4)
-        add([9000], [33], "linear-same", K=1, batch=4)
-        add([5000000], [255], "linear-same", K=1, batch=2)
-        add([100000], [129], "linear-full", "correlation", K=2, batch=4, sin=True, sout=True, zr=True, zw=True)
+    # long lines with short kernels (overlap-save by default: MI355FFT_RCONV_OLS for real data, MI355FFT_CONV_OLS for complex; their 0 restores pad[..]
+    # rconv[K] / fftconv[K] or the pipeline and, above 2^22, Bluestein or its refusal)
+    add([1 << 20], [1024], "linear-same", K=1, batch=8)
+    add([100000], [129], "linear-same", K=2, batch=4)
+    add([9000], [33], "linear-same", K=1, batch=4)
+    add([5000000], [255], "linear-same", K=1, batch=2)
+    add([100000], [129], "linear-full", "correlation", K=2, batch=4, sin=True, sout=True, zr=True, zw=True)
+    if not real:
+        add([1 << 20], [255], "linear-same", K=4, batch=8)
+        add([700000], [255], "linear-valid", "correlation", K=1, batch=4)
+        add([20000], [513], "linear-same", K=1, batch=4, layout="batch-major")
     return cases
 
 

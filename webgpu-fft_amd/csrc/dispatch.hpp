@@ -71,6 +71,36 @@ template <class L> bool launch_lines_rconv_ols(int id, const RconvOlsArgs& a, un
 }
 #endif
 
+// complex overlap-save (kern_lines.hpp fft_lines_conv_ols_kernel, route lines-conv-ols): block lengths P = 128 .. 4096, in a unit of their own
+// (lines_conv_ols.hip).  `id`: the registry id of the forward ROW configuration of P points
+template <class L> bool launch_lines_conv_ols(int id, const RconvOlsArgs& a, unsigned grid, L& l);
+#if defined(MI355_CONV_OLS_DEFINE_INSTANCES) || defined(MI355_HOST_EMU)
+template <class L> bool launch_lines_conv_ols(int id, const RconvOlsArgs& a, unsigned grid, L& l) {
+  int cur = 0;
+#define LINE_ROW(N, R0, R1, R2, T)                                                                          \
+  if (id == cur) {                                                                                          \
+    using C = LineCfg<N, R0, R1, R2, T, false, false, false, false, 0>;                                     \
+    if constexpr (C::NSTAGES >= 2 && (N) >= 128 && (N) <= 4096) {                                           \
+      l.launch(fft_lines_conv_ols_kernel<C>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a);        \
+      return true;                                                                                          \
+    } else return false;                                                                                    \
+  }                                                                                                         \
+  cur += 2;
+#define LINE_ROW_TRIG(N, R0, R1, R2, T) cur += 1;
+#define LINE_PASS_A(N, R0, R1, R2, T) cur += 3;
+#define LINE_PASS_B(N, R0, R1, R2, T) cur += 2;
+#define LINE_COL_RAGGED(N, R0, R1, R2, T) cur += 2;
+#include "line_kernels.def"
+#undef LINE_ROW
+#undef LINE_ROW_TRIG
+#undef LINE_PASS_A
+#undef LINE_PASS_B
+#undef LINE_COL_RAGGED
+  (void)cur; (void)a; (void)grid; (void)l;
+  return false;
+}
+#endif
+
 template <int FAMILY, class L>
 bool launch_lines_family(int id, const LineArgs& a, unsigned grid, L& l) {
   int cur = 0;
@@ -350,6 +380,13 @@ bool dispatch_step(const Step& s, void* const ptr[STEP_PTRS], L& l, LinesFn&& li
         oa.a = a;
         oa.o.fN = (int)s.i[LS_OLS_FN]; oa.o.plim = (int)s.i[LS_OLS_PLIM]; oa.o.nb = (int)s.i[LS_OLS_NB]; oa.o.L = (int)s.i[LS_OLS_L]; oa.o.w0 = (int)s.i[LS_OLS_W0]; oa.o.pre = (int)s.i[LS_OLS_PRE];
         return launch_lines_rconv_ols(s.variant, oa, s.grid, l);
+      }
+      if (a.real_mode == LM_CONV_OLS) {   // overlap-save on complex lines: p[LP_MUL_SPECTRUM] (tw_lo) is the kernel spectrum on P points; the same argument block
+        RconvOlsArgs oa{};
+        a.conj = (int)s.i[LS_CONJ];
+        oa.a = a;
+        oa.o.fN = (int)s.i[LS_OLS_FN]; oa.o.plim = (int)s.i[LS_OLS_PLIM]; oa.o.nb = (int)s.i[LS_OLS_NB]; oa.o.L = (int)s.i[LS_OLS_L]; oa.o.w0 = (int)s.i[LS_OLS_W0]; oa.o.pre = (int)s.i[LS_OLS_PRE];
+        return launch_lines_conv_ols(s.variant, oa, s.grid, l);
       }
       const LineKernelMeta& m = line_kernel_registry()[(size_t)s.variant];
       return lines_fn(family_of_line_kernel(m), s.variant, a, s.grid);

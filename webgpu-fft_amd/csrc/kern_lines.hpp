@@ -106,6 +106,7 @@ struct LineArgs {
                          //   LM_RCONV: fft_lines_rconv_kernel (real fftconv line: r2c, product, c2r in one launch; tw_hi = the packed kernel spectrum, H + 1 bins, and the HI
                          //     roots sit behind the 1024 LO roots at tw_lo + 1024; rconv_split, rconv_padD: the padded-domain index map, conj != 0: conjugate the spectrum)
                          //   LM_RCONV_OLS: fft_lines_rconv_ols_kernel (the same on overlap-save blocks: RconvOlsArgs)
+                         //   LM_CONV_OLS: fft_lines_conv_ols_kernel (complex overlap-save blocks: RconvOlsArgs; tw_lo = the kernel spectrum on P points, conj != 0: conjugate it)
   long long fs_group;    // TWID_FOURSTEP_IN: lines per group (line index inside the group = G % fs_group); COL_RAGGED: tiles per group
   // VIEW instantiations of stage_read / stage_compute_write (kern_xcd.hpp fused kernels): rank-1 ranges of a four-step line.  The real fftconv
   // line kernels have no view and keep their own three scalars in the first three (second names)
@@ -1291,6 +1292,103 @@ __global__ void __launch_bounds__(C::THREADS, C::THREADS == 256 && C::T == 1 ? 2
             if (m1 >= slo && m1 < shi) y[base + (long long)m1 * so] = y1;
           }
         }
+      }
+    }
+    __syncthreads();   // LDS is re-used by the next tile
+  }
+}
+
+// Overlap-save on complex lines (type MI355FFT_FFTCONV, route lines-conv-ols): forward FFT, product with one kernel spectrum and inverse FFT
+// of blocks of P = C::N points without leaving LDS.  The block geometry is RconvOls's without the evenness term (complex elements are 8 bytes:
+// every access is naturally aligned): pre = M - 1, L = P - pre, block j = G % nb of signal line G / nb holds signal indices [s0, s0 + P),
+// s0 = j L - pre.  C is the forward ROW configuration of P; the inverse stages run on it through the re/im swap, as in fft_lines_rconv_kernel.
+//   load    : 8-byte loads through a.imap, whose bounds move with the block: [lo - s0, hi - s0) cut to [0, P); 0 elsewhere
+//   forward : the ROW stages, finished spectrum kept in LDS
+//   product : a lane reads the bins its first inverse stage starts from, multiplies them by the spectrum (a.tw_lo = p[LP_MUL_SPECTRUM], P bins,
+//             conjugated when correlating) and swaps re and im: the product costs no pass over LDS of its own
+//   inverse : the same stages, finished block kept in LDS, swapped
+//   store   : the sweep of fft_lines_rconv_ols_kernel, one complex element per position: window [w0, w0 + L), p = s0 + i < plim, m = p or p + fN,
+//             then crop, zeroPad.write and the lane through a.omap; scale 1/P in a.scale
+// Element indices are 32-bit (the planner keeps fN and the number of block-lines below 2^31); offsets into the buffers are formed in 64 bits
+template <class C>
+__global__ void __launch_bounds__(C::THREADS) fft_lines_conv_ols_kernel(const RconvOlsArgs p) {
+  const LineArgs& a = p.a;
+  const RconvOls& o = p.o;
+  static_assert(!C::IN_COL && !C::OUT_COL && !C::SWAP_IN && !C::SWAP_OUT && C::TWID == TWID_NONE && C::NSTAGES >= 2, "forward ROW configuration with an LDS line buffer");
+  MI_SMEM_DECL(smem);
+  cf* lds = reinterpret_cast<cf*>(smem);
+  cf* tw_lds = lds + C::DATA_ELEMS;
+  const int t = threadIdx.x;
+  if constexpr (C::TW_LDS_ELEMS > 0) {
+    for (int i = t; i < C::TW_LDS_ELEMS; i += C::THREADS) tw_lds[i] = a.tw[i];
+    __syncthreads();
+  }
+  using I0 = StageInfo<C, 0>;
+  int line, u; thread_map<C, 0>(t, line, u);      // head, product and store sweep: a thread stays on one line
+  // the spectrum values of this lane's bins, the same for every tile: kept in registers where a workgroup is one line (P = 4096: the LDS bounds the CU to
+  // two workgroups, the registers are free: +7 %), loaded per tile (cache hits) elsewhere, where 2 E more registers cost a workgroup per CU (P = 512 .. 2048:
+  // 20-45 % slower; profiles/fftconv_cols_ab.log)
+  constexpr bool KEEP_SPECTRUM = C::T == 1;
+  cf hk[KEEP_SPECTRUM ? C::E : 1];
+  if constexpr (KEEP_SPECTRUM) {
+#pragma unroll
+    for (int b = 0; b < I0::NB; ++b) {
+#pragma unroll
+      for (int q = 0; q < I0::R; ++q) {
+        cf h = a.tw_lo[u + b * C::TPL + q * (C::N / I0::R)];
+        if (a.conj) h.y = -h.y;
+        hk[b * I0::R + q] = h;
+      }
+    }
+  }
+  const SideMap& im = a.imap;
+  const SideMap& om = a.omap;
+  const long long sa = im.stride[im.ax], so = om.stride[om.ax];
+  const int slo = om.lo[om.ax], shi = om.hi[om.ax], zlo = om.zlo[om.ax], zhi = om.zhi[om.ax];
+  for (long long tile = blockIdx.x; tile < a.num_tiles; tile += gridDim.x) {
+    const unsigned G = (unsigned)(tile * C::T + line), sb = G / (unsigned)o.nb;
+    const int s0 = (int)(G - sb * (unsigned)o.nb) * o.L - o.pre;       // the block's first signal index
+    const bool ok = G < a.num_lines;
+    cf v[C::E];
+    {
+      const cf* x = a.in + (im.offset + (long long)sb * im.batch_stride + (long long)s0 * sa);    // (dereferenced inside [lo, hi) only)
+      const int l0 = im.lo[im.ax] - s0, h0 = im.hi[im.ax] - s0;
+      const int lo = l0 < 0 ? 0 : l0, hi = h0 > C::N ? C::N : h0;     // the block's share of [lo, hi)
+#pragma unroll
+      for (int b = 0; b < I0::NB; ++b) {
+#pragma unroll
+        for (int q = 0; q < I0::R; ++q) {
+          const int idx = u + b * C::TPL + q * (C::N / I0::R);
+          cf xv = {0.0f, 0.0f};
+          if (ok && idx >= lo && idx < hi) xv = x[(long long)idx * sa];
+          v[b * I0::R + q] = xv;
+        }
+      }
+    }
+    stages_keep_in_lds<C>(v, a, tile, t, lds, tw_lds);
+#pragma unroll
+    for (int b = 0; b < I0::NB; ++b) {
+#pragma unroll
+      for (int q = 0; q < I0::R; ++q) {
+        const int idx = u + b * C::TPL + q * (C::N / I0::R);
+        cf h;
+        if constexpr (KEEP_SPECTRUM) h = hk[b * I0::R + q];
+        else { h = a.tw_lo[idx]; if (a.conj) h.y = -h.y; }
+        v[b * I0::R + q] = cswap_if<true>(cmul(lds[lds_index<C>(line, idx)], h));
+      }
+    }
+    __syncthreads();   // everyone has its inputs before stage 0 re-uses the buffer
+    stages_keep_in_lds<C>(v, a, tile, t, lds, tw_lds);
+    if (ok) {
+      cf* y = a.out + (om.offset + (long long)sb * om.batch_stride);
+      for (int i = u; i < C::N; i += C::TPL) {
+        const int q = s0 + i;
+        if (i < o.w0 || i >= o.w0 + o.L || q >= o.plim) continue;      // outside the block's window, or beyond the last index the signal gives
+        const int m = q < 0 ? q + o.fN : q;                            // (the negative lags of a correlation sit at the top of the domain)
+        if (m < slo || m >= shi) continue;
+        cf r = cswap_if<true>(lds[lds_index<C>(line, i)]) * a.scale;
+        if (m < zlo || m >= zhi) r = cf{0.0f, 0.0f};
+        y[(long long)m * so] = r;
       }
     }
     __syncthreads();   // LDS is re-used by the next tile

@@ -158,6 +158,7 @@ PlannerOptions planner_options_from_env() {
   if (const char* s = std::getenv("MI355FFT_CONV_PAD")) o.conv_pad = std::atoi(s);
   if (const char* s = std::getenv("MI355FFT_RCONV_FUSED")) o.rconv_fused = std::atoi(s);
   if (const char* s = std::getenv("MI355FFT_RCONV_OLS")) o.rconv_ols = std::atoi(s);
+  if (const char* s = std::getenv("MI355FFT_CONV_OLS")) o.conv_ols = std::atoi(s);
   if (const char* s = std::getenv("MI355FFT_SOLO_MAX_KB")) { const int v = std::atoi(s); if (v >= 0) o.solo_max_kb = v; }
   if (const char* s = std::getenv("MI355FFT_SOLO_CAP_MB")) { const int v = std::atoi(s); if (v >= 1) o.solo_cap_mb = v; }
   if (const char* s = std::getenv("MI355FFT_XCD_SLOTS")) { const int v = std::atoi(s); if (v >= 0 && v <= 2) o.xcd_slots = v; }
@@ -1737,6 +1738,18 @@ void restage(PlanIR& ir, uint64_t in_stage, uint64_t out_stage, uint64_t kernel_
   ir.steps.swap(front);
 }
 
+// The block length the default rule (PlannerOptions::conv_ols == 1) gives to overlap-save on a complex line of lfN = shape + M - 1 logical points
+// and a kernel of M points; 0: the request keeps its earlier route.  Left alone: requests of at most 16384 points and kernels beyond 513 points (where a
+// 4096-point block returns less than 7/8 of its positions; not measured).  Measured (profiles/fftconv_cols_ab.log: 128 x 2^20 (*) {31, 255, 513}, K = 1 and 4,
+// 1024 x 100000 (*) 129, 128 x 700000 (*) 255 and two lines above 2^22, P = 512 .. 4096): every block length is 4.1-9.9x ahead of pad[..] fftconv[K] and
+// 2.4-3.2x ahead of fftconv-pipeline-view; the fastest P is the smallest power of two >= 8 (M - 1) from 2048 on (M = 31: 512, 1024 and 2048 within the
+// 3 % spread; M = 129: 2048 is 5 % ahead of 1024; M = 255: 2048; M = 513: 2048 and 4096 within 2 %)
+constexpr int64_t CONV_OLS_MIN_FN = 16384, CONV_OLS_MAX_KERNEL = 513;
+int64_t conv_ols_block(int64_t lfN, int64_t M) {
+  if (lfN <= CONV_OLS_MIN_FN || M > CONV_OLS_MAX_KERNEL) return 0;
+  return 8 * (M - 1) <= 2048 ? 2048 : 4096;
+}
+
 // y_k = IFFT( FFT(x) .* (conj?)FFT(h_k) ) / Nfft, cropped per boundary, written per output layout / lanes
 // (runtime/plans/fftconv.js:308-709, exec :1415-1712; reference semantics: src/utils/math.js:469-603)
 int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
@@ -1746,6 +1759,41 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
   const int64_t K = g.K, B = g.B, inN = g.inN;
   const int64_t *ks = g.ks, *fs = g.fs, zero[8] = {0};
   const bool zpad = d.zero_read.enabled || d.zero_write.enabled;
+  // ---- overlap-save: long complex lines, short kernels, one launch per kernel on blocks of P points -----------------------------
+  // Block j of a line holds signal indices [s0, s0 + P), s0 = j L - pre, pre = M - 1, and gives L = P - pre results (kern_lines.hpp
+  // fft_lines_conv_ols_kernel has the index map).  No padded domain, no transform of a whole line: 1 + K launches and K P 8 bytes of workspace
+  // for any length.  Strided lanes, channel-policy lanes, zeroPad and the crop ride the two address maps.  The switch 0 keeps the routes below
+  // for every request; a power of two 128 .. 4096 forces that block length on every request it fits (L >= 2); 1 is the rule of conv_ols_block
+  if (rank == 1 && g.linear && b.opt.conv_ols != 0 && b.opt.conv_lines && !b.opt.force_generic && g.lfN < ((int64_t)1 << 31) - 16384) {   // (the kernel's indices are 32-bit)
+    const int64_t M = ks[0], pre = M - 1, lfN = g.lfN;
+    int64_t P = 0;
+    if (b.opt.conv_ols > 1) { if (is_pow2(b.opt.conv_ols) && b.opt.conv_ols >= 128 && b.opt.conv_ols <= 4096) P = b.opt.conv_ols; }
+    else P = conv_ols_block(lfN, M);
+    const int64_t L = P - pre;
+    const int64_t nb = L >= 2 ? (lfN + L - 1) / L : 0, lines = B * nb;
+    const LineKernelMeta* om = (P && L >= 2 && lines < ((int64_t)1 << 31) - 64 && b.axis_mappable(P, 1, false)) ? find_line_kernel((int)P, false, false, false, false, 0) : nullptr;
+    if (om && om->lds_bytes > 0 && om->R1 > 1) {
+      const int64_t pd[1] = {P};
+      const PtrRef G = b.alloc_work((uint64_t)K * P * 8);
+      if (int rv = b.emit_axis_mapped(PtrRef(BUF_KERNEL, 0), G, P, 1, K, false, 1.0f, conv_kernel_map(g, pd, 1), Builder::dense_map(pd, 1), 0)) return rv;
+      const PtrRef tables = b.line_tables(*om);
+      const SideMap xm = conv_load_map(d, g, fs, 1);
+      const int64_t tiles = (lines + om->T - 1) / om->T;
+      for (int64_t k = 0; k < K; ++k) {
+        Step& st = b.push(ST_LINES);
+        st.variant = om->id;
+        st.p[LP_IN] = PtrRef(BUF_INPUT, 0); st.p[LP_OUT] = PtrRef(BUF_OUTPUT, 0); st.p[LP_TW] = tables; st.p[LP_MUL_SPECTRUM] = G.plus(k * P * 8);
+        st.i[LS_TILES] = tiles; st.i[LS_LINES] = lines; st.i[LS_IN_S] = 1; st.i[LS_IN_OUTER] = P; st.i[LS_OUT_S] = 1; st.i[LS_OUT_OUTER] = P;
+        st.i[LS_MODE] = LM_CONV_OLS; st.i[LS_MAPPED] = 1; st.i[LS_CONJ] = g.corr ? 1 : 0;
+        st.i[LS_OLS_FN] = lfN; st.i[LS_OLS_PLIM] = g.corr ? d.shape[0] : lfN; st.i[LS_OLS_NB] = nb; st.i[LS_OLS_L] = L; st.i[LS_OLS_W0] = g.corr ? 0 : pre; st.i[LS_OLS_PRE] = pre;
+        st.f[F_SCALE] = (float)(1.0 / (double)P);
+        st.imap = xm; st.omap = conv_store_map(d, g, fs, 1, k);
+        st.grid = b.lines_grid(*om, tiles);
+      }
+      b.ir.route += "lines-conv-ols[N=" + std::to_string(P) + ",L=" + std::to_string(L) + "] ";
+      return MI355FFT_OK;
+    }
+  }
   // Long rank-1 linear modes: the next power of two keeps the transforms off the Bluestein / mixed-radix routes (ConvGeom)
   if (b.opt.conv_pad && rank == 1 && g.linear && g.lfN > 16384 && g.lfN <= ((int64_t)1 << 22) && !is_pow2(g.lfN)) {
     int64_t P = 32768;

@@ -124,7 +124,8 @@ enum LineMode : int {
   LM_DCT2 = 5, LM_DST2 = 6,   // one-launch DCT-II / DST-II on the r2c kernel
   LM_DCT3 = 7, LM_DST3 = 8,   // one-launch DCT-III / DST-III on the c2r kernel
   LM_RCONV = 9,       // real fftconv line: r2c, product and c2r in one launch (fft_lines_rconv_kernel)
-  LM_RCONV_OLS = 10   // its overlap-save form (fft_lines_rconv_ols_kernel)
+  LM_RCONV_OLS = 10,  // its overlap-save form (fft_lines_rconv_ols_kernel)
+  LM_CONV_OLS = 11    // overlap-save on complex lines: forward FFT, product and inverse FFT of a block in one launch (fft_lines_conv_ols_kernel)
 };
 // Bluestein's two mapped launches: bits of i[LS_CHIRP_FLAGS] (LineArgs::fs_lo_mask)
 enum : unsigned { LINES_CHIRP = 1, LINES_CHIRP_SWAP = 2 };   // multiply by the chirp in p[LP_CHIRP]; inverse transform: the chirp's conjugate
@@ -138,8 +139,8 @@ enum LinesSlot {
   LS_MODE = 9,                               // LineMode
   LS_MAPPED = 10,                            // sides through Step::imap / omap
   LS_H16 = 11,                               // binary16 sides (f16-storage)
-  LS_CONJ = 12,                              // LM_RCONV, LM_RCONV_OLS: correlation
-  LS_RCONV_SPLIT = 13, LS_OLS_FN = 13,       // LM_RCONV: ConvGeom split / padD;  LM_RCONV_OLS: the block geometry (kern_lines.hpp RconvOls)
+  LS_CONJ = 12,                              // LM_RCONV, LM_RCONV_OLS, LM_CONV_OLS: correlation
+  LS_RCONV_SPLIT = 13, LS_OLS_FN = 13,       // LM_RCONV: ConvGeom split / padD;  LM_RCONV_OLS, LM_CONV_OLS: the block geometry (kern_lines.hpp RconvOls)
   LS_RCONV_PADD = 14, LS_OLS_PLIM = 14,
   LS_OLS_NB = 15, LS_OLS_L = 16, LS_OLS_W0 = 17, LS_OLS_PRE = 18,
   LS_LAST = LS_OLS_PRE
@@ -147,7 +148,7 @@ enum LinesSlot {
 static_assert(LS_LAST < STEP_INTS, "ST_LINES slots");
 enum LinesPtr {
   LP_IN = 0, LP_OUT = 1, LP_TW = 2,
-  LP_TW_LO = 3, LP_MUL_SPECTRUM = 3,         // four-step / split LO roots (LM_RCONV*: LO and HI in one table); LM_MUL: the spectrum multiplied in
+  LP_TW_LO = 3, LP_MUL_SPECTRUM = 3,         // four-step / split LO roots (LM_RCONV*: LO and HI in one table); LM_MUL, LM_CONV_OLS: the spectrum multiplied in
   LP_TW_HI = 4, LP_CHIRP = 4, LP_RCONV_SPECTRUM = 4,   // HI roots; Bluestein: the chirp; LM_RCONV*: the packed kernel spectrum
   LP_LAST = LP_RCONV_SPECTRUM
 };
@@ -301,6 +302,14 @@ struct PlannerOptions {
                                        // real fftconv, rank 1, linear boundaries: overlap-save on blocks of P points, one launch per kernel whatever the line's length
                                        // (kern_lines.hpp fft_lines_rconv_ols_kernel); 1: where measured ahead (plan.cpp build_fftconv_real); 0: never; a power of two
                                        // 128..8192: that block length on every request it fits (tests and measurement).  rconv_fused = 0 / 2 come first
+#ifdef MI355_HOST_EMU
+  int conv_ols = std::getenv("MI355_EMU_CONV_OLS") ? std::atoi(std::getenv("MI355_EMU_CONV_OLS")) : 1;
+#else
+  int conv_ols = 1;
+#endif
+                                       // fftconv, rank 1, linear boundaries: overlap-save on blocks of P complex points, one launch per kernel whatever the line's length
+                                       // (kern_lines.hpp fft_lines_conv_ols_kernel); 1: where measured ahead (plan.cpp build_fftconv); 0: never; a power of two
+                                       // 128..4096: that block length on every request it fits (tests and measurement).  conv_lines = 0 and force_generic come first
   int conv_lines = 1;                  // fftconv: kernel-spectrum product fused behind the forward line FFT (1-D, power-of-two FFT length <= max_line)
   int trig_fused = 1;                  // dct2 / dst2 of dense lines (half length a line-kernel size): permutation + real FFT + phase in one launch
   int trig_real = 1;                   // dct2/dst2/dct3/dst3 along a dense even axis through a real FFT of length N (kern_trig.hpp)
