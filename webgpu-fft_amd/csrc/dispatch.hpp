@@ -21,6 +21,7 @@
 #include "kern_xcd_real.hpp"
 #include "kern_regtile.hpp"
 #include "kern_xcd_res.hpp"
+#include "kern_tiles.hpp"
 #include "plan.hpp"
 
 namespace mi355 {
@@ -96,6 +97,39 @@ template <class L> bool launch_lines_conv_ols(int id, const RconvOlsArgs& a, uns
 #undef LINE_PASS_A
 #undef LINE_PASS_B
 #undef LINE_COL_RAGGED
+  (void)cur; (void)a; (void)grid; (void)l;
+  return false;
+}
+#endif
+
+// overlap-save on rank-2 complex tiles (kern_tiles.hpp fft_tiles_conv_ols_kernel, routes tiles-spectrum / tiles-conv-ols): the instances of
+// MI355_TILE_KERNEL_LIST, in a unit of their own (tiles_conv_ols.hip).  `id`: position in that list (plan.cpp find_tile_kernel)
+template <class L> bool launch_tiles_conv_ols(int id, const TilesArgs& a, unsigned grid, L& l);
+// its argument block from an ST_LINES step of mode LM_TILES_CONV_OLS / LM_TILES_SPECTRUM: every geometry slot holds axis 0 in its low 32 bits and axis 1 in its high
+inline TilesArgs tiles_args_of(const Step& s, void* const ptr[STEP_PTRS]) {
+  TilesArgs ta{};
+  ta.in = (const cf*)ptr[LP_IN]; ta.out = (cf*)ptr[LP_OUT]; ta.tw = (const cf*)ptr[LP_TW]; ta.spectrum = (const cf*)ptr[LP_MUL_SPECTRUM];
+  ta.num_tiles = s.i[LS_TILES]; ta.scale = s.f[F_SCALE];
+  ta.conj = (int)s.i[LS_CONJ]; ta.spectrum_only = s.i[LS_MODE] == LM_TILES_SPECTRUM;
+  for (int x = 0; x < 2; ++x) {
+    const auto half = [x](int64_t v) { return (int)(uint32_t)((uint64_t)v >> (32 * x)); };
+    ta.ax[x] = TileAxis{half(s.i[LS_OLS_FN]), half(s.i[LS_OLS_PLIM]), half(s.i[LS_OLS_NB]), half(s.i[LS_OLS_L]), half(s.i[LS_OLS_W0]), half(s.i[LS_OLS_PRE])};
+  }
+  ta.imap = s.imap; ta.omap = s.omap;
+  return ta;
+}
+#if defined(MI355_TILES_DEFINE_INSTANCES) || defined(MI355_HOST_EMU)
+template <class L> bool launch_tiles_conv_ols(int id, const TilesArgs& a, unsigned grid, L& l) {
+  int cur = 0;
+#define X(P, R0, R1, TH)                                                                              \
+  if (id == cur) {                                                                                    \
+    using C = TileCfg<P, R0, R1, TH>;                                                                 \
+    l.launch(fft_tiles_conv_ols_kernel<C>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a);    \
+    return true;                                                                                      \
+  }                                                                                                   \
+  ++cur;
+  MI355_TILE_KERNEL_LIST(X)
+#undef X
   (void)cur; (void)a; (void)grid; (void)l;
   return false;
 }
@@ -388,6 +422,7 @@ bool dispatch_step(const Step& s, void* const ptr[STEP_PTRS], L& l, LinesFn&& li
         oa.o.fN = (int)s.i[LS_OLS_FN]; oa.o.plim = (int)s.i[LS_OLS_PLIM]; oa.o.nb = (int)s.i[LS_OLS_NB]; oa.o.L = (int)s.i[LS_OLS_L]; oa.o.w0 = (int)s.i[LS_OLS_W0]; oa.o.pre = (int)s.i[LS_OLS_PRE];
         return launch_lines_conv_ols(s.variant, oa, s.grid, l);
       }
+      if (a.real_mode == LM_TILES_CONV_OLS || a.real_mode == LM_TILES_SPECTRUM) return launch_tiles_conv_ols(s.variant, tiles_args_of(s, ptr), s.grid, l);   // rank-2 overlap-save tiles
       const LineKernelMeta& m = line_kernel_registry()[(size_t)s.variant];
       return lines_fn(family_of_line_kernel(m), s.variant, a, s.grid);
     }

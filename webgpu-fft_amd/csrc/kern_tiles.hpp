@@ -1,0 +1,246 @@
+// kern_tiles.hpp — overlap-save on rank-2 complex tiles (type MI355FFT_FFTCONV, route tiles-conv-ols): forward 2-D FFT, product with one kernel
+// spectrum and inverse 2-D FFT of a P x P tile without leaving LDS.  The 2-D form of kern_lines.hpp fft_lines_conv_ols_kernel: its block
+// geometry once per axis a (axis 0 fastest, as everywhere in the planner):
+//   M_a = kernelShape[a], pre_a = M_a - 1, L_a = P - pre_a, fN_a = shape[a] + M_a - 1, nb_a = ceil(fN_a / L_a)
+//   tile (j0, j1) of image b holds signal indices [s0_a, s0_a + P), s0_a = j_a L_a - pre_a, and gives the L0 x L1 results of its window
+//   [w0_a, w0_a + L_a): w0_a = pre_a (convolution) or 0 (correlation); q_a = s0_a + i_a < plim_a (shape[a] when correlating, else fN_a);
+//   logical index m_a = q_a < 0 ? q_a + fN_a : q_a (the negative lags of a correlation sit at the top of each axis of the domain)
+//
+// One workgroup owns a tile.  A pass transforms the P lines of one axis with the two Stockham stages of kern_lines.hpp (butterflies: radix.hpp);
+// in BOTH passes lane -> line (line = t % P, butterfly u = t / P), so that a wave's 64 lanes sit on 64 neighbouring lines:
+//   column pass (axis 1, the line is column i0 = line): element idx of the line at lds[idx * PITCH + line] — consecutive lanes, consecutive
+//                addresses: conflict-free whatever the stage's index pattern, and in global memory runs of 64 elements along axis 0
+//   row pass    (axis 0, the line is row i1 = line):    lds[line * PITCH + idx] — lanes PITCH apart.  PITCH = P + 1 is odd, so the 32 lanes a
+//                ds_read_b64 / ds_write_b64 serves at once fall on 32 different bank pairs: conflict-free as well
+// Forward runs columns then rows, the inverse rows then columns: the tile's first stage loads straight from global memory and its last stage
+// stores straight to it, both contiguous along axis 0, and no load or store sweep over LDS exists.
+//   load    : 8-byte loads through imap; on both axes its bounds are moved by the tile's origin ([lo_a - s0_a, hi_a - s0_a) cut to [0, P)), zero
+//             elsewhere: the embed and zeroPad.read are the map's predicates, strided lanes its strides.  Nothing outside [lo, hi) is dereferenced
+//   product : a lane reads the bins its first inverse stage starts from, multiplies them by the spectrum (conjugated when correlating) and swaps
+//             re and im, so that the inverse re-uses the forward stages: no product pass over LDS.  The spectrum is read per tile (cache hits), not
+//             kept in registers (profiles/fftconv_cols_ab.log: that cost a workgroup per CU in 1-D).  Its order is the tile's own: bin (k0, k1) at
+//             [k0 * P + k1], which the row pass reads with consecutive lanes; LM_TILES_SPECTRUM is this kernel's forward half storing that order
+//   store   : positions inside both windows, then the crop [lo_a, hi_a) of omap, zeroPad.write (zlo, zhi) and the output lane; scale 1/P^2
+// Element indices are 32-bit (the planner keeps every fN_a and the number of tiles below 2^31 - 16384); buffer offsets are formed in 64 bits
+#pragma once
+#include "platform.hpp"
+#include "radix.hpp"
+#include "plan.hpp"
+
+// a value the optimizer must take as new at this point: comparisons of a lane's positions with it stay inside the tile loop instead of being hoisted
+// out of it as one 64-bit lane mask per position (32 such masks: 64 SGPRs, spilt)
+#ifdef MI355_HOST_EMU
+#define MI_TILE_OPAQUE(x) do { } while (0)
+#define MI_TILE_OPAQUE_LANE(x) do { } while (0)
+#else
+#define MI_TILE_OPAQUE(x) asm volatile("" : "+s"(x))
+#define MI_TILE_OPAQUE_LANE(x) asm volatile("" : "+v"(x))     // the same for a lane's value: its 16 positions u + d are formed where they are used, not held in 16 VGPRs
+#endif
+
+namespace mi355 {
+
+struct TileAxis { int fN, plim, nb, L, w0, pre; };   // RconvOls (kern_lines.hpp) of one axis
+struct TilesArgs {
+  const cf* in;
+  cf* out;
+  const cf* tw;         // stage-1 roots [R1 - 1][R0] of order P (the table of a line kernel of P = R0 R1 points)
+  const cf* spectrum;   // the kernel spectrum on P x P, bin (k0, k1) at [k0 * P + k1]
+  long long num_tiles;
+  float scale;
+  int conj;             // correlation: the spectrum's conjugate
+  int spectrum_only;    // LM_TILES_SPECTRUM: forward half only; tile k is kernel k, its spectrum stored dense at out + k P^2
+  TileAxis ax[2];
+  SideMap imap, omap;
+};
+
+template <int P_, int R0_, int R1_, int THREADS_>
+struct TileCfg {
+  static constexpr int P = P_, R0 = R0_, R1 = R1_, THREADS = THREADS_;
+  static_assert(R0 * R1 == P, "radix product");
+  static_assert(THREADS % P == 0 && THREADS <= 1024, "a thread stays on one line");
+  static constexpr int TPL = THREADS / P;           // threads per line
+  static constexpr int E = P / TPL;                 // complex values per thread
+  static_assert(E % R0 == 0 && E % R1 == 0, "whole butterflies per thread");
+  static constexpr int PITCH = P + 1;
+  static constexpr int DATA_ELEMS = P * PITCH, TW_ELEMS = (R1 - 1) * R0;
+  static constexpr int LDS_BYTES = tile_kernel_lds_bytes(P, R0, R1);
+  static_assert(LDS_BYTES == (DATA_ELEMS + TW_ELEMS) * 8 && LDS_BYTES <= 160 * 1024, "tile does not fit LDS");
+  // waves per SIMD when a CU holds the workgroups its 160 KB of LDS take (four of P = 64, one of P = 128: 16 waves, 4 a SIMD): the register budget
+  // P = 128: the 16 positions u + d of a lane's loads and of its stores are formed again in every tile (MI_TILE_OPAQUE_LANE) instead of living in VGPRs across
+  // the kernel: 124 VGPRs and no scratch where holding them spilt 8; P = 64 fits its 128 VGPRs holding them and spilt 4 without
+  static constexpr bool REFORM_POSITIONS = P >= 128;
+  static constexpr int WAVES_PER_SIMD = ((160 * 1024) / LDS_BYTES) * (THREADS / 64) / 4;
+};
+
+template <class C, int S> struct TileStage {
+  static constexpr int R = S == 0 ? C::R0 : C::R1;
+  static constexpr int NSP = S == 0 ? 1 : C::R0;
+  static constexpr int NB = C::E / R;               // butterflies per thread
+};
+
+template <class C, bool COLS> MI_DEV int tile_index(int line, int idx) { return COLS ? idx * C::PITCH + line : line * C::PITCH + idx; }
+
+// the inputs of stage S of this thread's butterflies, from LDS
+template <class C, int S, bool COLS> MI_DEV void tile_stage_read(cf (&v)[C::E], const cf* lds, int line, int u) {
+  using I = TileStage<C, S>;
+#pragma unroll
+  for (int b = 0; b < I::NB; ++b)
+#pragma unroll
+    for (int q = 0; q < I::R; ++q) v[b * I::R + q] = lds[tile_index<C, COLS>(line, u + b * C::TPL + q * (C::P / I::R))];
+}
+// roots and butterflies of stage S in registers: v[b R + q] becomes output q of butterfly b
+template <class C, int S> MI_DEV void tile_stage_compute(cf (&v)[C::E], const cf* tw_lds, int u) {
+  using I = TileStage<C, S>;
+#pragma unroll
+  for (int b = 0; b < I::NB; ++b) {
+    cf w[I::R];
+#pragma unroll
+    for (int q = 0; q < I::R; ++q) w[q] = v[b * I::R + q];
+    if constexpr (S > 0) {
+      const int k = (u + b * C::TPL) % I::NSP;
+#pragma unroll
+      for (int q = 1; q < I::R; ++q) w[q] = cmul(w[q], tw_lds[(q - 1) * I::NSP + k]);
+    }
+    fft_radix<I::R>(w);
+#pragma unroll
+    for (int q = 0; q < I::R; ++q) v[b * I::R + q] = w[q];
+  }
+}
+// the index along the line of output q of butterfly b (Stockham autosort: natural order behind the last stage)
+template <class C, int S> MI_DEV int tile_stage_out(int u, int b, int q) {
+  using I = TileStage<C, S>;
+  const int j = u + b * C::TPL;
+  return (j / I::NSP) * (I::NSP * I::R) + j % I::NSP + q * I::NSP;
+}
+template <class C, int S, bool COLS> MI_DEV void tile_stage_write(const cf (&v)[C::E], cf* lds, int line, int u) {
+  using I = TileStage<C, S>;
+#pragma unroll
+  for (int b = 0; b < I::NB; ++b)
+#pragma unroll
+    for (int q = 0; q < I::R; ++q) lds[tile_index<C, COLS>(line, tile_stage_out<C, S>(u, b, q))] = v[b * I::R + q];
+}
+
+template <class C>
+__global__ void __launch_bounds__(C::THREADS, C::WAVES_PER_SIMD) fft_tiles_conv_ols_kernel(const TilesArgs a) {
+  MI_SMEM_DECL(smem);
+  cf* lds = reinterpret_cast<cf*>(smem);
+  cf* tw_lds = lds + C::DATA_ELEMS;
+  const int t = threadIdx.x;
+  for (int i = t; i < C::TW_ELEMS; i += C::THREADS) tw_lds[i] = a.tw[i];
+  __syncthreads();
+  const int line = t % C::P, u = t / C::P;
+  using I0 = TileStage<C, 0>;
+  using I1 = TileStage<C, 1>;
+  const SideMap& im = a.imap;
+  const SideMap& om = a.omap;
+  const TileAxis& A0 = a.ax[0];
+  const TileAxis& A1 = a.ax[1];
+  const unsigned per_image = (unsigned)A0.nb * (unsigned)A1.nb;
+  for (long long tile = blockIdx.x; tile < a.num_tiles; tile += gridDim.x) {
+    const unsigned sb = (unsigned)tile / per_image, r = (unsigned)tile - sb * per_image, j1 = r / (unsigned)A0.nb, j0 = r - j1 * (unsigned)A0.nb;
+    const int s00 = (int)j0 * A0.L - A0.pre, s01 = (int)j1 * A1.L - A1.pre;      // the tile's first signal index on each axis
+    cf v[C::E];
+    // ---- forward, columns: stage 0 from global memory (this lane: column i0 = line) ----
+    {
+      const int q0 = s00 + line;
+      const bool ok0 = q0 >= im.lo[0] && q0 < im.hi[0];
+      const cf* x = a.in + (im.offset + (long long)sb * im.batch_stride + (long long)q0 * im.stride[0]);   // (dereferenced inside [lo, hi) only)
+      const int l1 = im.lo[1] - s01, h1 = im.hi[1] - s01;
+      const int lo1 = l1 < 0 ? 0 : l1, hi1 = h1 > C::P ? C::P : h1;               // the tile's share of [lo, hi) on axis 1
+      const long long s1 = im.stride[1];
+      int ul = u;
+      if constexpr (C::REFORM_POSITIONS) MI_TILE_OPAQUE_LANE(ul);
+#pragma unroll
+      for (int b = 0; b < I0::NB; ++b) {
+#pragma unroll
+        for (int q = 0; q < I0::R; ++q) {
+          const int i1 = ul + b * C::TPL + q * (C::P / I0::R);
+          cf xv = {0.0f, 0.0f};
+          if (ok0 && i1 >= lo1 && i1 < hi1) xv = x[(long long)(s01 + i1) * s1];
+          v[b * I0::R + q] = xv;
+        }
+      }
+    }
+    tile_stage_compute<C, 0>(v, tw_lds, u);
+    tile_stage_write<C, 0, true>(v, lds, line, u);
+    __syncthreads();
+    tile_stage_read<C, 1, true>(v, lds, line, u);
+    __syncthreads();
+    tile_stage_compute<C, 1>(v, tw_lds, u);
+    tile_stage_write<C, 1, true>(v, lds, line, u);
+    __syncthreads();
+    // ---- forward, rows (this lane: row i1 = line) ----
+    tile_stage_read<C, 0, false>(v, lds, line, u);
+    __syncthreads();
+    tile_stage_compute<C, 0>(v, tw_lds, u);
+    tile_stage_write<C, 0, false>(v, lds, line, u);
+    __syncthreads();
+    tile_stage_read<C, 1, false>(v, lds, line, u);
+    __syncthreads();
+    tile_stage_compute<C, 1>(v, tw_lds, u);
+    tile_stage_write<C, 1, false>(v, lds, line, u);
+    __syncthreads();
+    if (a.spectrum_only) {      // the spectrum as the product reads it: bin (k0, k1 = line) at [k0 * P + k1]
+      cf* g = a.out + (long long)sb * (C::P * C::P);
+      for (int k0 = u; k0 < C::P; k0 += C::TPL) g[k0 * C::P + line] = lds[tile_index<C, false>(line, k0)];
+      __syncthreads();          // LDS is re-used by the next tile
+      continue;
+    }
+    // ---- product in the loads of the inverse's first stage; inverse, rows ----
+#pragma unroll
+    for (int b = 0; b < I0::NB; ++b) {
+#pragma unroll
+      for (int q = 0; q < I0::R; ++q) {
+        const int k0 = u + b * C::TPL + q * (C::P / I0::R);
+        cf h = a.spectrum[k0 * C::P + line];
+        if (a.conj) h.y = -h.y;
+        v[b * I0::R + q] = cswap(cmul(lds[tile_index<C, false>(line, k0)], h));
+      }
+    }
+    __syncthreads();
+    tile_stage_compute<C, 0>(v, tw_lds, u);
+    tile_stage_write<C, 0, false>(v, lds, line, u);
+    __syncthreads();
+    tile_stage_read<C, 1, false>(v, lds, line, u);
+    __syncthreads();
+    tile_stage_compute<C, 1>(v, tw_lds, u);
+    tile_stage_write<C, 1, false>(v, lds, line, u);
+    __syncthreads();
+    // ---- inverse, columns: the last stage stores to global memory ----
+    tile_stage_read<C, 0, true>(v, lds, line, u);
+    __syncthreads();
+    tile_stage_compute<C, 0>(v, tw_lds, u);
+    tile_stage_write<C, 0, true>(v, lds, line, u);
+    __syncthreads();
+    tile_stage_read<C, 1, true>(v, lds, line, u);
+    __syncthreads();            // everyone has its inputs: LDS is free for the next tile
+    tile_stage_compute<C, 1>(v, tw_lds, u);
+    {
+      const int q0 = s00 + line;
+      const int m0 = q0 < 0 ? q0 + A0.fN : q0;                                   // (the negative lags of a correlation sit at the top of the domain)
+      const bool ok0 = line >= A0.w0 && line < A0.w0 + A0.L && q0 < A0.plim && m0 >= om.lo[0] && m0 < om.hi[0];
+      const bool z0 = m0 < om.zlo[0] || m0 >= om.zhi[0];
+      cf* y = a.out + (om.offset + (long long)sb * om.batch_stride + (long long)m0 * om.stride[0]);   // (dereferenced inside the crop only)
+      const long long s1 = om.stride[1];
+      int wlo = A1.w0, us = u;
+      MI_TILE_OPAQUE(wlo);
+      if constexpr (C::REFORM_POSITIONS) MI_TILE_OPAQUE_LANE(us);
+      const int wend = A1.w0 + A1.L, pend = A1.plim - s01, whi = wend < pend ? wend : pend;   // the window, cut at the last index the signal gives
+#pragma unroll
+      for (int b = 0; b < I1::NB; ++b) {
+#pragma unroll
+        for (int q = 0; q < I1::R; ++q) {
+          const int i1 = tile_stage_out<C, 1>(us, b, q), q1 = s01 + i1;
+          if (!ok0 || i1 < wlo || i1 >= whi) continue;
+          const int m1 = q1 < 0 ? q1 + A1.fN : q1;
+          if (m1 < om.lo[1] || m1 >= om.hi[1]) continue;
+          cf r = cswap(v[b * I1::R + q]) * a.scale;
+          if (z0 || m1 < om.zlo[1] || m1 >= om.zhi[1]) r = cf{0.0f, 0.0f};
+          y[(long long)m1 * s1] = r;
+        }
+      }
+    }
+  }
+}
+
+}  // namespace mi355

@@ -87,6 +87,19 @@ const std::vector<ConvKernelMeta>& conv_kernel_registry() {
   return reg;
 }
 
+const TileKernelMeta* find_tile_kernel(int P) {
+  static const std::vector<TileKernelMeta> reg = [] {
+    std::vector<TileKernelMeta> r;
+    int id = 0;
+#define X(P, R0, R1, TH) r.push_back(TileKernelMeta{id++, P, R0, R1, TH, tile_kernel_lds_bytes(P, R0, R1)});
+    MI355_TILE_KERNEL_LIST(X)
+#undef X
+    return r;
+  }();
+  for (const auto& m : reg) if (m.P == P) return &m;
+  return nullptr;
+}
+
 namespace {
 // launch shape of an XCD-fused instance: host copies of the Cfg constants its case in dispatch.hpp launches with (kern_xcd.hpp
 // XcdFusedCfg, kern_regtile.hpp), checked against them by tests/emu (emu_check_xcd_registry)
@@ -159,6 +172,7 @@ PlannerOptions planner_options_from_env() {
   if (const char* s = std::getenv("MI355FFT_RCONV_FUSED")) o.rconv_fused = std::atoi(s);
   if (const char* s = std::getenv("MI355FFT_RCONV_OLS")) o.rconv_ols = std::atoi(s);
   if (const char* s = std::getenv("MI355FFT_CONV_OLS")) o.conv_ols = std::atoi(s);
+  if (const char* s = std::getenv("MI355FFT_CONV_OLS2D")) o.conv_ols2d = std::atoi(s);
   if (const char* s = std::getenv("MI355FFT_SOLO_MAX_KB")) { const int v = std::atoi(s); if (v >= 0) o.solo_max_kb = v; }
   if (const char* s = std::getenv("MI355FFT_SOLO_CAP_MB")) { const int v = std::atoi(s); if (v >= 1) o.solo_cap_mb = v; }
   if (const char* s = std::getenv("MI355FFT_XCD_SLOTS")) { const int v = std::atoi(s); if (v >= 0 && v <= 2) o.xcd_slots = v; }
@@ -1750,6 +1764,22 @@ int64_t conv_ols_block(int64_t lfN, int64_t M) {
   return 8 * (M - 1) <= 2048 ? 2048 : 4096;
 }
 
+// The tile edge the default rule (PlannerOptions::conv_ols2d == 1) gives to overlap-save on a rank-2 image of fN0 x fN1 = shape + M - 1 logical points and a
+// kernel of M0 x M1 points; 0: the request keeps its earlier route.  Left alone: domains of at most 16384 points and axes below 64 points (the small requests
+// whose routes the tests pin; a tile would be mostly padding) and kernels beyond 33 points on an axis (a 128-point tile returns less than 3/4 of its
+// positions per axis; not measured).
+// Measured (profiles/fftconv_tiles_ab.log: 8 x 1024^2 (*) 9x9, 4 x 512^2 (*) 5x5, 3 x 1920x1080 (*) 17x17, 4096^2 (*) 33x33 valid, 16 x 256^2 (*) 3x3 and
+// 8 x 1016^2 (*) 9x9 full, K = 1 and 4, both tiles; spread between repeated samples <= 3.2 %): both tiles are 9-44x ahead of the Bluestein / mixed-radix
+// plans and 2.0-3.4x ahead of the power-of-two domain 1024^2 of the linear-full request (lines-mapped + columns: 0.206 ms against 0.061), so no class is
+// excluded.  P = 64 is 29-68 % ahead of P = 128 up to 17 points (9x9: 138 against 107 G points/s; 17x17: 109 against 81; 3x3 and 5x5: 52 against 31);
+// at 33 points P = 128 is 47-51 % ahead (95-102 against 65-68).  Kernels of 18 .. 32 points were not measured: they take the larger tile
+constexpr int64_t CONV_TILES_MIN_POINTS = 16384, CONV_TILES_MIN_AXIS = 64, CONV_TILES_MAX_KERNEL = 33, CONV_TILES_P64_MAX_KERNEL = 17;
+int64_t conv_tiles_block(int64_t fN0, int64_t fN1, int64_t M0, int64_t M1) {
+  const int64_t M = std::max(M0, M1);
+  if (fN0 * fN1 <= CONV_TILES_MIN_POINTS || fN0 < CONV_TILES_MIN_AXIS || fN1 < CONV_TILES_MIN_AXIS || M > CONV_TILES_MAX_KERNEL) return 0;
+  return M <= CONV_TILES_P64_MAX_KERNEL ? 64 : 128;
+}
+
 // y_k = IFFT( FFT(x) .* (conj?)FFT(h_k) ) / Nfft, cropped per boundary, written per output layout / lanes
 // (runtime/plans/fftconv.js:308-709, exec :1415-1712; reference semantics: src/utils/math.js:469-603)
 int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
@@ -1791,6 +1821,60 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
         st.grid = b.lines_grid(*om, tiles);
       }
       b.ir.route += "lines-conv-ols[N=" + std::to_string(P) + ",L=" + std::to_string(L) + "] ";
+      return MI355FFT_OK;
+    }
+  }
+  // ---- overlap-save in two dimensions: images, small kernels, one launch per kernel on P x P tiles ---------------------------------
+  // Tile (j0, j1) of an image holds signal indices [s0_a, s0_a + P) on axis a, s0_a = j_a L_a - pre_a, pre_a = M_a - 1, and gives L0 x L1 results,
+  // L_a = P - pre_a (kern_tiles.hpp has the index map).  No exact-length domain, no Bluestein or column launch: 1 + K launches and K P^2 8 bytes of
+  // workspace for any image.  The first launch is the tile kernel's forward half on the kernels, zero-padded into a tile by conv_kernel_map: the K
+  // spectra in the order the product reads them.  Strided lanes, channel-policy lanes, zeroPad and the crop ride the two address maps.  The switch 0
+  // keeps the routes below for every request; 64 or 128 forces that tile on every request it fits (L_a >= 2); 1 is the rule of conv_tiles_block
+  if (rank == 2 && g.linear && b.opt.conv_ols2d != 0 && b.opt.conv_lines && !b.opt.force_generic && b.opt.fuse_views &&
+      fs[0] < ((int64_t)1 << 31) - 16384 && fs[1] < ((int64_t)1 << 31) - 16384) {   // (the kernel's indices are 32-bit)
+    int64_t P = 0;
+    if (b.opt.conv_ols2d > 1) { if (b.opt.conv_ols2d == 64 || b.opt.conv_ols2d == 128) P = b.opt.conv_ols2d; }
+    else P = conv_tiles_block(fs[0], fs[1], ks[0], ks[1]);
+    const TileKernelMeta* tm = P ? find_tile_kernel((int)P) : nullptr;
+    const int64_t pre[2] = {ks[0] - 1, ks[1] - 1}, L[2] = {P - pre[0], P - pre[1]};
+    const int64_t nb[2] = {L[0] >= 2 ? (fs[0] + L[0] - 1) / L[0] : 0, L[1] >= 2 ? (fs[1] + L[1] - 1) / L[1] : 0};
+    const bool fits = tm && L[0] >= 2 && L[1] >= 2 && nb[0] * nb[1] < ((int64_t)1 << 31) - 16384 && B * nb[0] * nb[1] < ((int64_t)1 << 31) - 16384;
+    if (fits) {
+      const int64_t pd[2] = {P, P}, tiles = B * nb[0] * nb[1];
+      const PtrRef G = b.alloc_work((uint64_t)K * P * P * 8);
+      std::vector<float2h> roots;
+      for (int q = 1; q < tm->R1; ++q) for (int k = 0; k < tm->R0; ++k) roots.push_back(root_of_unity((int64_t)q * k, P));
+      const PtrRef tables = b.add_table(roots);
+      const auto both = [](int64_t a0, int64_t a1) { return (int64_t)((uint64_t)(uint32_t)a0 | ((uint64_t)(uint32_t)a1 << 32)); };
+      int64_t per_cu = std::min<int64_t>((160 * 1024) / tm->lds_bytes, 2048 / tm->threads);
+      per_cu = std::max<int64_t>(per_cu, 1);
+      const auto push = [&](LineMode mode, PtrRef src, PtrRef dst, int64_t count) -> Step& {
+        Step& st = b.push(ST_LINES);
+        st.variant = tm->id;
+        st.p[LP_IN] = src; st.p[LP_OUT] = dst; st.p[LP_TW] = tables;
+        st.i[LS_TILES] = count; st.i[LS_LINES] = count; st.i[LS_IN_S] = 1; st.i[LS_IN_OUTER] = P; st.i[LS_OUT_S] = 1; st.i[LS_OUT_OUTER] = P;
+        st.i[LS_MODE] = mode; st.i[LS_MAPPED] = 1;
+        st.grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(count, per_cu * b.opt.compute_units));
+        return st;
+      };
+      {   // the K kernel spectra: one tile a kernel, no overlap
+        Step& st = push(LM_TILES_SPECTRUM, PtrRef(BUF_KERNEL, 0), G, K);
+        st.i[LS_OLS_FN] = both(P, P); st.i[LS_OLS_PLIM] = both(P, P); st.i[LS_OLS_NB] = both(1, 1); st.i[LS_OLS_L] = both(P, P);
+        st.imap = conv_kernel_map(g, pd, 2); st.omap = Builder::dense_map(pd, 2);
+        b.ir.route += "tiles-spectrum[N=" + std::to_string(P) + "x" + std::to_string(P) + "] ";
+      }
+      const SideMap xm = conv_load_map(d, g, fs, 2);
+      for (int64_t k = 0; k < K; ++k) {
+        Step& st = push(LM_TILES_CONV_OLS, PtrRef(BUF_INPUT, 0), PtrRef(BUF_OUTPUT, 0), tiles);
+        st.p[LP_MUL_SPECTRUM] = G.plus(k * P * P * 8);
+        st.i[LS_CONJ] = g.corr ? 1 : 0;
+        st.i[LS_OLS_FN] = both(fs[0], fs[1]); st.i[LS_OLS_PLIM] = g.corr ? both(d.shape[0], d.shape[1]) : both(fs[0], fs[1]);
+        st.i[LS_OLS_NB] = both(nb[0], nb[1]); st.i[LS_OLS_L] = both(L[0], L[1]);
+        st.i[LS_OLS_W0] = g.corr ? 0 : both(pre[0], pre[1]); st.i[LS_OLS_PRE] = both(pre[0], pre[1]);
+        st.f[F_SCALE] = (float)(1.0 / (double)(P * P));
+        st.imap = xm; st.omap = conv_store_map(d, g, fs, 2, k);
+      }
+      b.ir.route += "tiles-conv-ols[N=" + std::to_string(P) + "x" + std::to_string(P) + ",L=" + std::to_string(L[0]) + "x" + std::to_string(L[1]) + "] ";
       return MI355FFT_OK;
     }
   }
