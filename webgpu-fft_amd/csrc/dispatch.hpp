@@ -105,12 +105,14 @@ template <class L> bool launch_lines_conv_ols(int id, const RconvOlsArgs& a, uns
 // overlap-save on rank-2 complex tiles (kern_tiles.hpp fft_tiles_conv_ols_kernel, routes tiles-spectrum / tiles-conv-ols): the instances of
 // MI355_TILE_KERNEL_LIST, in a unit of their own (tiles_conv_ols.hip).  `id`: position in that list (plan.cpp find_tile_kernel)
 template <class L> bool launch_tiles_conv_ols(int id, const TilesArgs& a, unsigned grid, L& l);
-// its argument block from an ST_LINES step of mode LM_TILES_CONV_OLS / LM_TILES_SPECTRUM: every geometry slot holds axis 0 in its low 32 bits and axis 1 in its high
+// the real form (fft_tiles_conv_ols_kernel on RTileCfg, routes tiles-rspectrum / tiles-rconv-ols): the same list, in a unit of its own (tiles_rconv_ols.hip)
+template <class L> bool launch_tiles_rconv_ols(int id, const TilesArgs& a, unsigned grid, L& l);
+// its argument block from an ST_LINES step of mode LM_TILES_CONV_OLS / LM_TILES_SPECTRUM (and their real forms): every geometry slot holds axis 0 in its low 32 bits and axis 1 in its high
 inline TilesArgs tiles_args_of(const Step& s, void* const ptr[STEP_PTRS]) {
   TilesArgs ta{};
   ta.in = (const cf*)ptr[LP_IN]; ta.out = (cf*)ptr[LP_OUT]; ta.tw = (const cf*)ptr[LP_TW]; ta.spectrum = (const cf*)ptr[LP_MUL_SPECTRUM];
   ta.num_tiles = s.i[LS_TILES]; ta.scale = s.f[F_SCALE];
-  ta.conj = (int)s.i[LS_CONJ]; ta.spectrum_only = s.i[LS_MODE] == LM_TILES_SPECTRUM;
+  ta.conj = (int)s.i[LS_CONJ]; ta.spectrum_only = s.i[LS_MODE] == LM_TILES_SPECTRUM || s.i[LS_MODE] == LM_TILES_RSPECTRUM;
   for (int x = 0; x < 2; ++x) {
     const auto half = [x](int64_t v) { return (int)(uint32_t)((uint64_t)v >> (32 * x)); };
     ta.ax[x] = TileAxis{half(s.i[LS_OLS_FN]), half(s.i[LS_OLS_PLIM]), half(s.i[LS_OLS_NB]), half(s.i[LS_OLS_L]), half(s.i[LS_OLS_W0]), half(s.i[LS_OLS_PRE])};
@@ -124,6 +126,23 @@ template <class L> bool launch_tiles_conv_ols(int id, const TilesArgs& a, unsign
 #define X(P, R0, R1, TH)                                                                              \
   if (id == cur) {                                                                                    \
     using C = TileCfg<P, R0, R1, TH>;                                                                 \
+    l.launch(fft_tiles_conv_ols_kernel<C>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a);    \
+    return true;                                                                                      \
+  }                                                                                                   \
+  ++cur;
+  MI355_TILE_KERNEL_LIST(X)
+#undef X
+  (void)cur; (void)a; (void)grid; (void)l;
+  return false;
+}
+#endif
+
+#if defined(MI355_RTILES_DEFINE_INSTANCES) || defined(MI355_HOST_EMU)
+template <class L> bool launch_tiles_rconv_ols(int id, const TilesArgs& a, unsigned grid, L& l) {
+  int cur = 0;
+#define X(P, R0, R1, TH)                                                                              \
+  if (id == cur) {                                                                                    \
+    using C = RTileCfg<P, R0, R1, TH>;                                                                \
     l.launch(fft_tiles_conv_ols_kernel<C>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a);    \
     return true;                                                                                      \
   }                                                                                                   \
@@ -423,6 +442,7 @@ bool dispatch_step(const Step& s, void* const ptr[STEP_PTRS], L& l, LinesFn&& li
         return launch_lines_conv_ols(s.variant, oa, s.grid, l);
       }
       if (a.real_mode == LM_TILES_CONV_OLS || a.real_mode == LM_TILES_SPECTRUM) return launch_tiles_conv_ols(s.variant, tiles_args_of(s, ptr), s.grid, l);   // rank-2 overlap-save tiles
+      if (a.real_mode == LM_TILES_RCONV_OLS || a.real_mode == LM_TILES_RSPECTRUM) return launch_tiles_rconv_ols(s.variant, tiles_args_of(s, ptr), s.grid, l);   // and on real tile pairs
       const LineKernelMeta& m = line_kernel_registry()[(size_t)s.variant];
       return lines_fn(family_of_line_kernel(m), s.variant, a, s.grid);
     }

@@ -22,6 +22,16 @@
 //             [k0 * P + k1], which the row pass reads with consecutive lanes; LM_TILES_SPECTRUM is this kernel's forward half storing that order
 //   store   : positions inside both windows, then the crop [lo_a, hi_a) of omap, zeroPad.write (zlo, zhi) and the output lane; scale 1/P^2
 // Element indices are 32-bit (the planner keeps every fN_a and the number of tiles below 2^31 - 16384); buffer offsets are formed in 64 bits
+//
+// Real data (type MI355FFT_FFTCONV_REAL, route tiles-rconv-ols, the kernel on an RTileCfg): two real tiles a and b ride one complex tile as z = a + i b.
+// The kernel h is real, so IFFT(FFT(z) H) = (a (*) h) + i (b (*) h), and with conj(H) the two correlations: the real parts are tile a's results and the
+// imaginary parts tile b's; no Hermitian split, no packed bins, no separation pass.  Everything between the first load and the last store is the complex
+// kernel's.  The partners are neighbours on axis 1: work item (sb, j0, jp) holds tile (j0, 2 jp) in .x and tile (j0, 2 jp + 1) in .y.  They share s0_0, the
+// lane's column, its axis-0 predicates and both base pointers and differ in s0_1 alone, s0_1(b) = s0_1(a) + L_1, which is the same for every lane (SGPRs).
+// pairs_1 = ceil(nb_1 / 2); with odd nb_1 the last pair's partner does not exist and needs no special case: s0_1(b) >= shape[1], so every load of its
+// fails the map's hi bound, and s0_1(b) + w0_1 >= plim_1, so its window is empty.  Sides are 4-byte elements: every access is naturally aligned whatever s0_0.
+// The kernel spectra come from the same kernel (LM_TILES_RSPECTRUM): one kernel per work item in .x; nb_1 = 1 and L_1 = P put partner b at s0_1 = P, beyond the
+// kernel map's hi: zero imaginary parts, and the full complex P x P spectrum in the order above
 #pragma once
 #include "platform.hpp"
 #include "radix.hpp"
@@ -41,11 +51,11 @@ namespace mi355 {
 
 struct TileAxis { int fN, plim, nb, L, w0, pre; };   // RconvOls (kern_lines.hpp) of one axis
 struct TilesArgs {
-  const cf* in;
+  const cf* in;         // the real form (RTileCfg) reads `in` and writes `out` as float arrays: the maps count 4-byte elements
   cf* out;
   const cf* tw;         // stage-1 roots [R1 - 1][R0] of order P (the table of a line kernel of P = R0 R1 points)
   const cf* spectrum;   // the kernel spectrum on P x P, bin (k0, k1) at [k0 * P + k1]
-  long long num_tiles;
+  long long num_tiles;  // work items: tiles, or tile pairs in the real form (ax[1].nb stays the number of tiles)
   float scale;
   int conj;             // correlation: the spectrum's conjugate
   int spectrum_only;    // LM_TILES_SPECTRUM: forward half only; tile k is kernel k, its spectrum stored dense at out + k P^2
@@ -56,6 +66,7 @@ struct TilesArgs {
 template <int P_, int R0_, int R1_, int THREADS_>
 struct TileCfg {
   static constexpr int P = P_, R0 = R0_, R1 = R1_, THREADS = THREADS_;
+  static constexpr bool REAL = false;               // RTileCfg: real tile pairs
   static_assert(R0 * R1 == P, "radix product");
   static_assert(THREADS % P == 0 && THREADS <= 1024, "a thread stays on one line");
   static constexpr int TPL = THREADS / P;           // threads per line
@@ -120,8 +131,11 @@ template <class C, int S, bool COLS> MI_DEV void tile_stage_write(const cf (&v)[
     for (int q = 0; q < I::R; ++q) lds[tile_index<C, COLS>(line, tile_stage_out<C, S>(u, b, q))] = v[b * I::R + q];
 }
 
+// C::REAL: two real tiles, neighbours on axis 1, as re / im of the complex tile (see the header); the form differs at the loads, at the stores and where a
+// work item's tile is found.  It is a property of the configuration, not a second template parameter: the complex instances keep their names and their code
 template <class C>
 __global__ void __launch_bounds__(C::THREADS, C::WAVES_PER_SIMD) fft_tiles_conv_ols_kernel(const TilesArgs a) {
+  constexpr bool REAL = C::REAL;
   MI_SMEM_DECL(smem);
   cf* lds = reinterpret_cast<cf*>(smem);
   cf* tw_lds = lds + C::DATA_ELEMS;
@@ -135,13 +149,35 @@ __global__ void __launch_bounds__(C::THREADS, C::WAVES_PER_SIMD) fft_tiles_conv_
   const SideMap& om = a.omap;
   const TileAxis& A0 = a.ax[0];
   const TileAxis& A1 = a.ax[1];
-  const unsigned per_image = (unsigned)A0.nb * (unsigned)A1.nb;
+  const unsigned per_image = (unsigned)A0.nb * (REAL ? ((unsigned)A1.nb + 1u) / 2u : (unsigned)A1.nb);
   for (long long tile = blockIdx.x; tile < a.num_tiles; tile += gridDim.x) {
     const unsigned sb = (unsigned)tile / per_image, r = (unsigned)tile - sb * per_image, j1 = r / (unsigned)A0.nb, j0 = r - j1 * (unsigned)A0.nb;
-    const int s00 = (int)j0 * A0.L - A0.pre, s01 = (int)j1 * A1.L - A1.pre;      // the tile's first signal index on each axis
+    const int s00 = (int)j0 * A0.L - A0.pre, s01 = (int)(REAL ? 2u * j1 : j1) * A1.L - A1.pre;      // the tile's first signal index on each axis (REAL: partner a's)
     cf v[C::E];
     // ---- forward, columns: stage 0 from global memory (this lane: column i0 = line) ----
-    {
+    if constexpr (REAL) {
+      const int q0 = s00 + line;
+      const bool ok0 = q0 >= im.lo[0] && q0 < im.hi[0];
+      const float* x = reinterpret_cast<const float*>(a.in) + (im.offset + (long long)sb * im.batch_stride + (long long)q0 * im.stride[0]);   // (dereferenced inside [lo, hi) only)
+      const int s01b = s01 + A1.L;                                                 // partner b: the next tile on axis 1
+      const int l1 = im.lo[1] - s01, h1 = im.hi[1] - s01, l1b = im.lo[1] - s01b, h1b = im.hi[1] - s01b;
+      const int lo1 = l1 < 0 ? 0 : l1, hi1 = h1 > C::P ? C::P : h1;               // each partner's share of [lo, hi) on axis 1
+      const int lo1b = l1b < 0 ? 0 : l1b, hi1b = h1b > C::P ? C::P : h1b;
+      const long long s1 = im.stride[1];
+      int ul = u;
+      if constexpr (C::REFORM_POSITIONS) MI_TILE_OPAQUE_LANE(ul);
+#pragma unroll
+      for (int b = 0; b < I0::NB; ++b) {
+#pragma unroll
+        for (int q = 0; q < I0::R; ++q) {
+          const int i1 = ul + b * C::TPL + q * (C::P / I0::R);
+          cf xv = {0.0f, 0.0f};
+          if (ok0 && i1 >= lo1 && i1 < hi1) xv.x = x[(long long)(s01 + i1) * s1];
+          if (ok0 && i1 >= lo1b && i1 < hi1b) xv.y = x[(long long)(s01b + i1) * s1];
+          v[b * I0::R + q] = xv;
+        }
+      }
+    } else {
       const int q0 = s00 + line;
       const bool ok0 = q0 >= im.lo[0] && q0 < im.hi[0];
       const cf* x = a.in + (im.offset + (long long)sb * im.batch_stride + (long long)q0 * im.stride[0]);   // (dereferenced inside [lo, hi) only)
@@ -215,7 +251,37 @@ __global__ void __launch_bounds__(C::THREADS, C::WAVES_PER_SIMD) fft_tiles_conv_
     tile_stage_read<C, 1, true>(v, lds, line, u);
     __syncthreads();            // everyone has its inputs: LDS is free for the next tile
     tile_stage_compute<C, 1>(v, tw_lds, u);
-    {
+    if constexpr (REAL) {
+      const int q0 = s00 + line;
+      const int m0 = q0 < 0 ? q0 + A0.fN : q0;                                   // (the negative lags of a correlation sit at the top of the domain)
+      const bool ok0 = line >= A0.w0 && line < A0.w0 + A0.L && q0 < A0.plim && m0 >= om.lo[0] && m0 < om.hi[0];
+      const bool z0 = m0 < om.zlo[0] || m0 >= om.zhi[0];
+      float* y = reinterpret_cast<float*>(a.out) + (om.offset + (long long)sb * om.batch_stride + (long long)m0 * om.stride[0]);   // (dereferenced inside the crop only)
+      const long long s1 = om.stride[1];
+      const int s01b = s01 + A1.L;
+      int wlo = A1.w0, us = u;
+      MI_TILE_OPAQUE(wlo);
+      if constexpr (C::REFORM_POSITIONS) MI_TILE_OPAQUE_LANE(us);
+      const int wend = A1.w0 + A1.L, pend = A1.plim - s01, whi = wend < pend ? wend : pend;   // each partner's window, cut at the last index the signal gives;
+      const int pendb = A1.plim - s01b, whib = wend < pendb ? wend : pendb;                    // an absent partner's is empty: s0_1(b) + w0_1 >= plim_1 in both modes
+#pragma unroll
+      for (int b = 0; b < I1::NB; ++b) {
+#pragma unroll
+        for (int q = 0; q < I1::R; ++q) {
+          const int i1 = tile_stage_out<C, 1>(us, b, q);
+          if (!ok0 || i1 < wlo) continue;
+          const cf r = cswap(v[b * I1::R + q]) * a.scale;
+          if (i1 < whi) {
+            const int q1 = s01 + i1, m1 = q1 < 0 ? q1 + A1.fN : q1;
+            if (m1 >= om.lo[1] && m1 < om.hi[1]) y[(long long)m1 * s1] = (z0 || m1 < om.zlo[1] || m1 >= om.zhi[1]) ? 0.0f : r.x;
+          }
+          if (i1 < whib) {
+            const int q1 = s01b + i1, m1 = q1 < 0 ? q1 + A1.fN : q1;
+            if (m1 >= om.lo[1] && m1 < om.hi[1]) y[(long long)m1 * s1] = (z0 || m1 < om.zlo[1] || m1 >= om.zhi[1]) ? 0.0f : r.y;
+          }
+        }
+      }
+    } else {
       const int q0 = s00 + line;
       const int m0 = q0 < 0 ? q0 + A0.fN : q0;                                   // (the negative lags of a correlation sit at the top of the domain)
       const bool ok0 = line >= A0.w0 && line < A0.w0 + A0.L && q0 < A0.plim && m0 >= om.lo[0] && m0 < om.hi[0];
@@ -242,5 +308,8 @@ __global__ void __launch_bounds__(C::THREADS, C::WAVES_PER_SIMD) fft_tiles_conv_
     }
   }
 }
+
+// the real form: instantiated in a unit of its own (tiles_rconv_ols.hip)
+template <int P_, int R0_, int R1_, int THREADS_> struct RTileCfg : TileCfg<P_, R0_, R1_, THREADS_> { static constexpr bool REAL = true; };
 
 }  // namespace mi355

@@ -87,16 +87,18 @@ const std::vector<ConvKernelMeta>& conv_kernel_registry() {
   return reg;
 }
 
-const TileKernelMeta* find_tile_kernel(int P) {
+const TileKernelMeta* find_tile_kernel(int P, bool real) {
   static const std::vector<TileKernelMeta> reg = [] {
     std::vector<TileKernelMeta> r;
-    int id = 0;
-#define X(P, R0, R1, TH) r.push_back(TileKernelMeta{id++, P, R0, R1, TH, tile_kernel_lds_bytes(P, R0, R1)});
-    MI355_TILE_KERNEL_LIST(X)
+    for (int real = 0; real < 2; ++real) {   // both forms instantiate the whole list: an id is the position in it
+      int id = 0;
+#define X(P, R0, R1, TH) r.push_back(TileKernelMeta{id++, P, R0, R1, TH, tile_kernel_lds_bytes(P, R0, R1), real != 0});
+      MI355_TILE_KERNEL_LIST(X)
 #undef X
+    }
     return r;
   }();
-  for (const auto& m : reg) if (m.P == P) return &m;
+  for (const auto& m : reg) if (m.P == P && m.real == real) return &m;
   return nullptr;
 }
 
@@ -173,6 +175,7 @@ PlannerOptions planner_options_from_env() {
   if (const char* s = std::getenv("MI355FFT_RCONV_OLS")) o.rconv_ols = std::atoi(s);
   if (const char* s = std::getenv("MI355FFT_CONV_OLS")) o.conv_ols = std::atoi(s);
   if (const char* s = std::getenv("MI355FFT_CONV_OLS2D")) o.conv_ols2d = std::atoi(s);
+  if (const char* s = std::getenv("MI355FFT_RCONV_OLS2D")) o.rconv_ols2d = std::atoi(s);
   if (const char* s = std::getenv("MI355FFT_SOLO_MAX_KB")) { const int v = std::atoi(s); if (v >= 0) o.solo_max_kb = v; }
   if (const char* s = std::getenv("MI355FFT_SOLO_CAP_MB")) { const int v = std::atoi(s); if (v >= 1) o.solo_cap_mb = v; }
   if (const char* s = std::getenv("MI355FFT_XCD_SLOTS")) { const int v = std::atoi(s); if (v >= 0 && v <= 2) o.xcd_slots = v; }
@@ -2046,7 +2049,10 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
 
 // ---- fftconv over real data (type MI355FFT_FFTCONV_REAL) ------------------------------------------------------------------------
 // Signals, kernels and results are f32 reals; the values are the real parts of what build_fftconv's plan returns for the same data
-// with zero imaginary parts.  Every option keeps its meaning; side layouts and the kernel stride count f32 elements.  Four routes:
+// with zero imaginary parts.  Every option keeps its meaning; side layouts and the kernel stride count f32 elements.  Five routes:
+//   tiles-rconv-ols[N=PxP,L=L0xL1]  rank 2, linear modes, images with small kernels by default (rconv_tiles_block; MI355FFT_RCONV_OLS2D): overlap-save on
+//                     P x P tiles, two real tiles that are neighbours on axis 1 as re / im of one complex tile (kern_tiles.hpp); 1 + K launches for any
+//                     image, strided lanes too
 //   lines-rconv-ols[N=P,L=L]  rank 1, linear modes, shape + kernelShape - 1 > 8192 and kernelShape <= 4096 by default (MI355FFT_RCONV_OLS): overlap-save,
 //                     the line cut into blocks of P points that each run the pipeline of lines-rconv; 1 + K launches for any length, strided lanes too
 //   lines-rconv[N=P]  rank 1, FFT length P a power of two, 128 <= P <= 8192 by default (16384 and 32768 with strided sides or MI355FFT_RCONV_FUSED=2) (circular: P = shape; linear modes: the next power of two
@@ -2061,6 +2067,15 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
 //   rconv-widened     circular with odd shape[0] (no even domain is allowed): the complex plan between widening / narrowing passes
 // Validation, shapes, lanes and the padded-domain index map are ConvGeom's, shared with build_fftconv; each route hands it the
 // axis-0 length it transforms on.
+// The tile edge the default rule (PlannerOptions::rconv_ols2d == 1) gives to overlap-save on a real rank-2 image: conv_tiles_block's bounds (they also keep the
+// small real rank-2 requests on rconv[K], whose routes the tests pin) and, as measured, its tile edges.
+// Measured (profiles/fftconv_rtiles_ab.log: conv_tiles_block's six requests as real data, K = 1 and 4, both tiles; spread between repeated samples <= 3.9 %):
+// both tiles are 2.5-38x ahead of rconv[K] on the exact-length domain on every request (the nearest: 3.8-5.3x at P = 64 on 8 x 1016^2 (*) 9x9 linear-full,
+// whose domain 1024^2 keeps rconv[K] off the Bluestein lines), so no class is excluded.  P = 64 is 48-86 % ahead of P = 128 up to 17 points (9x9: 210-246
+// against 137-165 G real points/s; 17x17: 163-191 against 104-123; 3x3 and 5x5: 52-72 against 28-38); at 33 points P = 128 is 41-48 % ahead (160-175 against
+// 113-118): the complex route's boundary.  Kernels of 18 .. 32 points were not measured: they take the larger tile, as there
+int64_t rconv_tiles_block(int64_t fN0, int64_t fN1, int64_t M0, int64_t M1) { return conv_tiles_block(fN0, fN1, M0, M1); }
+
 constexpr int64_t OLS_MAX_KERNEL = 4096;   // the longest kernel the default rule gives to overlap-save: the longest one measured (3.8x / 2.5x ahead at K = 1 / 4)
 int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
   ConvGeom g;
@@ -2110,6 +2125,62 @@ int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err
         st.grid = b.lines_grid(*om, tiles);
       }
       b.ir.route += "lines-rconv-ols[N=" + std::to_string(P) + ",L=" + std::to_string(L) + "] ";
+      return MI355FFT_OK;
+    }
+  }
+
+  // ---- overlap-save in two dimensions: real images, small kernels, one launch per kernel on pairs of P x P tiles ---------------------
+  // build_fftconv's tile block on real data: the geometry, the two maps and the geometry slots are the same (they count f32 elements here), and a work item is
+  // a PAIR of tiles that are neighbours on axis 1, one in the real and one in the imaginary parts of the complex tile (kern_tiles.hpp has the index map):
+  // B nb_0 ceil(nb_1 / 2) work items a launch.  The first launch is the kernel's forward half on the real kernels, one a work item: K complex spectra on
+  // P x P points.  In front of the rejection of strided sides: lanes, outputLayout, the kernel stride and zeroPad ride the two address maps.  The switch 0
+  // keeps the routes below for every request; 64 or 128 forces that tile on every request it fits (L_a >= 2); 1 is the rule of rconv_tiles_block
+  if (rank == 2 && linear && b.opt.rconv_ols2d != 0 && b.opt.rconv_fused != 0 && !b.opt.force_generic &&
+      fs[0] < ((int64_t)1 << 31) - 16384 && fs[1] < ((int64_t)1 << 31) - 16384) {   // (the kernel's indices are 32-bit)
+    int64_t P = 0;
+    if (b.opt.rconv_ols2d > 1) { if (b.opt.rconv_ols2d == 64 || b.opt.rconv_ols2d == 128) P = b.opt.rconv_ols2d; }
+    else P = rconv_tiles_block(fs[0], fs[1], ks[0], ks[1]);
+    const TileKernelMeta* tm = P ? find_tile_kernel((int)P, true) : nullptr;
+    const int64_t pre[2] = {ks[0] - 1, ks[1] - 1}, L[2] = {P - pre[0], P - pre[1]};
+    const int64_t nb[2] = {L[0] >= 2 ? (fs[0] + L[0] - 1) / L[0] : 0, L[1] >= 2 ? (fs[1] + L[1] - 1) / L[1] : 0};
+    const int64_t pairs1 = (nb[1] + 1) / 2;
+    const bool fits = tm && L[0] >= 2 && L[1] >= 2 && nb[0] * nb[1] < ((int64_t)1 << 31) - 16384 && B * nb[0] * pairs1 < ((int64_t)1 << 31) - 16384;
+    if (fits) {
+      const int64_t pd[2] = {P, P}, items = B * nb[0] * pairs1;
+      const PtrRef G = b.alloc_work((uint64_t)K * P * P * 8);
+      std::vector<float2h> roots;
+      for (int q = 1; q < tm->R1; ++q) for (int k = 0; k < tm->R0; ++k) roots.push_back(root_of_unity((int64_t)q * k, P));
+      const PtrRef tables = b.add_table(roots);
+      const auto both = [](int64_t a0, int64_t a1) { return (int64_t)((uint64_t)(uint32_t)a0 | ((uint64_t)(uint32_t)a1 << 32)); };
+      int64_t per_cu = std::min<int64_t>((160 * 1024) / tm->lds_bytes, 2048 / tm->threads);
+      per_cu = std::max<int64_t>(per_cu, 1);
+      const auto push = [&](LineMode mode, PtrRef src, PtrRef dst, int64_t count) -> Step& {
+        Step& st = b.push(ST_LINES);
+        st.variant = tm->id;
+        st.p[LP_IN] = src; st.p[LP_OUT] = dst; st.p[LP_TW] = tables;
+        st.i[LS_TILES] = count; st.i[LS_LINES] = count; st.i[LS_IN_S] = 1; st.i[LS_IN_OUTER] = P; st.i[LS_OUT_S] = 1; st.i[LS_OUT_OUTER] = P;
+        st.i[LS_MODE] = mode; st.i[LS_MAPPED] = 1;
+        st.grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(count, per_cu * b.opt.compute_units));
+        return st;
+      };
+      {   // the K kernel spectra: one kernel a work item (nb_1 = 1 and L_1 = P put its partner beyond the kernel map: zero imaginary parts), no overlap
+        Step& st = push(LM_TILES_RSPECTRUM, kern, G, K);
+        st.i[LS_OLS_FN] = both(P, P); st.i[LS_OLS_PLIM] = both(P, P); st.i[LS_OLS_NB] = both(1, 1); st.i[LS_OLS_L] = both(P, P);
+        st.imap = conv_kernel_map(g, pd, 2); st.omap = Builder::dense_map(pd, 2);
+        b.ir.route += "tiles-rspectrum[N=" + std::to_string(P) + "x" + std::to_string(P) + "] ";
+      }
+      const SideMap xm = conv_load_map(d, g, fs, 2);
+      for (int64_t k = 0; k < K; ++k) {
+        Step& st = push(LM_TILES_RCONV_OLS, in, out, items);
+        st.p[LP_MUL_SPECTRUM] = G.plus(k * P * P * 8);
+        st.i[LS_CONJ] = corr ? 1 : 0;
+        st.i[LS_OLS_FN] = both(fs[0], fs[1]); st.i[LS_OLS_PLIM] = corr ? both(d.shape[0], d.shape[1]) : both(fs[0], fs[1]);
+        st.i[LS_OLS_NB] = both(nb[0], nb[1]); st.i[LS_OLS_L] = both(L[0], L[1]);
+        st.i[LS_OLS_W0] = corr ? 0 : both(pre[0], pre[1]); st.i[LS_OLS_PRE] = both(pre[0], pre[1]);
+        st.f[F_SCALE] = (float)(1.0 / (double)(P * P));
+        st.imap = xm; st.omap = conv_store_map(d, g, fs, 2, k);
+      }
+      b.ir.route += "tiles-rconv-ols[N=" + std::to_string(P) + "x" + std::to_string(P) + ",L=" + std::to_string(L[0]) + "x" + std::to_string(L[1]) + "] ";
       return MI355FFT_OK;
     }
   }

@@ -42,8 +42,10 @@ struct ConvKernelMeta { int id, N, R0, R1, TL; };
 // LDS: the P x P tile at a pitch of P + 1 elements and the stage-1 roots
 #define MI355_TILE_KERNEL_LIST(X) X(64, 8, 8, 256) X(128, 16, 8, 1024)
 constexpr int tile_kernel_lds_bytes(int P, int R0, int R1) { return (P * (P + 1) + (R1 - 1) * R0) * 8; }
-struct TileKernelMeta { int id, P, R0, R1, threads, lds_bytes; };
-const TileKernelMeta* find_tile_kernel(int P);
+struct TileKernelMeta { int id, P, R0, R1, threads, lds_bytes; bool real; };
+// `real`: the same list as instances of fft_tiles_conv_ols_kernel on an RTileCfg (real fftconv: two real tiles as re / im of a complex one), a unit of their own
+// (tiles_rconv_ols.hip); an id counts positions in the list for both forms, and the step's line mode says which form is launched
+const TileKernelMeta* find_tile_kernel(int P, bool real = false);
 // mixed-radix line kernels with compile-time plans (kern_mixed_ct.hpp): id = position in the list
 // instances: X(N, lines per workgroup, threads, radices...).  Tile shapes keep every stage's butterfly count (T * N / R) at or
 // above the thread count and two workgroups per CU inside the LDS.
@@ -133,7 +135,9 @@ enum LineMode : int {
   LM_RCONV_OLS = 10,  // its overlap-save form (fft_lines_rconv_ols_kernel)
   LM_CONV_OLS = 11,   // overlap-save on complex lines: forward FFT, product and inverse FFT of a block in one launch (fft_lines_conv_ols_kernel)
   LM_TILES_CONV_OLS = 12,   // overlap-save on rank-2 complex tiles (kern_tiles.hpp fft_tiles_conv_ols_kernel): `variant` is a TileKernelMeta id, not a line kernel's
-  LM_TILES_SPECTRUM = 13    // its forward half on the zero-padded kernels: the K spectra in the order the product reads them
+  LM_TILES_SPECTRUM = 13,   // its forward half on the zero-padded kernels: the K spectra in the order the product reads them
+  LM_TILES_RCONV_OLS = 14,  // overlap-save on rank-2 real tiles, two of them as re / im of a complex tile (kern_tiles.hpp fft_tiles_conv_ols_kernel on an RTileCfg); `variant` as above
+  LM_TILES_RSPECTRUM = 15   // its forward half on the zero-padded real kernels, one a work item: the K complex spectra as LM_TILES_SPECTRUM stores them
 };
 // Bluestein's two mapped launches: bits of i[LS_CHIRP_FLAGS] (LineArgs::fs_lo_mask)
 enum : unsigned { LINES_CHIRP = 1, LINES_CHIRP_SWAP = 2 };   // multiply by the chirp in p[LP_CHIRP]; inverse transform: the chirp's conjugate
@@ -147,7 +151,7 @@ enum LinesSlot {
   LS_MODE = 9,                               // LineMode
   LS_MAPPED = 10,                            // sides through Step::imap / omap
   LS_H16 = 11,                               // binary16 sides (f16-storage)
-  LS_CONJ = 12,                              // LM_RCONV, LM_RCONV_OLS, LM_CONV_OLS, LM_TILES_CONV_OLS: correlation
+  LS_CONJ = 12,                              // LM_RCONV, LM_RCONV_OLS, LM_CONV_OLS, LM_TILES_CONV_OLS, LM_TILES_RCONV_OLS: correlation
   LS_RCONV_SPLIT = 13, LS_OLS_FN = 13,       // LM_RCONV: ConvGeom split / padD;  LM_RCONV_OLS, LM_CONV_OLS: the block geometry (kern_lines.hpp RconvOls)
                                              // LM_TILES_*: the same six per axis (kern_tiles.hpp TileAxis), axis 0 in the low 32 bits of a slot and axis 1 in the high
   LS_RCONV_PADD = 14, LS_OLS_PLIM = 14,
@@ -157,7 +161,7 @@ enum LinesSlot {
 static_assert(LS_LAST < STEP_INTS, "ST_LINES slots");
 enum LinesPtr {
   LP_IN = 0, LP_OUT = 1, LP_TW = 2,
-  LP_TW_LO = 3, LP_MUL_SPECTRUM = 3,         // four-step / split LO roots (LM_RCONV*: LO and HI in one table); LM_MUL, LM_CONV_OLS, LM_TILES_CONV_OLS: the spectrum multiplied in
+  LP_TW_LO = 3, LP_MUL_SPECTRUM = 3,         // four-step / split LO roots (LM_RCONV*: LO and HI in one table); LM_MUL, LM_CONV_OLS, LM_TILES_CONV_OLS, LM_TILES_RCONV_OLS: the spectrum multiplied in
   LP_TW_HI = 4, LP_CHIRP = 4, LP_RCONV_SPECTRUM = 4,   // HI roots; Bluestein: the chirp; LM_RCONV*: the packed kernel spectrum
   LP_LAST = LP_RCONV_SPECTRUM
 };
@@ -327,6 +331,15 @@ struct PlannerOptions {
                                        // fftconv, rank 2, linear boundaries: overlap-save on P x P complex tiles, one launch per kernel whatever the image's size
                                        // (kern_tiles.hpp fft_tiles_conv_ols_kernel); 1: where measured ahead (plan.cpp conv_tiles_block); 0: never; 64 or 128: that
                                        // tile on every request it fits (tests and measurement).  conv_lines = 0 and force_generic come first
+#ifdef MI355_HOST_EMU
+  int rconv_ols2d = std::getenv("MI355_EMU_RCONV_OLS2D") ? std::atoi(std::getenv("MI355_EMU_RCONV_OLS2D")) : 1;
+#else
+  int rconv_ols2d = 1;
+#endif
+                                       // real fftconv, rank 2, linear boundaries: overlap-save on P x P tiles, two real tiles as re / im of a complex one, one launch
+                                       // per kernel whatever the image's size (kern_tiles.hpp fft_tiles_conv_ols_kernel on an RTileCfg); 1: where measured ahead (plan.cpp
+                                       // rconv_tiles_block); 0: never; 64 or 128: that tile on every request it fits (tests and measurement).  rconv_fused = 0 and
+                                       // force_generic come first
   int conv_lines = 1;                  // fftconv: kernel-spectrum product fused behind the forward line FFT (1-D, power-of-two FFT length <= max_line)
   int trig_fused = 1;                  // dct2 / dst2 of dense lines (half length a line-kernel size): permutation + real FFT + phase in one launch
   int trig_real = 1;                   // dct2/dst2/dct3/dst3 along a dense even axis through a real FFT of length N (kern_trig.hpp)
