@@ -306,7 +306,7 @@ template <int ONLY, class L> bool launch_xcd_sel(int id, const XcdFusedArgs& a, 
     l.launch_concurrent(fft_xcd_conv1m_kernel<k.N1, true>, grid, (unsigned)F::THREADS, (unsigned)F::LDS_BYTES, a);
   } else {   // XK_RT1K, XK_RT1K_16, XK_RT1K_VIEW, XK_RT1K_2048: Tb-line register tiles along the 1024-point rows
     using F = Rt1kCfgT<k.tb>;
-    constexpr unsigned smem = F::LDS_BYTES + (k.N1 == 2048 ? RtCfg::TW2_ELEMS * 8 : 0);   // (2048-point columns: their stage-2 roots too)
+    constexpr unsigned smem = F::LDS_BYTES + (k.N1 == 2048 ? RtCfg::TW2_ELEMS * 8 : 0) + rt1k_root_lds_elems(k.tb, k.kind == XK_RT1K_VIEW, k.N1) * 8;   // (2048-point columns: their stage-2 roots too; MI355_RT1K_ROOTS_LDS: the four-step tables)
     l.launch_concurrent(fft_xcd_rt1k_kernel<k.inverse, k.tb, k.kind == XK_RT1K_VIEW, k.N1>, grid, (unsigned)F::THREADS, smem, a);
   }
   return true;

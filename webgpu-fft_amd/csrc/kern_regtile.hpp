@@ -725,6 +725,13 @@ __global__ void __launch_bounds__(HxCfg::THREADS, MI355_HX_WAVES) fft_xcd_hx_ker
 //                          transform (at most va's 32).  32: 205.6 - 206.5 alone, 211.8 - 213.7 with A = B = 32 (no gain over A + B): off.
 //   MI355_RT1K_PREFETCH    when defined sets A and B together (the form measured before the kernel's register diet: 32 spilt 276 B at 256 VGPRs
 //                          then, 174.5 vs 196.4 GPoints/s, profiles/r03_headline_rt32_ab.log).
+// Four-step root tables in LDS (MI355_RT1K_ROOTS_LDS, plan.hpp; same instances; profiles/rt1k_roots_lds_ab.log, one box, five interleaved rounds, byte-equal output).
+//   Phase B builds six roots per row tile as HI[m >> 10] * LO[m & 1023]: 12 global loads per thread that sat at the loop top behind 15 of the 16 row loads issued
+//   there, and loads and stores return through one queue in issue order, so the tile's first product waited for those rows and for all 64 output stores of the
+//   previous tile (profiles/rt1k_roots_lds_isa.log).  The two tables are 16 KB at N = 2^20: staged once per launch behind tw1 (152 KB of LDS, still one workgroup
+//   per CU) the roots are ds_reads under lgkmcnt, and the products on the rows that were requested a tile ahead run while the stores retire.
+//   1: 214.8 - 215.6 against the parent's 211.4 - 212.2 GPoints/s (+1.6 %), 240 VGPRs, no scratch: the default.  On top of it MI355_RT1K_PREFETCH_B = 48 / 56
+//   (214.1 - 214.4 / 214.3 - 214.6) and MI355_RT1K_PREFETCH_A = 32 (214.4 - 214.7) stay below it: their defaults do not move.
 #ifndef MI355_RT1K_PREFETCH_A
 #ifdef MI355_RT1K_PREFETCH
 #define MI355_RT1K_PREFETCH_A MI355_RT1K_PREFETCH
@@ -811,9 +818,19 @@ __global__ void __launch_bounds__(Rt1kCfgT<T>::THREADS, 2) fft_xcd_rt1k_kernel(c
   cf* xb = reinterpret_cast<cf*>(smem);
   cf* tw1 = xb + K::HALF_ELEMS;
   cf* tw2 = tw1 + K::TW1_ELEMS;                                     // (N1_ = 2048: stage-2 roots of the 2048-point columns)
-  unsigned* s_words = reinterpret_cast<unsigned*>(tw2 + (N1_ == 2048 ? RtCfg::TW2_ELEMS : 0));
+  // MI355_RT1K_ROOTS_LDS (plan.hpp): the four-step tables HI | LO behind the stage tables, where the instance fixes their size; elsewhere ROOT_ELEMS is 0
+  constexpr int ROOT_ELEMS = rt1k_root_lds_elems(T, VIEW, N1_);
+  constexpr bool ROOTS_LDS = ROOT_ELEMS != 0;
+  cf* rt_hi = tw2 + (N1_ == 2048 ? RtCfg::TW2_ELEMS : 0);
+  cf* rt_lo = rt_hi + (ROOTS_LDS ? RT1K_ROOT_HI : 0);
+  unsigned* s_words = reinterpret_cast<unsigned*>(rt_hi + ROOT_ELEMS);
+  static_assert(K::LDS_BYTES + (N1_ == 2048 ? RtCfg::TW2_ELEMS : 0) * 8 + ROOT_ELEMS * 8 <= 160 * 1024, "does not fit LDS");
   const int t = threadIdx.x;
   for (int i = t; i < K::TW1_ELEMS; i += K::THREADS) tw1[i] = f.tw_b[i];
+  if constexpr (ROOTS_LDS) {
+    static_assert(RT1K_ROOT_HI == RT1K_ROOT_LO && N1_ * 1024 == RT1K_ROOT_HI << RT1K_ROOT_SHIFT, "HI[m >> shift] * LO[m & mask] covers m < N");
+    for (int i = t; i < RT1K_ROOT_HI; i += K::THREADS) { rt_hi[i] = f.tw_hi[i]; rt_lo[i] = f.tw_lo[i]; }
+  }
   if constexpr (N1_ == 2048) { for (int i = t; i < RtCfg::TW2_ELEMS; i += K::THREADS) tw2[i] = f.tw_a[i]; }
   if (!xcd_register(f.ctl, f.split, f.spin_limit, f.sticky_error, s_words)) return;
   // (as wave-uniform values: the tile loops below branch on them around a workgroup barrier and build scalar bases from them)
@@ -833,7 +850,11 @@ __global__ void __launch_bounds__(Rt1kCfgT<T>::THREADS, 2) fft_xcd_rt1k_kernel(c
   cf* const W0 = f.wslots + (size_t)((two_slots ? 2u : 1u) * gslot) * (size_t)f.N;
   const int cl = t & (T - 1), h = t / T;    // column-side map
   const int rl = t >> 4, hh = t & 15;       // row-side map
-  const auto root = [&](unsigned m) { return rt1k_cmul(f.tw_hi[m >> f.fs_shift], f.tw_lo[m & f.fs_lo_mask]); };
+  // (same values, same product either way: the LDS copies are read with lgkmcnt, outside the queue the tile's stores and row loads share; m < N = 2^20)
+  const auto root = [&](unsigned m) {
+    if constexpr (ROOTS_LDS) return rt1k_cmul(rt_hi[m >> RT1K_ROOT_SHIFT], rt_lo[m & (unsigned)(RT1K_ROOT_LO - 1)]);
+    else return rt1k_cmul(f.tw_hi[m >> f.fs_shift], f.tw_lo[m & f.fs_lo_mask]);
+  };
   const auto stage1 = [&](cf (&w)[32], int j2) {
     int ti = j2; MI_OPAQUE_LANE_INT(ti);     // (not loop-invariant for the optimiser: hoisted, the 31 roots would pin 62 registers)
 #pragma unroll

@@ -123,9 +123,9 @@ XcdKernelMeta xcd_meta(int id, const XcdInstance& k) {
   } else if (k.kind == XK_HX) {   // HxCfg: 16-line tiles, 512 threads
     m.threads = 512;
     m.lds_bytes = (16 * 32 * 16 + TW1_1K) * 8 + 64;
-  } else {   // Rt1kCfgT<Tb>: Tb-line tiles, 16 Tb threads; 2048 x 1024 adds the stage-2 roots of its 2048-point columns
+  } else {   // Rt1kCfgT<Tb>: Tb-line tiles, 16 Tb threads; 2048 x 1024 adds the stage-2 roots of its 2048-point columns, the plain 32-line 1024 x 1024 instances the four-step tables
     m.threads = 16 * k.tb;
-    m.lds_bytes = (k.tb * 32 * 16 + TW1_1K + (k.N1 == 2048 ? RT_TW2 : 0)) * 8 + 64;
+    m.lds_bytes = (k.tb * 32 * 16 + TW1_1K + (k.N1 == 2048 ? RT_TW2 : 0) + (k.kind == XK_CONV || k.kind == XK_CONV_VIEW ? 0 : rt1k_root_lds_elems(k.tb, k.kind == XK_RT1K_VIEW, k.N1))) * 8 + 64;
   }
   return m;
 }
@@ -400,8 +400,9 @@ struct Builder {
     return x;
   }
   // four-step roots e^{-2 pi i m/N}: 2^shift LO roots (shift = 10 from 2^20 up, half of log2 N below), HI of N >> shift
+  // (N = 2^20: 1024 + 1024 entries, the RT1K_ROOT_* constants of plan.hpp with which fft_xcd_rt1k_kernel stages both tables in LDS)
   void xcd_roots(XcdLaunch& x, int64_t N) {
-    x.shift = N >= (1 << 20) ? 10 : lg2(N) / 2;
+    x.shift = N >= (1 << 20) ? RT1K_ROOT_SHIFT : lg2(N) / 2;
     std::vector<float2h> lo((size_t)1 << x.shift), hi((size_t)std::max<int64_t>(1, N >> x.shift));
     for (size_t l = 0; l < lo.size(); ++l) lo[l] = root_of_unity((int64_t)l, N);
     for (size_t h = 0; h < hi.size(); ++h) hi[h] = root_of_unity((int64_t)h << x.shift, N);

@@ -78,6 +78,14 @@ constexpr int XCD_INSTANCE_COUNT = (int)(sizeof XCD_INSTANCES / sizeof XCD_INSTA
 struct XcdKernelMeta : XcdInstance { int id, threads, lds_bytes; };   // + the launch shape (plan.cpp xcd_kernel_registry)
 const std::vector<XcdKernelMeta>& xcd_kernel_registry();
 const std::vector<ConvKernelMeta>& conv_kernel_registry();
+// fft_xcd_rt1k_kernel (kern_regtile.hpp): the four-step root tables HI and LO staged in LDS once per launch, so that a row tile's six roots are LDS
+// reads and not global loads queued behind the previous tile's stores.  Only where the instance fixes their size and they fit beside the exchange
+// half: the 32-line 1024 x 1024 instances without predicates (N = 2^20: shift 10, 1024 + 1024 entries, 16 KB; plan.cpp xcd_roots).  0: global tables.
+#ifndef MI355_RT1K_ROOTS_LDS
+#define MI355_RT1K_ROOTS_LDS 1
+#endif
+constexpr int RT1K_ROOT_SHIFT = 10, RT1K_ROOT_HI = 1024, RT1K_ROOT_LO = 1 << RT1K_ROOT_SHIFT;
+constexpr int rt1k_root_lds_elems(int tb, bool view, int N1) { return MI355_RT1K_ROOTS_LDS && tb == 32 && !view && N1 == 1024 ? RT1K_ROOT_HI + RT1K_ROOT_LO : 0; }
 
 enum BufId : int { BUF_NONE = -1, BUF_INPUT = 0, BUF_OUTPUT = 1, BUF_WORK = 2, BUF_KERNEL = 3, BUF_TABLE = 4 };
 struct PtrRef {
