@@ -783,6 +783,52 @@ MI_DEV cf rt1k_cmul(cf a, cf b) {
   return cmul(a, b);
 #endif
 }
+// Butterfly policy (radix.hpp) of the tile loops' radix-32 DFTs: bfly32's K = 4, 8, 12 bit for bit, with the operand selection written out.  The compiler
+// builds (b.y, -b.x) for K = 8 as a sign-bit xor and a copy in front of the two packed adds, the pair s of K = 4 as two packed adds and a copy, that of
+// K = 12 as an add, an xor, a packed add and a copy (profiles/rt1k_lean_bfly_isa.log: 508 of the two loops' 2817 vector instructions); here
+//   K = 8    a' = (a.x + b.y, a.y - b.x), b' = (a.x - b.y, a.y + b.x)     two v_pk_add_f32: b crossed, neg_hi / neg_lo on b
+//   K = 4    s = (b.x + b.y, b.y - b.x)                                    one v_pk_add_f32 of b with itself crossed, neg_hi on the second
+//            a' = fma(h, s, a), b' = fma(-h, s, a)                         two v_pk_fma_f32, h from the low half of a scalar pair, the second with neg on h
+//   K = 12   s = (b.y - b.x, b.x + b.y)                                    one v_pk_add_f32; bfly32's s.y is the NEGATED sum, and that negation is
+//            a' = (fma(h, s.x, a.x), fma(h, -s.y, a.y))                    neg_hi on s here: -(x + y) itself differs from (-x) + (-y) in the sign of a zero sum,
+//            b' = (fma(-h, s.x, a.x), fma(h, s.y, a.y))                    a negated operand never does; (-h)(-s.y) = h s.y exactly
+// A negation by modifier is exact and x - y is x + (-y), so every output keeps bfly32's operations, order and roundings.  K = 0 and the twelve generic
+// roots are bfly32's own code: the compiler already keeps their (-wi, wi) pairs in scalar registers and negates t in the fma (no xor, no copy there).
+#if MI355_RT1K_LEAN_BFLY && !MI355_EXP_NO_MATH && !defined(MI355_HOST_EMU)
+#define MI355_RT1K_BFLY_ASM 1
+#else
+#define MI355_RT1K_BFLY_ASM 0   /* the policy is BflyStd: plain C++ of the same rounding */
+#endif
+struct Rt1kBfly {
+  static constexpr bool STD = !MI355_RT1K_BFLY_ASM;
+  template <int K> static MI_DEV void run(cf& a, cf& b) {
+#if MI355_RT1K_BFLY_ASM
+    if constexpr (K == 8) {
+      cf t, u;
+      asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(t) : "v"(a), "v"(b));
+      asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]" : "=v"(u) : "v"(a), "v"(b));
+      a = t; b = u;
+    } else if constexpr (K == 4 || K == 12) {
+      const cf hc = {0.70710678118654752440f, 0.70710678118654752440f};
+      cf s, t, u;
+      if constexpr (K == 4) {
+        asm("v_pk_add_f32 %0, %1, %1 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(s) : "v"(b));
+        asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[1,0,1]" : "=v"(t) : "v"(s), "s"(hc), "v"(a));
+        asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[1,0,1] neg_lo:[0,1,0] neg_hi:[0,1,0]" : "=v"(u) : "v"(s), "s"(hc), "v"(a));
+      } else {
+        asm("v_pk_add_f32 %0, %1, %1 op_sel:[1,0] op_sel_hi:[0,1] neg_lo:[0,1]" : "=v"(s) : "v"(b));
+        asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[1,0,1] neg_hi:[1,0,0]" : "=v"(t) : "v"(s), "s"(hc), "v"(a));
+        asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[1,0,1] neg_lo:[0,1,0]" : "=v"(u) : "v"(s), "s"(hc), "v"(a));
+      }
+      a = t; b = u;
+    } else bfly32<K>(a, b);
+#else
+    bfly32<K>(a, b);
+#endif
+  }
+};
+template <bool PIPE> struct Rt1kBflyOf { using type = BflyStd; };
+template <> struct Rt1kBflyOf<true> { using type = Rt1kBfly; };
 template <int T = 32> MI_DEV int rt1k_slot(int line, int pl, int u) { return u * (16 * T) + pl * T + ((line + (u >> 1)) & (T - 1)); }
 
 // producers (line, ua), (line, ub) with outputs va[p], vb[p]; consumers (cl, h) in the first half and (cl, h + 16) in the second.
@@ -839,6 +885,7 @@ __global__ void __launch_bounds__(Rt1kCfgT<T>::THREADS, 2) fft_xcd_rt1k_kernel(c
   const bool two_slots = f.slots != 1u;
   // the software pipeline (MI355_RT1K_PREFETCH_A / _B / _X) exists in the 32-line 1024 x 1024 instances without predicates; the others compile it out
   constexpr bool PIPE = T == 32 && !VIEW && N1_ == 1024;
+  using BF = typename Rt1kBflyOf<PIPE>::type;   // MI355_RT1K_LEAN_BFLY: the butterflies of the four radix-32 DFTs per tile, both phases
   constexpr int PFA = PIPE ? MI355_RT1K_PREFETCH_A : 0, PFB = PIPE ? MI355_RT1K_PREFETCH_B / 2 : 0, PFX = PIPE ? MI355_RT1K_PREFETCH_X : 0;
   // inverse instances: the re/im swap of x is applied when a tile's loads are consumed, not to each load — on a load requested a tile ahead the
   // compiler keeps the swapped copy next to the landing registers (256 VGPRs + 132 B of scratch at A = B = 32; this way 241 and 0 B)
@@ -847,6 +894,11 @@ __global__ void __launch_bounds__(Rt1kCfgT<T>::THREADS, 2) fft_xcd_rt1k_kernel(c
   // slot re-use as a split barrier (kern_xcd.hpp): workgroups that own tiles (rank < NT: every one that enters a tile loop) signal their
   // last read of W early and wait for the peers' late
   constexpr bool SPLIT_HANDOFF = MI355_RT1K_SPLIT_HANDOFF && N1_ == 1024;
+  // MI355_RT1K_EARLY_B (plan.hpp; protocol: kern_xcd.hpp): phase B's head, the PFB row loads of a workgroup's first tile, is requested between the arrive and
+  // the wait of the A | B barrier.  Element q of a row tile is column 32 q + 2 hh (+ 1) of W, written by phase-A tile q alone, so the head reads what tiles
+  // 0 .. PFB - 1 stored.  Per launch, wave-uniform: on iff every workgroup owns NT / gsize tiles (then each has a last tile to signal in, and rank < NT) and
+  // those tiles all lie in rounds before the last one; otherwise nothing below differs from the form without it.
+  const bool early_b = MI355_RT1K_EARLY_B && PFB != 0 && gsize != 0u && NT % gsize == 0u && (NT / gsize - 1u) * gsize >= (unsigned)PFB;
   cf* const W0 = f.wslots + (size_t)((two_slots ? 2u : 1u) * gslot) * (size_t)f.N;
   const int cl = t & (T - 1), h = t / T;    // column-side map
   const int rl = t >> 4, hh = t & 15;       // row-side map
@@ -862,7 +914,7 @@ __global__ void __launch_bounds__(Rt1kCfgT<T>::THREADS, 2) fft_xcd_rt1k_kernel(c
       w[q] = rt1k_cmul(w[q], tw1[(q - 1) * 32 + ti]);
       if (MI355_RT1K_TW_FENCE && q % MI355_RT1K_TW_FENCE == 0) MI_SCHED_FENCE();   // at most this many roots in flight (registers) at a time
     }
-    fft_radix<32>(w);
+    fft_radix<32, BF>(w);
   };
   cf va[32], vb[32], w[32];   // (transform-loop scope: va carries the boundary prefetch from a transform's last phase-B tile into the next one's phase A)
   unsigned k = 0;
@@ -912,8 +964,12 @@ __global__ void __launch_bounds__(Rt1kCfgT<T>::THREADS, 2) fft_xcd_rt1k_kernel(c
 #pragma unroll
           for (int q = 0; q < 32; ++q) { va[q] = cswap_if<true>(va[q]); vb[q] = cswap_if<true>(vb[q]); }
         }
-        fft_radix<32>(va);
-        fft_radix<32>(vb);
+        fft_radix<32, BF>(va);
+        fft_radix<32, BF>(vb);
+        // MI355_RT1K_EARLY_B, producer: in the workgroup's last tile every wave drains its queue here.  The tile's loads of x, the youngest entries, are
+        // consumed by the butterflies above, so this waits for next to nothing, and it makes "all W stores of my earlier tiles of this transform are complete
+        // in the L2" true whatever order loads and stores return in.  The count follows in mid(), behind the exchange's workgroup barriers.
+        if constexpr (PFB != 0 && MI355_RT1K_EARLY_B) { if (early_b && tile + gsize >= NT) MI_WAIT_VMEM(); }
         cf* const po = W + tile * TU;
         const unsigned so = (unsigned)h * N2 + (unsigned)cl;
         // the peers' reads of W in transform k - 1 end here at the latest: the first store to W follows the exchange below.  No acquire:
@@ -925,6 +981,7 @@ __global__ void __launch_bounds__(Rt1kCfgT<T>::THREADS, 2) fft_xcd_rt1k_kernel(c
         }
         rt1k_exchange<T>(va, vb, w, xb, cl, h, h + 16, cl, h, [&] {
           if (PF && tile + gsize < NT) load_a(tile + gsize, 0, PF);
+          if constexpr (PFB != 0 && MI355_RT1K_EARLY_B) { if (early_b && tile + gsize >= NT) xcd_arrive_reads(&f.ctl->bar[gslot][2], so == 0u); }   // (one add per workgroup and transform, one slot or two)
           stage1(w, h);
 #pragma unroll
           for (int q = 0; q < 32; ++q) st_stream<MI355_RT1K_W_NT != 0>(sgpr_base(po + (unsigned)(32 * q) * N2) + so, w[q]);
@@ -936,6 +993,32 @@ __global__ void __launch_bounds__(Rt1kCfgT<T>::THREADS, 2) fft_xcd_rt1k_kernel(c
       }
     }
     xcd_arrive(&f.ctl->bar[gslot][0]);
+    // MI355_RT1K_EARLY_B, consumer (kern_xcd.hpp): ONE relaxed read of the head's counter, no loop.  At the target every workgroup of the group has confirmed
+    // its stores of all tiles but its last, which covers tiles 0 .. PFB - 1; the leader's acquire drops this CU's L1 first (the slot is re-used: the lines
+    // may sit there from transform k - 1), and behind one workgroup barrier every thread requests the head, which then flies during the wait for the
+    // peers.  Short of the target nothing is requested and the head follows the wait as before.  The wait's workgroup-uniform early return now happens
+    // with these loads outstanding: as with the tile prefetch, they are dropped and no global store follows.
+    bool head_sent = false;
+    if constexpr (PFB != 0 && MI355_RT1K_EARLY_B) {
+      if (early_b) {
+        if (t == 0) {
+          const unsigned ready = MI_ATOMIC_LOAD_U32(&f.ctl->bar[gslot][2]) >= (k + 1u) * gsize ? 1u : 0u;
+          if (ready) MI_ACQUIRE_AGENT();
+          s_words[7] = ready;
+        }
+        __syncthreads();
+        head_sent = MI_UNIFORM_U32(s_words[7]) != 0u;
+        if (head_sent) {   // load_rows(rank, 0, PFB) of the block below, which stays as it was for the instances and builds without this path
+          const unsigned lo = (unsigned)rl * N2 + 2u * (unsigned)hh;
+          const cf* p = W + (size_t)(rank * TU) * N2;
+#pragma unroll
+          for (int q = 0; q < PFB; ++q) {
+            const cf4 pr = *reinterpret_cast<const cf4*>(sgpr_base(p + 32 * q) + lo);
+            va[q] = cf{pr.x, pr.y}; vb[q] = cf{pr.z, pr.w};
+          }
+        }
+      }
+    }
     if (!xcd_wait(&f.ctl->bar[gslot][0], (k + 1u) * gsize, f.spin_limit, f.sticky_error, &s_words[6])) return;
     // ---- phase B: 32 adjacent rows per tile, four-step roots on load, transposed store ----
     cf* const y = f.out + tr * f.out_pitch;
@@ -950,7 +1033,8 @@ __global__ void __launch_bounds__(Rt1kCfgT<T>::THREADS, 2) fft_xcd_rt1k_kernel(c
           va[q] = cf{pr.x, pr.y}; vb[q] = cf{pr.z, pr.w};
         }
       };
-      if (PF && rank < NT) load_rows(rank, 0, PF);
+      if constexpr (PFB != 0 && MI355_RT1K_EARLY_B) { if (rank < NT && !head_sent) load_rows(rank, 0, PF); }
+      else { if (PF && rank < NT) load_rows(rank, 0, PF); }
       for (unsigned tile = rank; tile < NT; tile += gsize) {
         load_rows(tile, PF, 32);
         {
@@ -967,8 +1051,8 @@ __global__ void __launch_bounds__(Rt1kCfgT<T>::THREADS, 2) fft_xcd_rt1k_kernel(c
             }
           }
         }
-        fft_radix<32>(va);
-        fft_radix<32>(vb);
+        fft_radix<32, BF>(va);
+        fft_radix<32, BF>(vb);
         cf* const po = y + tile * TU;
         const unsigned so = (unsigned)h * N1 + (unsigned)cl;
         const auto store = [&](cf (&ww)[32], unsigned off) {

@@ -50,7 +50,8 @@ struct XcdCtl {                  // zeroed by a memset step before every launch
                                  // that sees the grid complete has by construction also seen every per-XCD count (two counters
                                  // updated by relaxed atomics could be observed out of step)
   unsigned reg_pad[15];
-  unsigned bar[512][16];         // one 64-byte line per group (XCC id x split): [0] A->B barrier, [1] B->A barrier (one-slot mode)
+  unsigned bar[512][16];         // one 64-byte line per group (XCC id x split): [0] A->B barrier, [1] B->A barrier (one-slot mode),
+                                 // [2] fft_xcd_rt1k_kernel: workgroups whose W stores of all tiles but their last are confirmed (below)
 };
 
 struct XcdFusedArgs {
@@ -140,6 +141,23 @@ MI_DEV void fourstep_apply_chain(cf (&v)[C::E], const XcdFusedArgs& a, unsigned 
 //     sticky error word and the workgroup-uniform early return are xcd_wait's; after a group's last transform nobody waits.
 // A workgroup without tiles (rank >= tiles) has no such places and arrives and waits the plain way at the end of the transform: the
 // counter sees one increment per workgroup and transform either way.
+//
+// Early head of phase B (bar[gslot][2], fft_xcd_rt1k_kernel with MI355_RT1K_EARLY_B; a third monotonic counter in the group's line, zeroed with it).  The
+// A | B barrier certifies ALL of phase A, but a workgroup's first row tile starts with elements that only the first phase-A tiles wrote.  The counter
+// certifies just those, a round early:
+//   producer: in its LAST phase-A tile, once the tile's loads of x are consumed, every wave waits for vmcnt(0) (its stores of all EARLIER tiles of this
+//     transform are then complete in the shared L2; the last tile's own stores come later and are not covered), and behind the exchange's workgroup barriers
+//     one lane adds 1 (xcd_arrive_reads: nothing left to drain).  One add per workgroup and transform, with one slot or two.
+//   What (k + 1) * gsize certifies: every workgroup of the group has confirmed, for transform k, the stores of all its tiles but the last.  The kernel enables
+//     the path only if all workgroups own the same number of tiles and the tiles the head reads lie in rounds before the last, so the head's columns are
+//     covered.  A peer cannot add for transform k + 1 before the A | B barrier of k has let it through, and every workgroup adds for k before it arrives
+//     there: a count at the target never stands for a missing add of k made up by a later one.
+//   consumer: after its own arrive at bar[gslot][0] (drain and add as always, so the new loads delay nobody's arrival) the leader reads the counter ONCE,
+//     relaxed, no loop.  At the target it issues the agent-scope acquire BEFORE anyone loads: the slot is re-used, so this CU's L1 may still hold the same
+//     addresses from transform k - 1, and a load that hit such a line would return the previous transform's W.  A flag in LDS and one workgroup barrier later
+//     every thread requests the head, and xcd_wait runs as always (poll, acquire, barrier) with those loads in flight.  Short of the target nothing is
+//     requested early and the head follows the wait.  No new spin, no new way to time out.
+//   Slot re-use is not touched: the head is consumed in the workgroup's first row tile, before the read-arrive of its last one.
 #ifndef MI355_XCD_RELEASE
 #define MI355_XCD_RELEASE 0
 #endif

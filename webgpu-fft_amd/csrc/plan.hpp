@@ -84,6 +84,19 @@ const std::vector<ConvKernelMeta>& conv_kernel_registry();
 #ifndef MI355_RT1K_ROOTS_LDS
 #define MI355_RT1K_ROOTS_LDS 1
 #endif
+// Same instances (the kernel's PIPE condition), both bit-identical to their 0 forms (profiles/rt1k_early_bfly_ab.log, one box, five interleaved rounds):
+//   MI355_RT1K_LEAN_BFLY  the four radix-32 DFTs of a tile take their K = 4, 8, 12 butterflies from Rt1kBfly (kern_regtile.hpp): the re/im crossing and the
+//                         negations are source modifiers of the packed adds and fmas instead of a sign-bit xor and a register copy per butterfly.
+//                         1: 217.9 - 218.7 against the parent's 215.4 - 215.9 GPoints/s (+1.4 %), 240 VGPRs, no scratch: the default.
+//   MI355_RT1K_EARLY_B    phase B's first 16 row loads are requested between the arrive and the wait of the A | B barrier when the counter bar[gslot][2]
+//                         (kern_xcd.hpp) already certifies the columns they read; otherwise after the wait, as with 0.  1: 215.4 - 216.3 alone, 218.3 - 219.1
+//                         on top of LEAN_BFLY (medians +0.1 %, ranges overlap both times): off by the project's rule.
+#ifndef MI355_RT1K_LEAN_BFLY
+#define MI355_RT1K_LEAN_BFLY 1
+#endif
+#ifndef MI355_RT1K_EARLY_B
+#define MI355_RT1K_EARLY_B 0
+#endif
 constexpr int RT1K_ROOT_SHIFT = 10, RT1K_ROOT_HI = 1024, RT1K_ROOT_LO = 1 << RT1K_ROOT_SHIFT;
 constexpr int rt1k_root_lds_elems(int tb, bool view, int N1) { return MI355_RT1K_ROOTS_LDS && tb == 32 && !view && N1 == 1024 ? RT1K_ROOT_HI + RT1K_ROOT_LO : 0; }
 

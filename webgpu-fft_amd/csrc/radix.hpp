@@ -50,12 +50,19 @@ template <int R> struct RootTable;
 constexpr int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 constexpr int bitrev(int x, int bits) { int y = 0; for (int i = 0; i < bits; ++i) { y = (y << 1) | (x & 1); x >>= 1; } return y; }
 
+// Butterfly policy of the power-of-two DFTs below: BflyStd is bfly32's own code.  A kernel may pass a policy with STD = false and a
+// `template <int K> static void run(cf& a, cf& b)` that writes some roots its own way, bit for bit the same outputs (kern_regtile.hpp
+// Rt1kBfly); every caller that names none compiles exactly as before.
+struct BflyStd { static constexpr bool STD = true; };
+
 // One DIT butterfly with the root W32^K (K in [0,16)): (a, b) <- (a + w*b, a - w*b).
 // The generic case is 6 FMAs (t = a + w*b in 4, then 2a - t in 2); K = 0, 8 are pure add/sub and K = 4, 12
 // use the (1 -+ i)/sqrt(2) structure.
-template <int K> MI_DEV void bfly32(cf& a, cf& b) {
+template <int K, class P = BflyStd> MI_DEV void bfly32(cf& a, cf& b) {
   static_assert(K >= 0 && K < 16, "root index");
-  if constexpr (K == 0) {
+  if constexpr (!P::STD) {
+    P::template run<K>(a, b);
+  } else if constexpr (K == 0) {
     cf t = a + b; b = a - b; a = t;
   } else if constexpr (K == 8) {                 // w = -i
     cf wb = mul_neg_i(b);
@@ -85,33 +92,33 @@ template <int K> MI_DEV void bfly32(cf& a, cf& b) {
 }
 
 // recursion helpers: fully unrolled (every index is a template constant, so v[] stays in VGPRs)
-template <int R, int M, int G, int K> struct DitInner {
+template <int R, int M, int G, int K, class P = BflyStd> struct DitInner {
   static MI_DEV void run(cf* t) {
-    bfly32<K*(32 / M)>(t[G + K], t[G + K + M / 2]);
-    if constexpr (K + 1 < M / 2) DitInner<R, M, G, K + 1>::run(t);
+    bfly32<K*(32 / M), P>(t[G + K], t[G + K + M / 2]);
+    if constexpr (K + 1 < M / 2) DitInner<R, M, G, K + 1, P>::run(t);
   }
 };
-template <int R, int M, int G> struct DitGroup {
+template <int R, int M, int G, class P = BflyStd> struct DitGroup {
   static MI_DEV void run(cf* t) {
-    DitInner<R, M, G, 0>::run(t);
-    if constexpr (G + M < R) DitGroup<R, M, G + M>::run(t);
+    DitInner<R, M, G, 0, P>::run(t);
+    if constexpr (G + M < R) DitGroup<R, M, G + M, P>::run(t);
   }
 };
-template <int R, int M> struct DitStage {
+template <int R, int M, class P = BflyStd> struct DitStage {
   static MI_DEV void run(cf* t) {
-    DitGroup<R, M, 0>::run(t);
-    if constexpr (M < R) DitStage<R, M * 2>::run(t);
+    DitGroup<R, M, 0, P>::run(t);
+    if constexpr (M < R) DitStage<R, M * 2, P>::run(t);
   }
 };
 
 // Forward R-point DFT, R in {1,2,4,8,16,32}, natural order in -> natural order out, in registers.
-template <int R> MI_DEV void fft_pow2(cf (&v)[R]) {
+template <int R, class P = BflyStd> MI_DEV void fft_pow2(cf (&v)[R]) {
   static_assert(R >= 1 && R <= 32 && (R & (R - 1)) == 0, "radix");
   if constexpr (R > 1) {
     cf t[R];
 #pragma unroll
     for (int i = 0; i < R; ++i) t[i] = v[bitrev(i, ilog2(R))];
-    DitStage<R, 2>::run(t);
+    DitStage<R, 2, P>::run(t);
 #pragma unroll
     for (int i = 0; i < R; ++i) v[i] = t[i];
   }
@@ -138,11 +145,11 @@ template <int R> MI_DEV void dft_odd(cf (&v)[R]) {
   for (int k = 0; k < R; ++k) v[k] = o[k];
 }
 
-template <int R> MI_DEV void fft_radix(cf (&v)[R]) {
+template <int R, class P = BflyStd> MI_DEV void fft_radix(cf (&v)[R]) {   // (P: butterflies of the power-of-two radices)
 #if MI355_EXP_NO_MATH
   return;
 #endif
-  if constexpr ((R & (R - 1)) == 0) fft_pow2<R>(v); else dft_odd<R>(v);
+  if constexpr ((R & (R - 1)) == 0) fft_pow2<R, P>(v); else dft_odd<R>(v);
 }
 
 }  // namespace mi355
