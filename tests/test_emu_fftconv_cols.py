@@ -4,37 +4,24 @@ The case table and its bars are fftconv_cols_cases.py's, shared with the GPU tie
 the route tag and 1 + K launches.  Then the planner alone on requests far beyond host memory (route, launches, workspace: the capability
 the route adds) and on the neighbours whose routes the switch must not move, the accuracy ladder, and the exec contract
 (exec_contract_cases.py's harness: guard bands catch a load or store outside a block's predicates) on a dense and a strided request."""
-import numpy as np
 import pytest
 
 import emu_harness as emu
-import exec_contract_cases as t
 import fftconv_cols_cases as cols
 import fftconv_linear_cases as lin
+import fftconv_ols_scaffold as scaffold
 import test_emu_accuracy as accuracy
 import test_emu_exec_contract as contract
 from test_emu_fftconv import _desc
 
 
-def _runner(monkeypatch):
-    def run(opts, x, out_floats, kernel, out_init=None):
-        desc, _ = _desc(opts)
-        return emu.run_plan(desc, x, out_floats, kernel=kernel, out_init=out_init)
-
-    def setenv(name, value):
-        monkeypatch.setenv("MI355_EMU_" + name, value)
-    return run, setenv
-
-
 @pytest.mark.parametrize("case", cols.CASES, ids=repr)
 def test_overlap_save(oracle, monkeypatch, case):
-    run, setenv = _runner(monkeypatch)
-    cols.check_case(run, setenv, oracle, case)
+    cols.ROUTE.check_case(*scaffold.emu_runner(monkeypatch), oracle, case)
 
 
 def test_strided_lanes_on_both_sides(oracle, monkeypatch):
-    run, setenv = _runner(monkeypatch)
-    cols.check_strided(run, setenv, oracle)
+    cols.ROUTE.check_strided(*scaffold.emu_runner(monkeypatch), oracle)
 
 
 # ---- planner only ------------------------------------------------------------------------------------------------------------------
@@ -52,10 +39,10 @@ def test_capability_long_lines_plan_to_the_route(n, kn, batch, K):
     """a complex line of 5000000 points (an error before the route: Bluestein axis above 2^22) and 256 lines of 2^20 points (12 launches and 9 GB of
     workspace before it): 1 + K launches and the K kernel spectra alone as workspace"""
     route, launches, work = _plan(n, kn, batch, K)
-    assert route.startswith("lines-mapped[N=") and cols.TAG in route, route
-    assert not any(f in route for f in cols.FORBIDDEN), route
+    assert route.startswith("lines-mapped[N=") and cols.ROUTE.tag in route, route
+    assert not any(f in route for f in cols.ROUTE.forbidden), route
     assert launches == 1 + K, (route, launches)
-    P = int(route.split(cols.TAG + "N=")[1].split(",")[0])
+    P = int(route.split(cols.ROUTE.tag + "N=")[1].split(",")[0])
     L = int(route.split(",L=")[1].split("]")[0])
     assert L == P - (kn - 1) and L >= 2, route
     assert work < 1 << 20 and work >= K * P * 8, (route, work)
@@ -65,7 +52,7 @@ def test_requests_that_were_an_error(monkeypatch):
     """exact-length domains above 2^22 that are not 13-smooth: a route where the planner raised Unsupported"""
     for n, kn, batch in ((5000000, 255, 16), (4194304, 255, 4), (6000000, 33, 2)):
         route, launches, work = _plan(n, kn, batch)
-        assert cols.TAG in route and launches == 2 and work < 1 << 20, (route, launches, work)
+        assert cols.ROUTE.tag in route and launches == 2 and work < 1 << 20, (route, launches, work)
     monkeypatch.setenv("MI355FFT_CONV_OLS", "0")
     with pytest.raises(emu.EmuError) as e:
         _plan(5000000, 255, 16)
@@ -75,11 +62,11 @@ def test_requests_that_were_an_error(monkeypatch):
 def test_the_default_rule():
     """the block length: the smallest power of two >= 8 (M - 1), from 2048 up to 4096"""
     for kn, P in ((1, 2048), (31, 2048), (129, 2048), (255, 2048), (257, 2048), (258, 4096), (513, 4096)):
-        assert f"{cols.TAG}N={P},L={P - kn + 1}]" in _plan(100000, kn, 4)[0], (kn, P)
+        assert f"{cols.ROUTE.tag}N={P},L={P - kn + 1}]" in _plan(100000, kn, 4)[0], (kn, P)
 
 
 def test_the_switch_and_the_neighbours(monkeypatch):
-    tag = cols.TAG
+    tag = cols.ROUTE.tag
     # the switch: 0 gives what the planner gave before the route, a block length forces it below the default rule's threshold
     assert tag in _plan(100000, 129, 4)[0]
     monkeypatch.setenv("MI355FFT_CONV_OLS", "0")
@@ -116,9 +103,7 @@ def test_the_switch_and_the_neighbours(monkeypatch):
 
 @pytest.mark.parametrize("case", cols.ACCURACY_CASES, ids=repr)
 def test_accuracy(oracle, monkeypatch, case):
-    for k, v in case.emu_env.items():
-        monkeypatch.setenv("MI355_EMU_" + k, v)
-    assert case.route_ok(emu.route_of(t.desc_of(case.opts)[0])[0])
+    scaffold.emu_planned(monkeypatch, case)
     accuracy.test_accuracy(oracle, monkeypatch, case)
 
 
@@ -127,7 +112,5 @@ def test_accuracy(oracle, monkeypatch, case):
 @pytest.mark.parametrize("case", cols.CONTRACT_CASES, ids=repr)
 def test_exec_contract(oracle, monkeypatch, case):
     """guard bands, exec offsets of 8 (mod 16), a workspace of 0xFF bytes, input and kernel untouched; no skip by route: the emulator plans both"""
-    for k, v in case.emu_env.items():
-        monkeypatch.setenv("MI355_EMU_" + k, v)
-    assert case.route_ok(emu.route_of(t.desc_of(case.opts)[0])[0])
+    scaffold.emu_planned(monkeypatch, case)
     contract.test_exec_contract(oracle, monkeypatch, case)

@@ -3,36 +3,22 @@
 The case table and its bars are fftconv_ols_cases.py's, shared with the GPU tier: float64 references, the same request with the switch at 0,
 the route tag and 1 + K launches.  Then the planner alone on requests far beyond host memory (route, launches, workspace) and on the
 neighbours whose routes the switch must not move, and the exec contract (exec_contract_cases.py's harness) on a dense and a strided request."""
-import numpy as np
 import pytest
 
 import emu_harness as emu
-import exec_contract_cases as t
 import fftconv_ols_cases as ols
+import fftconv_ols_scaffold as scaffold
 import test_emu_exec_contract as contract
 from test_emu_fftconv_real import _desc, _opts
 
 
-def _runner(monkeypatch):
-    def run(opts, x, out_floats, kernel, out_init=None):
-        desc, _ = _desc(opts)
-        kernel = np.concatenate(kernel) if isinstance(kernel, list) else kernel
-        return emu.run_plan(desc, x, out_floats, kernel=kernel, out_init=out_init)
-
-    def setenv(name, value):
-        monkeypatch.setenv("MI355_EMU_" + name, value)
-    return run, setenv
-
-
 @pytest.mark.parametrize("case", ols.CASES, ids=repr)
 def test_overlap_save(oracle, monkeypatch, case):
-    run, setenv = _runner(monkeypatch)
-    ols.check_case(run, setenv, oracle, case)
+    ols.ROUTE.check_case(*scaffold.emu_runner(monkeypatch), oracle, case)
 
 
 def test_strided_lanes_on_both_sides(oracle, monkeypatch):
-    run, setenv = _runner(monkeypatch)
-    ols.check_strided(run, setenv, oracle)
+    ols.ROUTE.check_strided(*scaffold.emu_runner(monkeypatch), oracle)
 
 
 # ---- planner only ------------------------------------------------------------------------------------------------------------------
@@ -100,7 +86,5 @@ def test_the_switch_and_the_neighbours(monkeypatch):
 @pytest.mark.parametrize("case", ols.CONTRACT_CASES, ids=repr)
 def test_exec_contract(oracle, monkeypatch, case):
     """guard bands, exec offsets of 8 (mod 16), a workspace of 0xFF bytes, input and kernel untouched; no skip by route: the emulator plans both"""
-    for k, v in case.emu_env.items():
-        monkeypatch.setenv("MI355_EMU_" + k, v)
-    assert case.route_ok(emu.route_of(t.desc_of(case.opts)[0])[0])
+    scaffold.emu_planned(monkeypatch, case)
     contract.test_exec_contract(oracle, monkeypatch, case)

@@ -8,7 +8,7 @@ strided request."""
 import pytest
 
 import emu_harness as emu
-import exec_contract_cases as t
+import fftconv_ols_scaffold as scaffold
 import fftconv_rtiles_cases as rtiles
 import test_emu_accuracy as accuracy
 import test_emu_exec_contract as contract
@@ -16,30 +16,17 @@ from mi355fft import _abi
 from test_emu_fftconv_real import _desc, _opts
 
 
-def _runner(monkeypatch):
-    def run(opts, x, out_floats, kernel, out_init=None):
-        desc, _ = _desc(opts)
-        return emu.run_plan(desc, x, out_floats, kernel=kernel, out_init=out_init)
-
-    def setenv(name, value):
-        monkeypatch.setenv("MI355_EMU_" + name, value)
-    return run, setenv
-
-
 @pytest.mark.parametrize("case", rtiles.CASES, ids=repr)
 def test_overlap_save_real_tiles(oracle, monkeypatch, case):
-    run, setenv = _runner(monkeypatch)
-    rtiles.check_case(run, setenv, oracle, case)
+    rtiles.ROUTE.check_case(*scaffold.emu_runner(monkeypatch), oracle, case)
 
 
 def test_strided_lanes_on_both_sides(oracle, monkeypatch):
-    run, setenv = _runner(monkeypatch)
-
     def unsupported(opts):
         with pytest.raises(emu.EmuError) as e:
             emu.plan_only(_desc(opts)[0])
         assert rtiles.UNSUPPORTED in str(e.value) and e.value.code == _abi.ERR_UNSUPPORTED
-    rtiles.check_strided(run, setenv, oracle, unsupported)
+    rtiles.ROUTE.check_strided(*scaffold.emu_runner(monkeypatch), oracle, unsupported)
 
 
 # ---- planner only ------------------------------------------------------------------------------------------------------------------
@@ -57,37 +44,37 @@ def test_capability_images_plan_to_the_route(monkeypatch, shape, ks, batch, K, b
     """1 + K launches and the K kernel spectra alone as workspace for any image; with the switch at 0 rconv[K] on the exact-length domain with a
     workspace of several whole-image spectra"""
     route, launches, work = _plan(shape, ks, batch, K, boundary)
-    assert route.startswith(f"tiles-rspectrum[N={P}x{P}] ") and rtiles.tag_of(P, ks) in route, route
-    assert not any(f in route for f in rtiles.FORBIDDEN), route
+    assert route.startswith(f"tiles-rspectrum[N={P}x{P}] ") and rtiles.ROUTE.tag_of(P, ks) in route, route
+    assert not any(f in route for f in rtiles.ROUTE.forbidden), route
     assert launches == 1 + K, (route, launches)
     assert work < 1 << 20 and work >= K * P * P * 8, (route, work)
     monkeypatch.setenv("MI355FFT_RCONV_OLS2D", "0")
     route0, launches0, work0 = _plan(shape, ks, batch, K, boundary)
-    assert rtiles.TAG not in route0 and f"rconv[K={K}]" in route0, route0
+    assert rtiles.ROUTE.tag not in route0 and f"rconv[K={K}]" in route0, route0
     assert launches0 > 1 + K and work0 > 64 << 20, (route0, launches0, work0)
 
 
 def test_the_default_rule():
     """the tile edge: 64 up to kernels of 17 points on their longer axis, 128 up to 33"""
     for ks, P in (((1, 1), 64), ((9, 9), 64), ((17, 3), 64), ((3, 17), 64), ((18, 3), 128), ((3, 18), 128), ((33, 33), 128)):
-        assert rtiles.tag_of(P, ks) in _plan((300, 200), ks, 2)[0], (ks, P)
+        assert rtiles.ROUTE.tag_of(P, ks) in _plan((300, 200), ks, 2)[0], (ks, P)
 
 
 def test_the_switch_and_the_neighbours(monkeypatch):
-    tag = rtiles.TAG
+    tag = rtiles.ROUTE.tag
     # the switch: 0 gives what the planner gave before the route, a tile edge forces it where the default rule does not go
     assert tag in _plan((300, 200), (9, 9), 2)[0]
     monkeypatch.setenv("MI355FFT_RCONV_OLS2D", "0")
     route = _plan((300, 200), (9, 9), 2)[0]
     assert "rconv[K=1]" in route and tag not in route, route
     monkeypatch.setenv("MI355FFT_RCONV_OLS2D", "64")
-    assert rtiles.tag_of(64, (9, 9)) in _plan((20, 30), (9, 9), 3, boundary="linear-full")[0]
-    assert rtiles.tag_of(64, (63, 3)) in _plan((70, 200), (63, 3), 1)[0]         # the longest kernel a tile takes on an axis: L >= 2
+    assert rtiles.ROUTE.tag_of(64, (9, 9)) in _plan((20, 30), (9, 9), 3, boundary="linear-full")[0]
+    assert rtiles.ROUTE.tag_of(64, (63, 3)) in _plan((70, 200), (63, 3), 1)[0]         # the longest kernel a tile takes on an axis: L >= 2
     assert tag not in _plan((70, 200), (64, 3), 1)[0]                           # L0 = 1: the routes below
     assert tag not in _plan((200, 70), (3, 64), 1)[0]
     assert tag not in _plan((64, 64), (9, 9), 2, boundary="circular")[0]        # a forced tile leaves circular requests alone
     monkeypatch.setenv("MI355FFT_RCONV_OLS2D", "128")
-    assert rtiles.tag_of(128, (9, 9)) in _plan((300, 200), (9, 9), 2)[0]
+    assert rtiles.ROUTE.tag_of(128, (9, 9)) in _plan((300, 200), (9, 9), 2)[0]
     for bad in ("32", "100", "256"):                                            # not a tile edge of the route: the other routes
         monkeypatch.setenv("MI355FFT_RCONV_OLS2D", bad)
         assert tag not in _plan((300, 200), (9, 9), 2)[0], bad
@@ -134,9 +121,7 @@ def test_the_switch_and_the_neighbours(monkeypatch):
 
 @pytest.mark.parametrize("case", rtiles.ACCURACY_CASES, ids=repr)
 def test_accuracy(oracle, monkeypatch, case):
-    for k, v in case.emu_env.items():
-        monkeypatch.setenv("MI355_EMU_" + k, v)
-    assert case.route_ok(emu.route_of(t.desc_of(case.opts)[0])[0])
+    scaffold.emu_planned(monkeypatch, case)
     accuracy.test_accuracy(oracle, monkeypatch, case)
 
 
@@ -145,7 +130,5 @@ def test_accuracy(oracle, monkeypatch, case):
 @pytest.mark.parametrize("case", rtiles.CONTRACT_CASES, ids=repr)
 def test_exec_contract(oracle, monkeypatch, case):
     """guard bands, exec offsets of 8 (mod 16), a workspace of 0xFF bytes, input and kernel untouched; no skip by route: the emulator plans both"""
-    for k, v in case.emu_env.items():
-        monkeypatch.setenv("MI355_EMU_" + k, v)
-    assert case.route_ok(emu.route_of(t.desc_of(case.opts)[0])[0])
+    scaffold.emu_planned(monkeypatch, case)
     contract.test_exec_contract(oracle, monkeypatch, case)

@@ -8,46 +8,33 @@ dense and a strided request."""
 import pytest
 
 import emu_harness as emu
-import exec_contract_cases as t
+import fftconv_ols_scaffold as scaffold
 import fftconv_tiles_cases as tiles
 import test_emu_accuracy as accuracy
 import test_emu_exec_contract as contract
 from test_emu_fftconv import _desc
 
 
-def _runner(monkeypatch):
-    def run(opts, x, out_floats, kernel, out_init=None):
-        desc, _ = _desc(opts)
-        return emu.run_plan(desc, x, out_floats, kernel=kernel, out_init=out_init)
-
-    def setenv(name, value):
-        monkeypatch.setenv("MI355_EMU_" + name, value)
-    return run, setenv
-
-
 @pytest.mark.parametrize("case", tiles.CASES, ids=repr)
 def test_overlap_save_tiles(oracle, monkeypatch, case):
-    run, setenv = _runner(monkeypatch)
-    tiles.check_case(run, setenv, oracle, case)
+    tiles.ROUTE.check_case(*scaffold.emu_runner(monkeypatch), oracle, case)
 
 
 def test_strided_lanes_on_both_sides(oracle, monkeypatch):
-    run, setenv = _runner(monkeypatch)
-    tiles.check_strided(run, setenv, oracle)
+    tiles.ROUTE.check_strided(*scaffold.emu_runner(monkeypatch), oracle)
 
 
 # ---- planner only ------------------------------------------------------------------------------------------------------------------
 
 def _plan(shape, ks, batch, K=1, boundary="linear-same", mode="convolution", layout=None, **fc):
-    opts = tiles.options(shape, ks, batch, K, mode, boundary)
+    opts = scaffold.options(shape, ks, batch, K, mode, boundary)
     opts["fftConv"].update(fc)
     if layout:
         opts["layout"] = layout
     return emu.plan_only(_desc(opts)[0])
 
 
-def _tag(P, ks):
-    return f"{tiles.TAG}N={P}x{P},L={P - ks[0] + 1}x{P - ks[1] + 1}]"
+_tag = tiles.ROUTE.tag_of
 
 
 @pytest.mark.parametrize("shape,ks,batch,K,boundary,P,before", [
@@ -60,12 +47,12 @@ def test_capability_images_plan_to_the_route(monkeypatch, shape, ks, batch, K, b
     1 + K launches and the K kernel spectra alone as workspace; with the switch at 0 the planner's earlier route and launch count"""
     route, launches, work = _plan(shape, ks, batch, K, boundary)
     assert route.startswith(f"tiles-spectrum[N={P}x{P}] ") and _tag(P, ks) in route, route
-    assert not any(f in route for f in tiles.FORBIDDEN), route
+    assert not any(f in route for f in tiles.ROUTE.forbidden), route
     assert launches == 1 + K, (route, launches)
     assert work < 1 << 20 and work >= K * P * P * 8, (route, work)
     monkeypatch.setenv("MI355FFT_CONV_OLS2D", "0")
     route0, launches0, work0 = _plan(shape, ks, batch, K, boundary)
-    assert tiles.TAG not in route0 and before[0] in route0 and f"fftconv[K={K}]" in route0, route0
+    assert tiles.ROUTE.tag not in route0 and before[0] in route0 and f"fftconv[K={K}]" in route0, route0
     assert before[1] is None or launches0 == before[1], (route0, launches0)
     assert work0 > 256 << 20, (route0, work0)
 
@@ -77,7 +64,7 @@ def test_the_default_rule():
 
 
 def test_the_switch_and_the_neighbours(monkeypatch):
-    tag = tiles.TAG
+    tag = tiles.ROUTE.tag
     # the switch: 0 gives what the planner gave before the route, a tile edge forces it where the default rule does not go
     assert tag in _plan((300, 200), (9, 9), 2)[0]
     monkeypatch.setenv("MI355FFT_CONV_OLS2D", "0")
@@ -127,9 +114,7 @@ def test_the_switch_and_the_neighbours(monkeypatch):
 
 @pytest.mark.parametrize("case", tiles.ACCURACY_CASES, ids=repr)
 def test_accuracy(oracle, monkeypatch, case):
-    for k, v in case.emu_env.items():
-        monkeypatch.setenv("MI355_EMU_" + k, v)
-    assert case.route_ok(emu.route_of(t.desc_of(case.opts)[0])[0])
+    scaffold.emu_planned(monkeypatch, case)
     accuracy.test_accuracy(oracle, monkeypatch, case)
 
 
@@ -138,7 +123,5 @@ def test_accuracy(oracle, monkeypatch, case):
 @pytest.mark.parametrize("case", tiles.CONTRACT_CASES, ids=repr)
 def test_exec_contract(oracle, monkeypatch, case):
     """guard bands, exec offsets of 8 (mod 16), a workspace of 0xFF bytes, input and kernel untouched; no skip by route: the emulator plans both"""
-    for k, v in case.emu_env.items():
-        monkeypatch.setenv("MI355_EMU_" + k, v)
-    assert case.route_ok(emu.route_of(t.desc_of(case.opts)[0])[0])
+    scaffold.emu_planned(monkeypatch, case)
     contract.test_exec_contract(oracle, monkeypatch, case)

@@ -9,6 +9,7 @@ import pytest
 
 import fftconv_cols_cases as cols
 import fftconv_linear_cases as lin
+import fftconv_ols_scaffold as scaffold
 import test_gpu_accuracy as accuracy
 import test_gpu_exec_contract as contract
 from test_gpu_exec_contract import dev, fft, harness  # noqa: F401  (fixtures)
@@ -17,40 +18,28 @@ from test_gpu_parity import run_plan
 pytestmark = pytest.mark.gpu
 
 
-def _runner(fft, dev, monkeypatch):
-    def run(opts, x, out_floats, kernel, out_init=None):
-        got, (route, launches) = run_plan(fft, dev, opts, x, out_floats, kernel=kernel, out_init=out_init)
-        return got, route, launches
-
-    def setenv(name, value):
-        monkeypatch.setenv("MI355FFT_" + name, value)
-    return run, setenv
-
-
 @pytest.mark.parametrize("case", cols.CASES, ids=repr)
 def test_overlap_save(fft, dev, oracle, monkeypatch, case):
-    run, setenv = _runner(fft, dev, monkeypatch)
-    cols.check_case(run, setenv, oracle, case)
+    cols.ROUTE.check_case(*scaffold.gpu_runner(fft, dev, monkeypatch), oracle, case)
 
 
 def test_strided_lanes_on_both_sides(fft, dev, oracle, monkeypatch):
-    run, setenv = _runner(fft, dev, monkeypatch)
-    cols.check_strided(run, setenv, oracle)
+    cols.ROUTE.check_strided(*scaffold.gpu_runner(fft, dev, monkeypatch), oracle)
 
 
 def test_capability_a_line_of_5000000_points(fft, dev):
     """1 x 5000000 (*) 255 linear-same (40 MB each way; the planner raised Unsupported before the route): three windows of 4096 outputs, the
     head, one straddling a block boundary and the tail, against float64 direct sums"""
     n, kn = 5000000, 255
-    x, h = cols._rand(n, 0x0CF1), cols._rand(kn, 0x0CF2)
+    x, h = cols.ROUTE.rand(n, 0x0CF1), cols.ROUTE.rand(kn, 0x0CF2)
     opts = lin.options((n, kn, "linear-same", "convolution", 1, "kernel-major", None), 1)
     got, (route, launches) = run_plan(fft, dev, opts, x, 2 * n, kernel=h)
-    assert cols.TAG in route and launches == 2 and not any(f in route for f in cols.FORBIDDEN), (route, launches)
+    assert cols.ROUTE.tag in route and launches == 2 and not any(f in route for f in cols.ROUTE.forbidden), (route, launches)
     L = int(route.split(",L=")[1].split("]")[0])
     mid = (n // 2) // L * L - (kn - 1) // 2          # output index of the first result of a block
     got = got.reshape(n, 2)
     for lo in (0, mid - 2048, n - 4096):
-        want = cols.direct_same_conv(x, h, n, kn, lo, lo + 4096)
+        want = cols.ROUTE.direct_same_conv(x, h, (n,), (kn,), (lo,), (lo + 4096,))
         g = got[lo:lo + 4096, 0].astype(np.float64) + 1j * got[lo:lo + 4096, 1]
         err = np.abs(g - want)
         rel = float(np.linalg.norm(g - want) / np.linalg.norm(want))
@@ -63,7 +52,7 @@ def test_full_size_against_the_earlier_route_on_the_device(fft, dev, monkeypatch
     switch's 0 restores"""
     n, kn, batch = 1 << 20, 255, 32
     opts = lin.options((n, kn, "linear-same", "convolution", 1, "kernel-major", None), batch)
-    h = cols._rand(kn, 0x0CF3)
+    h = cols.ROUTE.rand(kn, 0x0CF3)
     inp = dev.createBuffer({"size": 8 * n * batch})
     dev.fillRandom(inp, 0, 2 * n, batch, 0xC1F2)
     outs, routes = [], []
@@ -79,8 +68,8 @@ def test_full_size_against_the_earlier_route_on_the_device(fft, dev, monkeypatch
         routes.append(plan.describe())
         plan.destroy()
         outs.append(out)
-    assert cols.TAG in routes[0][0] and routes[0][1] == 2, routes[0]
-    assert "fftconv[K=1]" in routes[1][0] and cols.TAG not in routes[1][0], routes[1]
+    assert cols.ROUTE.tag in routes[0][0] and routes[0][1] == 2, routes[0]
+    assert "fftconv[K=1]" in routes[1][0] and cols.ROUTE.tag not in routes[1][0], routes[1]
     count = 2 * n * batch
     ref = dev.sumsq(outs[1], 0, count)
     diff = dev.diffSumsq(outs[0], 0, outs[1], 0, 1.0, count)

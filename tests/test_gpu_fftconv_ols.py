@@ -6,35 +6,22 @@ and the exec contract (test_gpu_exec_contract.py's harness) on a dense and a str
 import numpy as np
 import pytest
 
-import exec_contract_cases as t
 import fftconv_ols_cases as ols
+import fftconv_ols_scaffold as scaffold
 import test_gpu_exec_contract as contract
 from test_emu_fftconv_real import _check, _opts, _rand, _want
 from test_gpu_exec_contract import dev, fft, harness  # noqa: F401  (fixtures)
-from test_gpu_parity import run_plan
 
 pytestmark = pytest.mark.gpu
 
 
-def _runner(fft, dev, monkeypatch):
-    def run(opts, x, out_floats, kernel, out_init=None):
-        got, (route, launches) = run_plan(fft, dev, opts, x, out_floats, kernel=kernel, out_init=out_init)
-        return got, route, launches
-
-    def setenv(name, value):
-        monkeypatch.setenv("MI355FFT_" + name, value)
-    return run, setenv
-
-
 @pytest.mark.parametrize("case", ols.CASES, ids=repr)
 def test_overlap_save(fft, dev, oracle, monkeypatch, case):
-    run, setenv = _runner(fft, dev, monkeypatch)
-    ols.check_case(run, setenv, oracle, case)
+    ols.ROUTE.check_case(*scaffold.gpu_runner(fft, dev, monkeypatch), oracle, case)
 
 
 def test_strided_lanes_on_both_sides(fft, dev, oracle, monkeypatch):
-    run, setenv = _runner(fft, dev, monkeypatch)
-    ols.check_strided(run, setenv, oracle)
+    ols.ROUTE.check_strided(*scaffold.gpu_runner(fft, dev, monkeypatch), oracle)
 
 
 @pytest.mark.parametrize("use_graph", [False, True])

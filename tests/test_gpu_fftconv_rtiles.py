@@ -8,6 +8,7 @@ and a strided request."""
 import numpy as np
 import pytest
 
+import fftconv_ols_scaffold as scaffold
 import fftconv_rtiles_cases as rtiles
 import test_gpu_accuracy as accuracy
 import test_gpu_exec_contract as contract
@@ -18,30 +19,17 @@ from test_gpu_parity import run_plan
 pytestmark = pytest.mark.gpu
 
 
-def _runner(fft, dev, monkeypatch):
-    def run(opts, x, out_floats, kernel, out_init=None):
-        got, (route, launches) = run_plan(fft, dev, opts, x, out_floats, kernel=kernel, out_init=out_init)
-        return got, route, launches
-
-    def setenv(name, value):
-        monkeypatch.setenv("MI355FFT_" + name, value)
-    return run, setenv
-
-
 @pytest.mark.parametrize("case", rtiles.CASES, ids=repr)
 def test_overlap_save_real_tiles(fft, dev, oracle, monkeypatch, case):
-    run, setenv = _runner(fft, dev, monkeypatch)
-    rtiles.check_case(run, setenv, oracle, case)
+    rtiles.ROUTE.check_case(*scaffold.gpu_runner(fft, dev, monkeypatch), oracle, case)
 
 
 def test_strided_lanes_on_both_sides(fft, dev, oracle, monkeypatch):
-    run, setenv = _runner(fft, dev, monkeypatch)
-
     def unsupported(opts):
         with pytest.raises(Exception) as e:
             fft.createPlan(dev, opts)
         assert rtiles.UNSUPPORTED in str(e.value), e.value
-    rtiles.check_strided(run, setenv, oracle, unsupported)
+    rtiles.ROUTE.check_strided(*scaffold.gpu_runner(fft, dev, monkeypatch), oracle, unsupported)
 
 
 def test_capability_images_of_1024x1024_points(fft, dev):
@@ -52,14 +40,14 @@ def test_capability_images_of_1024x1024_points(fft, dev):
     n = shape[0] * shape[1]
     x, h = _rand(n * batch, 0x7EF1), _rand(ks[0] * ks[1], 0x7EF2)
     got, (route, launches) = run_plan(fft, dev, _opts(list(shape), list(ks), batch, boundary="linear-same"), x, n * batch, kernel=h)
-    assert rtiles.TAG in route and launches == 2 and not any(f in route for f in rtiles.FORBIDDEN), (route, launches)
+    assert rtiles.ROUTE.tag in route and launches == 2 and not any(f in route for f in rtiles.ROUTE.forbidden), (route, launches)
     L0, L1 = (int(v) for v in route.split(",L=")[1].split("]")[0].split("x"))
     seam0, seam1 = L0 - (ks[0] - 1) // 2, L1 - (ks[1] - 1) // 2        # output index of the first result of the second tile on each axis
     got = np.asarray(got).reshape(batch, shape[1], shape[0])
     for b in (0, batch - 1):
         for lo in ((0, 0), (seam0 - 24, 500), (500, seam1 - 24), (500, seam1 + L1 - 24), (seam0 - 24, seam1 - 24), (shape[0] - 48, shape[1] - 48)):
             hi = (lo[0] + 48, lo[1] + 48)
-            want = rtiles.direct_same_conv(x[n * b:n * (b + 1)], h, shape, ks, lo, hi)
+            want = rtiles.ROUTE.direct_same_conv(x[n * b:n * (b + 1)], h, shape, ks, lo, hi)
             g = got[b, lo[1]:hi[1], lo[0]:hi[0]].astype(np.float64)
             err = np.abs(g - want)
             rel = float(np.linalg.norm(g - want) / np.linalg.norm(want))
@@ -70,14 +58,14 @@ def test_capability_images_of_1024x1024_points(fft, dev):
 def test_plan_destroyed_and_created_again(fft, dev, monkeypatch):
     """the first case of the table: create, exec, destroy, create again, exec twice into one buffer"""
     case = rtiles.CASES[0]
-    x, h, want = rtiles.data(case)
-    monkeypatch.setenv("MI355FFT_" + rtiles.SWITCH, str(case.P))
+    x, h, want = rtiles.ROUTE.data(case)
+    monkeypatch.setenv("MI355FFT_" + rtiles.ROUTE.switch, str(case.P))
     inp = dev.createBuffer({"size": x.nbytes})
     dev.queue.writeBuffer(inp, 0, x)
     out = dev.createBuffer({"size": 4 * want.size})
     for round_, execs in enumerate((1, 2)):
         plan = fft.createPlan(dev, case.opts)
-        rtiles.assert_route(case, *plan.describe())
+        rtiles.ROUTE.assert_route(case, *plan.describe())
         for _ in range(execs):
             enc = dev.createCommandEncoder()
             plan.exec(enc, {"input": inp, "output": out, "kernel": h})

@@ -11,7 +11,8 @@ Two builds of the planner plan alike when their snapshots are equal:
 
 Without MI355_EMU_LIB the library is built from this tree (tests/emu/Makefile).  --full writes the dumps themselves.  --env NAME=VALUE
 adds a planner switch to every environment (a build that does not know the switch plans as ever): MI355FFT_RCONV_OLS=0 or MI355FFT_CONV_OLS=0
-on both sides compares a planner with that overlap-save route switched off against one without it.
+on both sides compares a planner with that overlap-save route switched off against one without it.  The fftconv corpora are also planned
+with each overlap-save switch forcing a block (CONV_ENVS); the other corpora never read those switches.
 """
 import argparse
 import hashlib
@@ -27,6 +28,9 @@ from mi355fft import _abi  # noqa: E402
 
 ENVS = [{}, {"MI355FFT_CONV_PAD": "0"}, {"MI355FFT_CONV_PIPELINE": "0"}, {"MI355FFT_CONV_LINES": "0"}, {"MI355FFT_RCONV_FUSED": "0"},
         {"MI355FFT_RCONV_FUSED": "2"}, {"MI355FFT_FORCE_GENERIC": "1"}, {"MI355FFT_FUSE_VIEWS": "0"}]
+# fftconv only: a forced block on each overlap-save route, and a value that is no legal tile (the switch decoder's reject path)
+CONV_ENVS = [{"MI355FFT_CONV_OLS": "256"}, {"MI355FFT_RCONV_OLS": "256"}, {"MI355FFT_CONV_OLS2D": "64"}, {"MI355FFT_RCONV_OLS2D": "128"},
+             {"MI355FFT_CONV_OLS2D": "100"}]
 BOUNDARIES = ["circular", "linear-full", "linear-same", "linear-valid"]
 MODES = ["convolution", "correlation"]
 LAYOUTS = ["kernel-major", "batch-major"]
@@ -185,6 +189,20 @@ def conv_corpus(real):
         add([1 << 20], [255], "linear-same", K=4, batch=8)
         add([700000], [255], "linear-valid", "correlation", K=1, batch=4)
         add([20000], [513], "linear-same", K=1, batch=4, layout="batch-major")
+    # rank-2 images with small kernels (overlap-save tiles by default: MI355FFT_CONV_OLS2D for complex data, MI355FFT_RCONV_OLS2D for real; P = 64, P = 128,
+    # and an even kernel with an odd number of tiles on axis 1)
+    tile_requests = (([300, 200], [9, 9]), ([300, 200], [31, 17]), ([150, 130], [8, 5]))
+    for (shape, ks), bd, md, K, lay in itertools.product(tile_requests, BOUNDARIES[1:], MODES, (1, 3), LAYOUTS):
+        add(shape, ks, bd, md, K=K, layout=lay)
+    for (shape, ks), (bd, md), v in itertools.product(tile_requests, (("linear-full", "convolution"), ("linear-same", "correlation"), ("linear-valid", "correlation")),
+                                                     side_variants()):
+        add(shape, ks, bd, md, **v)
+    # their neighbours, which stay off the tiles: a domain of 16384 points, a kernel beyond 33 points on an axis, a circular request
+    for bd, md, K in itertools.product(BOUNDARIES[1:], MODES, (1, 3)):
+        add([120, 120], [9, 9], bd, md, K=K)
+        add([300, 200], [34, 3], bd, md, K=K)
+    for md, K in itertools.product(MODES, (1, 3)):
+        add([256, 256], [9, 9], "circular", md, K=K)
     return cases
 
 
@@ -257,19 +275,21 @@ def real_sides_corpus():
 
 
 def corpus():
+    """(name, descriptor, environments) of every case."""
     seen, cases = set(), []
-    for name, desc in conv_corpus(False) + conv_corpus(True) + c2c_corpus() + real_sides_corpus():
-        if name not in seen:      # the name spells out every parameter: a repeated name is a repeated case
-            seen.add(name)
-            cases.append((name, desc))
+    for envs, group in ((ENVS + CONV_ENVS, conv_corpus(False) + conv_corpus(True)), (ENVS, c2c_corpus() + real_sides_corpus())):
+        for name, desc in group:
+            if name not in seen:      # the name spells out every parameter: a repeated name is a repeated case
+                seen.add(name)
+                cases.append((name, desc, envs))
     return cases
 
 
 def plan_case(job):
     import emu_harness
-    name, desc, full = job
+    name, desc, envs, full = job
     lines = []
-    for env in ENVS:
+    for env in envs:
         for k in [k for k in os.environ if k.startswith("MI355FFT_") or k.startswith("MI355_EMU_") and k != "MI355_EMU_LIB"]:
             del os.environ[k]
         os.environ.update(EXTRA_ENV)
@@ -290,7 +310,7 @@ def snapshot(full, jobs):
     emu_harness.lib()      # built (if need be) once, before the workers start
     cases = corpus()
     with multiprocessing.Pool(jobs) as pool:
-        chunks = pool.map(plan_case, [(n, d, full) for n, d in cases], chunksize=16)
+        chunks = pool.map(plan_case, [(n, d, e, full) for n, d, e in cases], chunksize=16)
     return len(cases), [line for chunk in chunks for line in chunk]
 
 
@@ -306,7 +326,8 @@ def main():
     if a.compare:
         la, lb = (open(p).read().splitlines() for p in a.compare)
         diff = [(x, y) for x, y in itertools.zip_longest(la, lb) if x != y]
-        print("planner IR: %d cases x %d environments = %d plans compared" % (len(la) // len(ENVS), len(ENVS), len(la)))
+        plans = [x for x in la if " | " in x]      # (a --full snapshot carries the dumps between them)
+        print("planner IR: %d cases, %d plans compared" % (len({x.split(" | ")[0] for x in plans}), len(plans)))
         print("identical" if not diff else "DIFFERENT: %d lines" % len(diff))
         for x, y in diff[:40]:
             print("-", x)
@@ -315,7 +336,7 @@ def main():
     n, lines = snapshot(a.full, a.jobs)
     out = open(a.output, "w") if a.output else sys.stdout
     out.write("\n".join(lines) + "\n")
-    print("%d cases x %d environments" % (n, len(ENVS)), file=sys.stderr)
+    print("%d cases, %d plans (%d environments, %d more for fftconv)" % (n, len(lines), len(ENVS), len(CONV_ENVS)), file=sys.stderr)
     return 0
 
 

@@ -114,8 +114,8 @@ inline TilesArgs tiles_args_of(const Step& s, void* const ptr[STEP_PTRS]) {
   ta.num_tiles = s.i[LS_TILES]; ta.scale = s.f[F_SCALE];
   ta.conj = (int)s.i[LS_CONJ]; ta.spectrum_only = s.i[LS_MODE] == LM_TILES_SPECTRUM || s.i[LS_MODE] == LM_TILES_RSPECTRUM;
   for (int x = 0; x < 2; ++x) {
-    const auto half = [x](int64_t v) { return (int)(uint32_t)((uint64_t)v >> (32 * x)); };
-    ta.ax[x] = TileAxis{half(s.i[LS_OLS_FN]), half(s.i[LS_OLS_PLIM]), half(s.i[LS_OLS_NB]), half(s.i[LS_OLS_L]), half(s.i[LS_OLS_W0]), half(s.i[LS_OLS_PRE])};
+    const OlsAxis g = ols_axis_of(s.i, x);
+    ta.ax[x] = TileAxis{(int)g.fN, (int)g.plim, (int)g.nb, (int)g.L, (int)g.w0, (int)g.pre};
   }
   ta.imap = s.imap; ta.omap = s.omap;
   return ta;
@@ -427,19 +427,15 @@ bool dispatch_step(const Step& s, void* const ptr[STEP_PTRS], L& l, LinesFn&& li
       if (a.real_mode == LM_RCONV) {   // real fftconv line: p[LP_RCONV_SPECTRUM] (tw_hi) is the packed kernel spectrum; the HI roots sit directly behind the 1024 LO roots (one table)
         a.conj = (int)s.i[LS_CONJ]; a.rconv_split = (int)s.i[LS_RCONV_SPLIT]; a.rconv_padD = (int)s.i[LS_RCONV_PADD];
       }
-      if (a.real_mode == LM_RCONV_OLS) {  // its overlap-save form: no padded domain; the block geometry in an argument block of its own (kern_lines.hpp RconvOls)
+      if (a.real_mode == LM_RCONV_OLS || a.real_mode == LM_CONV_OLS) {
+        // overlap-save on real lines (LM_RCONV's pointers) and on complex ones (p[LP_MUL_SPECTRUM] (tw_lo) is the kernel spectrum on P points): no padded domain;
+        // the block geometry in an argument block of its own (kern_lines.hpp RconvOls)
         RconvOlsArgs oa{};
         a.conj = (int)s.i[LS_CONJ];
         oa.a = a;
-        oa.o.fN = (int)s.i[LS_OLS_FN]; oa.o.plim = (int)s.i[LS_OLS_PLIM]; oa.o.nb = (int)s.i[LS_OLS_NB]; oa.o.L = (int)s.i[LS_OLS_L]; oa.o.w0 = (int)s.i[LS_OLS_W0]; oa.o.pre = (int)s.i[LS_OLS_PRE];
-        return launch_lines_rconv_ols(s.variant, oa, s.grid, l);
-      }
-      if (a.real_mode == LM_CONV_OLS) {   // overlap-save on complex lines: p[LP_MUL_SPECTRUM] (tw_lo) is the kernel spectrum on P points; the same argument block
-        RconvOlsArgs oa{};
-        a.conj = (int)s.i[LS_CONJ];
-        oa.a = a;
-        oa.o.fN = (int)s.i[LS_OLS_FN]; oa.o.plim = (int)s.i[LS_OLS_PLIM]; oa.o.nb = (int)s.i[LS_OLS_NB]; oa.o.L = (int)s.i[LS_OLS_L]; oa.o.w0 = (int)s.i[LS_OLS_W0]; oa.o.pre = (int)s.i[LS_OLS_PRE];
-        return launch_lines_conv_ols(s.variant, oa, s.grid, l);
+        const OlsAxis g = ols_axis_of(s.i, 0);
+        oa.o.fN = (int)g.fN; oa.o.plim = (int)g.plim; oa.o.nb = (int)g.nb; oa.o.L = (int)g.L; oa.o.w0 = (int)g.w0; oa.o.pre = (int)g.pre;
+        return a.real_mode == LM_RCONV_OLS ? launch_lines_rconv_ols(s.variant, oa, s.grid, l) : launch_lines_conv_ols(s.variant, oa, s.grid, l);
       }
       if (a.real_mode == LM_TILES_CONV_OLS || a.real_mode == LM_TILES_SPECTRUM) return launch_tiles_conv_ols(s.variant, tiles_args_of(s, ptr), s.grid, l);   // rank-2 overlap-save tiles
       if (a.real_mode == LM_TILES_RCONV_OLS || a.real_mode == LM_TILES_RSPECTRUM) return launch_tiles_rconv_ols(s.variant, tiles_args_of(s, ptr), s.grid, l);   // and on real tile pairs

@@ -1784,6 +1784,119 @@ int64_t conv_tiles_block(int64_t fN0, int64_t fN1, int64_t M0, int64_t M1) {
   return M <= CONV_TILES_P64_MAX_KERNEL ? 64 : 128;
 }
 
+// The tile edge the default rule (PlannerOptions::rconv_ols2d == 1) gives to overlap-save on a real rank-2 image: conv_tiles_block's bounds (they also keep the
+// small real rank-2 requests on rconv[K], whose routes the tests pin) and, as measured, its tile edges.
+// Measured (profiles/fftconv_rtiles_ab.log: conv_tiles_block's six requests as real data, K = 1 and 4, both tiles; spread between repeated samples <= 3.9 %):
+// both tiles are 2.5-38x ahead of rconv[K] on the exact-length domain on every request (the nearest: 3.8-5.3x at P = 64 on 8 x 1016^2 (*) 9x9 linear-full,
+// whose domain 1024^2 keeps rconv[K] off the Bluestein lines), so no class is excluded.  P = 64 is 48-86 % ahead of P = 128 up to 17 points (9x9: 210-246
+// against 137-165 G real points/s; 17x17: 163-191 against 104-123; 3x3 and 5x5: 52-72 against 28-38); at 33 points P = 128 is 41-48 % ahead (160-175 against
+// 113-118): the complex route's boundary.  Kernels of 18 .. 32 points were not measured: they take the larger tile, as there
+int64_t rconv_tiles_block(int64_t fN0, int64_t fN1, int64_t M0, int64_t M1) { return conv_tiles_block(fN0, fN1, M0, M1); }
+
+// ---- overlap-save: what its four routes share ------------------------------------------------------------------------------------------
+// Linear modes only.  A line (rank 1) or an image (rank 2) is cut into blocks of P points per axis, and each block runs forward transform, product with a kernel
+// spectrum on P points and inverse transform inside one workgroup: no padded or exact-length domain, no transform of a whole line, no Bluestein or column
+// launch.  One launch writes the K kernel spectra into the workspace, then one launch per kernel follows: 1 + K launches for any length.  Strided lanes,
+// channel-policy lanes, zeroPad and the crop ride the two address maps (the real routes stand in front of build_fftconv_real's rejection of strided sides
+// for that reason).  The kernels' indices are 32-bit: every route bounds its axes and its block count by 2^31 less a margin.
+//
+// A route's switch (PlannerOptions::conv_ols, rconv_ols, conv_ols2d, rconv_ols2d; `sw` nonzero here): 0 keeps the earlier routes for every request (the
+// caller's gate); 1 is the route's measured rule, `rule`; any other value forces that block on every request it fits (L >= 2 per axis) where it is a legal
+// block of the route (`legal`: complex lines a power of two 128 .. 4096, real lines 128 .. 8192, tiles 64 or 128), and gives none where it is not
+int64_t ols_switch(int64_t sw, bool legal, int64_t rule) { return sw > 1 ? (legal ? sw : 0) : rule; }
+
+// The geometry of one axis of fN = shape + M - 1 logical points under a kernel of M points and blocks of P.  Block j holds signal indices [s0, s0 + P),
+// s0 = j L - pre, pre = M - 1, and gives L = P - pre results.  A real line is transformed as P / 2 complex points, so pre and L stay even there:
+// pre = M - 1 + e, e = (M - 1) & 1, L = (P - pre) & ~1.  The result window of a block starts at w0 = pre convolving and at e correlating (the conjugated
+// spectrum puts the wrap-around at the top of the block); signal indices stay below plim.  nb = 0: the block does not fit (P = 0 included)
+OlsAxis ols_axis(int64_t fN, int64_t shape, int64_t M, int64_t P, bool corr, bool real_line) {
+  OlsAxis a;
+  a.pre = real_line ? M - 1 + ((M - 1) & 1) : M - 1;
+  a.L = real_line ? (P - a.pre) & ~(int64_t)1 : P - a.pre;
+  a.nb = a.L >= 2 ? (fN + a.L - 1) / a.L : 0;
+  a.fN = fN; a.plim = corr ? shape : fN; a.w0 = corr ? a.pre - (M - 1) : a.pre;
+  return a;
+}
+
+// One launch per kernel: K copies of the prepared step `proto`, launch k with kernel k's spectrum (`spectra` + k * `bytes`) in p[slot] and kernel k's
+// lane of the output behind its store map.  (The overlap-save routes and lines-rconv[N=P]; the caller has written the mode's own slots)
+void push_per_kernel(Builder& b, const mi355fft_plan_desc& d, const ConvGeom& g, const Step& proto, LinesPtr slot, PtrRef spectra, int64_t bytes) {
+  for (int64_t k = 0; k < g.K; ++k) {
+    Step& st = b.push(ST_LINES);
+    st = proto;
+    st.p[slot] = spectra.plus(k * bytes);
+    st.omap = conv_store_map(d, g, g.fs, g.rank, k);
+  }
+}
+
+// That step for the line routes: `lines` lines (or blocks) of P points on the line kernel `m`, `outer` LDS elements a line, read through the data map.
+// The real modes carry the split roots `proots` (LO and HI in one table) as well
+Step conv_line_proto(const Builder& b, const mi355fft_plan_desc& d, const ConvGeom& g, const LineKernelMeta& m, LineMode mode, int64_t lines, int64_t outer, int64_t P,
+                     PtrRef tables, PtrRef proots = PtrRef()) {
+  Step st;
+  st.kind = ST_LINES;
+  st.variant = m.id;
+  st.p[LP_IN] = PtrRef(BUF_INPUT, 0); st.p[LP_OUT] = PtrRef(BUF_OUTPUT, 0); st.p[LP_TW] = tables;
+  const int64_t tiles = (lines + m.T - 1) / m.T;
+  st.i[LS_TILES] = tiles; st.i[LS_LINES] = lines; st.i[LS_IN_S] = 1; st.i[LS_IN_OUTER] = outer; st.i[LS_OUT_S] = 1; st.i[LS_OUT_OUTER] = outer;
+  if (mode != LM_CONV_OLS) { st.p[LP_TW_LO] = proots; st.i[LS_FS_SHIFT] = 10; st.i[LS_FS_LO_MASK] = 1023; }
+  st.i[LS_MODE] = mode; st.i[LS_MAPPED] = 1; st.i[LS_CONJ] = g.corr ? 1 : 0;
+  st.f[F_SCALE] = (float)(1.0 / (double)P);
+  st.imap = conv_load_map(d, g, g.fs, 1);
+  st.grid = b.lines_grid(m, tiles);
+  return st;
+}
+
+// Overlap-save in two dimensions: images, small kernels, one launch per kernel on P x P tiles (kern_tiles.hpp has the index map).  Tile (j0, j1) holds signal
+// indices [s0_a, s0_a + P) on axis a and gives L0 x L1 results (ols_axis per axis); K P^2 8 bytes of workspace for any image.  The first launch is the tile
+// kernel's forward half on the kernels, zero-padded into a tile by conv_kernel_map: the K spectra in the order the product reads them, one tile a kernel, no
+// overlap.  `real`: f32 data (the maps and the geometry count f32 elements); a work item is a PAIR of tiles that are neighbours on axis 1, one in the real and
+// one in the imaginary parts of the complex tile: B nb_0 ceil(nb_1 / 2) work items a launch.  In the spectrum launch a work item is one real kernel (nb_1 = 1
+// and L_1 = P put its partner beyond the kernel map: zero imaginary parts): K complex spectra on P x P points.  False: the request keeps its earlier route
+bool emit_tiles_ols(Builder& b, const mi355fft_plan_desc& d, const ConvGeom& g, bool real) {
+  const int64_t *ks = g.ks, *fs = g.fs, lim = ((int64_t)1 << 31) - 16384;   // (the kernel's indices are 32-bit)
+  if (fs[0] >= lim || fs[1] >= lim) return false;
+  const int64_t sw = real ? b.opt.rconv_ols2d : b.opt.conv_ols2d;
+  const int64_t P = ols_switch(sw, sw == 64 || sw == 128, real ? rconv_tiles_block(fs[0], fs[1], ks[0], ks[1]) : conv_tiles_block(fs[0], fs[1], ks[0], ks[1]));
+  const TileKernelMeta* tm = P ? find_tile_kernel((int)P, real) : nullptr;
+  const OlsAxis ax[2] = {ols_axis(fs[0], d.shape[0], ks[0], P, g.corr, false), ols_axis(fs[1], d.shape[1], ks[1], P, g.corr, false)};
+  const int64_t items = g.B * ax[0].nb * (real ? (ax[1].nb + 1) / 2 : ax[1].nb);
+  if (!tm || ax[0].L < 2 || ax[1].L < 2 || ax[0].nb * ax[1].nb >= lim || items >= lim) return false;
+  const int64_t pd[2] = {P, P};
+  const PtrRef G = b.alloc_work((uint64_t)g.K * P * P * 8);
+  std::vector<float2h> roots;
+  for (int q = 1; q < tm->R1; ++q) for (int k = 0; k < tm->R0; ++k) roots.push_back(root_of_unity((int64_t)q * k, P));
+  const PtrRef tables = b.add_table(roots);
+  int64_t per_cu = std::min<int64_t>((160 * 1024) / tm->lds_bytes, 2048 / tm->threads);
+  per_cu = std::max<int64_t>(per_cu, 1);
+  const auto launch = [&](LineMode mode, PtrRef src, PtrRef dst, int64_t count) {
+    Step st;
+    st.kind = ST_LINES;
+    st.variant = tm->id;
+    st.p[LP_IN] = src; st.p[LP_OUT] = dst; st.p[LP_TW] = tables;
+    st.i[LS_TILES] = count; st.i[LS_LINES] = count; st.i[LS_IN_S] = 1; st.i[LS_IN_OUTER] = P; st.i[LS_OUT_S] = 1; st.i[LS_OUT_OUTER] = P;
+    st.i[LS_MODE] = mode; st.i[LS_MAPPED] = 1;
+    st.grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(count, per_cu * b.opt.compute_units));
+    return st;
+  };
+  const std::string tile = "[N=" + std::to_string(P) + "x" + std::to_string(P);
+  Step sp = launch(real ? LM_TILES_RSPECTRUM : LM_TILES_SPECTRUM, PtrRef(BUF_KERNEL, 0), G, g.K);
+  OlsAxis whole;
+  whole.fN = whole.plim = whole.L = P; whole.nb = 1;
+  ols_store(sp.i, whole, whole);
+  sp.imap = conv_kernel_map(g, pd, 2); sp.omap = Builder::dense_map(pd, 2);
+  b.ir.steps.push_back(sp);
+  b.ir.route += (real ? "tiles-rspectrum" : "tiles-spectrum") + tile + "] ";
+  Step proto = launch(real ? LM_TILES_RCONV_OLS : LM_TILES_CONV_OLS, PtrRef(BUF_INPUT, 0), PtrRef(BUF_OUTPUT, 0), items);
+  proto.i[LS_CONJ] = g.corr ? 1 : 0;
+  ols_store(proto.i, ax[0], ax[1]);
+  proto.f[F_SCALE] = (float)(1.0 / (double)(P * P));
+  proto.imap = conv_load_map(d, g, fs, 2);
+  push_per_kernel(b, d, g, proto, LP_MUL_SPECTRUM, G, P * P * 8);
+  b.ir.route += (real ? "tiles-rconv-ols" : "tiles-conv-ols") + tile + ",L=" + std::to_string(ax[0].L) + "x" + std::to_string(ax[1].L) + "] ";
+  return true;
+}
+
 // y_k = IFFT( FFT(x) .* (conj?)FFT(h_k) ) / Nfft, cropped per boundary, written per output layout / lanes
 // (runtime/plans/fftconv.js:308-709, exec :1415-1712; reference semantics: src/utils/math.js:469-603)
 int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
@@ -1793,95 +1906,27 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
   const int64_t K = g.K, B = g.B, inN = g.inN;
   const int64_t *ks = g.ks, *fs = g.fs, zero[8] = {0};
   const bool zpad = d.zero_read.enabled || d.zero_write.enabled;
-  // ---- overlap-save: long complex lines, short kernels, one launch per kernel on blocks of P points -----------------------------
-  // Block j of a line holds signal indices [s0, s0 + P), s0 = j L - pre, pre = M - 1, and gives L = P - pre results (kern_lines.hpp
-  // fft_lines_conv_ols_kernel has the index map).  No padded domain, no transform of a whole line: 1 + K launches and K P 8 bytes of workspace
-  // for any length.  Strided lanes, channel-policy lanes, zeroPad and the crop ride the two address maps.  The switch 0 keeps the routes below
-  // for every request; a power of two 128 .. 4096 forces that block length on every request it fits (L >= 2); 1 is the rule of conv_ols_block
-  if (rank == 1 && g.linear && b.opt.conv_ols != 0 && b.opt.conv_lines && !b.opt.force_generic && g.lfN < ((int64_t)1 << 31) - 16384) {   // (the kernel's indices are 32-bit)
-    const int64_t M = ks[0], pre = M - 1, lfN = g.lfN;
-    int64_t P = 0;
-    if (b.opt.conv_ols > 1) { if (is_pow2(b.opt.conv_ols) && b.opt.conv_ols >= 128 && b.opt.conv_ols <= 4096) P = b.opt.conv_ols; }
-    else P = conv_ols_block(lfN, M);
-    const int64_t L = P - pre;
-    const int64_t nb = L >= 2 ? (lfN + L - 1) / L : 0, lines = B * nb;
-    const LineKernelMeta* om = (P && L >= 2 && lines < ((int64_t)1 << 31) - 64 && b.axis_mappable(P, 1, false)) ? find_line_kernel((int)P, false, false, false, false, 0) : nullptr;
+  // ---- overlap-save: long complex lines, short kernels, one launch per kernel on blocks of P points (kern_lines.hpp fft_lines_conv_ols_kernel has the
+  // index map); K P 8 bytes of workspace for any length.  The switch's rule is conv_ols_block
+  if (rank == 1 && g.linear && b.opt.conv_ols != 0 && b.opt.conv_lines && !b.opt.force_generic && g.lfN < ((int64_t)1 << 31) - 16384) {
+    const int64_t sw = b.opt.conv_ols;
+    const int64_t P = ols_switch(sw, is_pow2(sw) && sw >= 128 && sw <= 4096, conv_ols_block(g.lfN, ks[0]));
+    const OlsAxis ax = ols_axis(g.lfN, d.shape[0], ks[0], P, g.corr, false);
+    const int64_t lines = B * ax.nb;
+    const LineKernelMeta* om = (P && ax.L >= 2 && lines < ((int64_t)1 << 31) - 64 && b.axis_mappable(P, 1, false)) ? find_line_kernel((int)P, false, false, false, false, 0) : nullptr;
     if (om && om->lds_bytes > 0 && om->R1 > 1) {
       const int64_t pd[1] = {P};
       const PtrRef G = b.alloc_work((uint64_t)K * P * 8);
       if (int rv = b.emit_axis_mapped(PtrRef(BUF_KERNEL, 0), G, P, 1, K, false, 1.0f, conv_kernel_map(g, pd, 1), Builder::dense_map(pd, 1), 0)) return rv;
-      const PtrRef tables = b.line_tables(*om);
-      const SideMap xm = conv_load_map(d, g, fs, 1);
-      const int64_t tiles = (lines + om->T - 1) / om->T;
-      for (int64_t k = 0; k < K; ++k) {
-        Step& st = b.push(ST_LINES);
-        st.variant = om->id;
-        st.p[LP_IN] = PtrRef(BUF_INPUT, 0); st.p[LP_OUT] = PtrRef(BUF_OUTPUT, 0); st.p[LP_TW] = tables; st.p[LP_MUL_SPECTRUM] = G.plus(k * P * 8);
-        st.i[LS_TILES] = tiles; st.i[LS_LINES] = lines; st.i[LS_IN_S] = 1; st.i[LS_IN_OUTER] = P; st.i[LS_OUT_S] = 1; st.i[LS_OUT_OUTER] = P;
-        st.i[LS_MODE] = LM_CONV_OLS; st.i[LS_MAPPED] = 1; st.i[LS_CONJ] = g.corr ? 1 : 0;
-        st.i[LS_OLS_FN] = lfN; st.i[LS_OLS_PLIM] = g.corr ? d.shape[0] : lfN; st.i[LS_OLS_NB] = nb; st.i[LS_OLS_L] = L; st.i[LS_OLS_W0] = g.corr ? 0 : pre; st.i[LS_OLS_PRE] = pre;
-        st.f[F_SCALE] = (float)(1.0 / (double)P);
-        st.imap = xm; st.omap = conv_store_map(d, g, fs, 1, k);
-        st.grid = b.lines_grid(*om, tiles);
-      }
-      b.ir.route += "lines-conv-ols[N=" + std::to_string(P) + ",L=" + std::to_string(L) + "] ";
+      Step proto = conv_line_proto(b, d, g, *om, LM_CONV_OLS, lines, P, P, b.line_tables(*om));
+      ols_store(proto.i, ax);
+      push_per_kernel(b, d, g, proto, LP_MUL_SPECTRUM, G, P * 8);
+      b.ir.route += "lines-conv-ols[N=" + std::to_string(P) + ",L=" + std::to_string(ax.L) + "] ";
       return MI355FFT_OK;
     }
   }
-  // ---- overlap-save in two dimensions: images, small kernels, one launch per kernel on P x P tiles ---------------------------------
-  // Tile (j0, j1) of an image holds signal indices [s0_a, s0_a + P) on axis a, s0_a = j_a L_a - pre_a, pre_a = M_a - 1, and gives L0 x L1 results,
-  // L_a = P - pre_a (kern_tiles.hpp has the index map).  No exact-length domain, no Bluestein or column launch: 1 + K launches and K P^2 8 bytes of
-  // workspace for any image.  The first launch is the tile kernel's forward half on the kernels, zero-padded into a tile by conv_kernel_map: the K
-  // spectra in the order the product reads them.  Strided lanes, channel-policy lanes, zeroPad and the crop ride the two address maps.  The switch 0
-  // keeps the routes below for every request; 64 or 128 forces that tile on every request it fits (L_a >= 2); 1 is the rule of conv_tiles_block
-  if (rank == 2 && g.linear && b.opt.conv_ols2d != 0 && b.opt.conv_lines && !b.opt.force_generic && b.opt.fuse_views &&
-      fs[0] < ((int64_t)1 << 31) - 16384 && fs[1] < ((int64_t)1 << 31) - 16384) {   // (the kernel's indices are 32-bit)
-    int64_t P = 0;
-    if (b.opt.conv_ols2d > 1) { if (b.opt.conv_ols2d == 64 || b.opt.conv_ols2d == 128) P = b.opt.conv_ols2d; }
-    else P = conv_tiles_block(fs[0], fs[1], ks[0], ks[1]);
-    const TileKernelMeta* tm = P ? find_tile_kernel((int)P) : nullptr;
-    const int64_t pre[2] = {ks[0] - 1, ks[1] - 1}, L[2] = {P - pre[0], P - pre[1]};
-    const int64_t nb[2] = {L[0] >= 2 ? (fs[0] + L[0] - 1) / L[0] : 0, L[1] >= 2 ? (fs[1] + L[1] - 1) / L[1] : 0};
-    const bool fits = tm && L[0] >= 2 && L[1] >= 2 && nb[0] * nb[1] < ((int64_t)1 << 31) - 16384 && B * nb[0] * nb[1] < ((int64_t)1 << 31) - 16384;
-    if (fits) {
-      const int64_t pd[2] = {P, P}, tiles = B * nb[0] * nb[1];
-      const PtrRef G = b.alloc_work((uint64_t)K * P * P * 8);
-      std::vector<float2h> roots;
-      for (int q = 1; q < tm->R1; ++q) for (int k = 0; k < tm->R0; ++k) roots.push_back(root_of_unity((int64_t)q * k, P));
-      const PtrRef tables = b.add_table(roots);
-      const auto both = [](int64_t a0, int64_t a1) { return (int64_t)((uint64_t)(uint32_t)a0 | ((uint64_t)(uint32_t)a1 << 32)); };
-      int64_t per_cu = std::min<int64_t>((160 * 1024) / tm->lds_bytes, 2048 / tm->threads);
-      per_cu = std::max<int64_t>(per_cu, 1);
-      const auto push = [&](LineMode mode, PtrRef src, PtrRef dst, int64_t count) -> Step& {
-        Step& st = b.push(ST_LINES);
-        st.variant = tm->id;
-        st.p[LP_IN] = src; st.p[LP_OUT] = dst; st.p[LP_TW] = tables;
-        st.i[LS_TILES] = count; st.i[LS_LINES] = count; st.i[LS_IN_S] = 1; st.i[LS_IN_OUTER] = P; st.i[LS_OUT_S] = 1; st.i[LS_OUT_OUTER] = P;
-        st.i[LS_MODE] = mode; st.i[LS_MAPPED] = 1;
-        st.grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(count, per_cu * b.opt.compute_units));
-        return st;
-      };
-      {   // the K kernel spectra: one tile a kernel, no overlap
-        Step& st = push(LM_TILES_SPECTRUM, PtrRef(BUF_KERNEL, 0), G, K);
-        st.i[LS_OLS_FN] = both(P, P); st.i[LS_OLS_PLIM] = both(P, P); st.i[LS_OLS_NB] = both(1, 1); st.i[LS_OLS_L] = both(P, P);
-        st.imap = conv_kernel_map(g, pd, 2); st.omap = Builder::dense_map(pd, 2);
-        b.ir.route += "tiles-spectrum[N=" + std::to_string(P) + "x" + std::to_string(P) + "] ";
-      }
-      const SideMap xm = conv_load_map(d, g, fs, 2);
-      for (int64_t k = 0; k < K; ++k) {
-        Step& st = push(LM_TILES_CONV_OLS, PtrRef(BUF_INPUT, 0), PtrRef(BUF_OUTPUT, 0), tiles);
-        st.p[LP_MUL_SPECTRUM] = G.plus(k * P * P * 8);
-        st.i[LS_CONJ] = g.corr ? 1 : 0;
-        st.i[LS_OLS_FN] = both(fs[0], fs[1]); st.i[LS_OLS_PLIM] = g.corr ? both(d.shape[0], d.shape[1]) : both(fs[0], fs[1]);
-        st.i[LS_OLS_NB] = both(nb[0], nb[1]); st.i[LS_OLS_L] = both(L[0], L[1]);
-        st.i[LS_OLS_W0] = g.corr ? 0 : both(pre[0], pre[1]); st.i[LS_OLS_PRE] = both(pre[0], pre[1]);
-        st.f[F_SCALE] = (float)(1.0 / (double)(P * P));
-        st.imap = xm; st.omap = conv_store_map(d, g, fs, 2, k);
-      }
-      b.ir.route += "tiles-conv-ols[N=" + std::to_string(P) + "x" + std::to_string(P) + ",L=" + std::to_string(L[0]) + "x" + std::to_string(L[1]) + "] ";
-      return MI355FFT_OK;
-    }
-  }
+  // ---- overlap-save in two dimensions (emit_tiles_ols); the switch's rule is conv_tiles_block
+  if (rank == 2 && g.linear && b.opt.conv_ols2d != 0 && b.opt.conv_lines && !b.opt.force_generic && b.opt.fuse_views && emit_tiles_ols(b, d, g, false)) return MI355FFT_OK;
   // Long rank-1 linear modes: the next power of two keeps the transforms off the Bluestein / mixed-radix routes (ConvGeom)
   if (b.opt.conv_pad && rank == 1 && g.linear && g.lfN > 16384 && g.lfN <= ((int64_t)1 << 22) && !is_pow2(g.lfN)) {
     int64_t P = 32768;
@@ -2052,10 +2097,9 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
 // Signals, kernels and results are f32 reals; the values are the real parts of what build_fftconv's plan returns for the same data
 // with zero imaginary parts.  Every option keeps its meaning; side layouts and the kernel stride count f32 elements.  Five routes:
 //   tiles-rconv-ols[N=PxP,L=L0xL1]  rank 2, linear modes, images with small kernels by default (rconv_tiles_block; MI355FFT_RCONV_OLS2D): overlap-save on
-//                     P x P tiles, two real tiles that are neighbours on axis 1 as re / im of one complex tile (kern_tiles.hpp); 1 + K launches for any
-//                     image, strided lanes too
-//   lines-rconv-ols[N=P,L=L]  rank 1, linear modes, shape + kernelShape - 1 > 8192 and kernelShape <= 4096 by default (MI355FFT_RCONV_OLS): overlap-save,
-//                     the line cut into blocks of P points that each run the pipeline of lines-rconv; 1 + K launches for any length, strided lanes too
+//                     pairs of P x P tiles (emit_tiles_ols)
+//   lines-rconv-ols[N=P,L=L]  rank 1, linear modes, shape + kernelShape - 1 > 8192 and kernelShape <= 4096 by default (MI355FFT_RCONV_OLS): overlap-save
+//                     on blocks of P points (what the overlap-save routes share is said once, above ols_switch)
 //   lines-rconv[N=P]  rank 1, FFT length P a power of two, 128 <= P <= 8192 by default (16384 and 32768 with strided sides or MI355FFT_RCONV_FUSED=2) (circular: P = shape; linear modes: the next power of two
 //                     >= max(shape + kernelShape - 1, 128) — a linear result is cropped, so any P >= that length is legal): one
 //                     lines-r2c-mapped launch writes the K packed kernel spectra, then ONE launch per kernel does r2c, product and c2r
@@ -2068,15 +2112,6 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
 //   rconv-widened     circular with odd shape[0] (no even domain is allowed): the complex plan between widening / narrowing passes
 // Validation, shapes, lanes and the padded-domain index map are ConvGeom's, shared with build_fftconv; each route hands it the
 // axis-0 length it transforms on.
-// The tile edge the default rule (PlannerOptions::rconv_ols2d == 1) gives to overlap-save on a real rank-2 image: conv_tiles_block's bounds (they also keep the
-// small real rank-2 requests on rconv[K], whose routes the tests pin) and, as measured, its tile edges.
-// Measured (profiles/fftconv_rtiles_ab.log: conv_tiles_block's six requests as real data, K = 1 and 4, both tiles; spread between repeated samples <= 3.9 %):
-// both tiles are 2.5-38x ahead of rconv[K] on the exact-length domain on every request (the nearest: 3.8-5.3x at P = 64 on 8 x 1016^2 (*) 9x9 linear-full,
-// whose domain 1024^2 keeps rconv[K] off the Bluestein lines), so no class is excluded.  P = 64 is 48-86 % ahead of P = 128 up to 17 points (9x9: 210-246
-// against 137-165 G real points/s; 17x17: 163-191 against 104-123; 3x3 and 5x5: 52-72 against 28-38); at 33 points P = 128 is 41-48 % ahead (160-175 against
-// 113-118): the complex route's boundary.  Kernels of 18 .. 32 points were not measured: they take the larger tile, as there
-int64_t rconv_tiles_block(int64_t fN0, int64_t fN1, int64_t M0, int64_t M1) { return conv_tiles_block(fN0, fN1, M0, M1); }
-
 constexpr int64_t OLS_MAX_KERNEL = 4096;   // the longest kernel the default rule gives to overlap-save: the longest one measured (3.8x / 2.5x ahead at K = 1 / 4)
 int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
   ConvGeom g;
@@ -2088,22 +2123,20 @@ int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err
   const bool strided = d.input.strided || d.output.strided;
   const PtrRef in(BUF_INPUT, 0), out(BUF_OUTPUT, 0), kern(BUF_KERNEL, 0);
 
-  // ---- overlap-save: long real lines, short kernels, one launch per kernel on blocks of P points ---------------------------------
-  // Block j of a line holds signal indices [s0, s0 + P), s0 = j L - pre, pre = M - 1 + e, e = (M - 1) & 1, and gives L = (P - pre) & ~1
-  // results (kern_lines.hpp fft_lines_rconv_ols_kernel has the index map).  The switch 0 keeps the routes below for every request; a
-  // power of two 128 .. 8192 forces that block length on every request it fits (L >= 2), whatever its length; 1 is the measured rule
-  if (rank == 1 && linear && b.opt.rconv_fused == 1 && b.opt.rconv_ols != 0 && lfN < ((int64_t)1 << 31) - 16384) {   // (the kernel's indices are 32-bit)
-    const int64_t M = ks[0], pre = (M - 1) + ((M - 1) & 1);
-    int64_t P = 0;
-    if (b.opt.rconv_ols > 1) { if (is_pow2(b.opt.rconv_ols) && b.opt.rconv_ols >= 128 && b.opt.rconv_ols <= 8192) P = b.opt.rconv_ols; }
+  // ---- overlap-save: long real lines, short kernels, one launch per kernel on blocks of P points, each running the pipeline of lines-rconv
+  // (kern_lines.hpp fft_lines_rconv_ols_kernel has the index map).  The switch's rule, whatever the line's length when a block is forced:
+  if (rank == 1 && linear && b.opt.rconv_fused == 1 && b.opt.rconv_ols != 0 && lfN < ((int64_t)1 << 31) - 16384) {
+    const int64_t M = ks[0], sw = b.opt.rconv_ols;
     // measured (profiles/fftconv_ols_ab.log, 256 x 2^20 (*) {31, 255, 1024, 4096}, K = 1 and 4, and three longer / shorter lines): every block length
     // 1024 .. 8192 is 2.5-8x ahead of pad[..] rconv[K] and 46-66x ahead of the Bluestein plans above 2^22; the fastest P is the smallest power of two
     // >= 8 (M - 1) from 1024 on (M = 31: 1024, 255: 2048, 1024 and 4096: 8192), except that P = 4096 is behind 8192 on every request (its instance
     // holds 190 VGPRs: two workgroups per CU where the LDS would take three) and is never chosen
-    else if (lfN > 8192 && M <= OLS_MAX_KERNEL) { P = 1024; while (P < 8 * (M - 1) && P < 8192) P <<= 1; if (P == 4096) P = 8192; }
-    const int64_t L = (P - pre) & ~(int64_t)1;
-    const int64_t nb = L >= 2 ? (lfN + L - 1) / L : 0, lines = B * nb;
-    const LineKernelMeta* om = (P && L >= 2 && lines < ((int64_t)1 << 31) - 64) ? b.lines_r2c_kernel(P, false, true) : nullptr;
+    int64_t rule = 0;
+    if (lfN > 8192 && M <= OLS_MAX_KERNEL) { rule = 1024; while (rule < 8 * (M - 1) && rule < 8192) rule <<= 1; if (rule == 4096) rule = 8192; }
+    const int64_t P = ols_switch(sw, is_pow2(sw) && sw >= 128 && sw <= 8192, rule);
+    const OlsAxis ax = ols_axis(lfN, d.shape[0], M, P, corr, true);
+    const int64_t lines = B * ax.nb;
+    const LineKernelMeta* om = (P && ax.L >= 2 && lines < ((int64_t)1 << 31) - 64) ? b.lines_r2c_kernel(P, false, true) : nullptr;
     if (om) {
       const int64_t H = P / 2;
       const int64_t pd[1] = {P}, pp[1] = {H + 1};
@@ -2112,79 +2145,15 @@ int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err
       const SideMap gm = Builder::dense_map(pp, 1);
       if (!b.emit_lines_r2c(kern, G, P, K, 1.0f, false, 0, &km, &gm)) { err = "no mapped r2c line kernel"; return MI355FFT_ERR_UNSUPPORTED; }
       const PtrRef tables = b.line_tables(*om), proots = b.rconv_roots(P);
-      const SideMap xm = conv_load_map(d, g, fs, 1);
-      const int64_t tiles = (lines + om->T - 1) / om->T;
-      for (int64_t k = 0; k < K; ++k) {
-        Step& st = b.push(ST_LINES);
-        st.variant = om->id;
-        st.p[LP_IN] = in; st.p[LP_OUT] = out; st.p[LP_TW] = tables; st.p[LP_TW_LO] = proots; st.p[LP_RCONV_SPECTRUM] = G.plus(k * (H + 1) * 8);
-        st.i[LS_TILES] = tiles; st.i[LS_LINES] = lines; st.i[LS_IN_S] = 1; st.i[LS_IN_OUTER] = H; st.i[LS_OUT_S] = 1; st.i[LS_OUT_OUTER] = H; st.i[LS_FS_SHIFT] = 10; st.i[LS_FS_LO_MASK] = 1023;
-        st.i[LS_MODE] = LM_RCONV_OLS; st.i[LS_MAPPED] = 1; st.i[LS_CONJ] = corr ? 1 : 0;
-        st.i[LS_OLS_FN] = lfN; st.i[LS_OLS_PLIM] = corr ? d.shape[0] : lfN; st.i[LS_OLS_NB] = nb; st.i[LS_OLS_L] = L; st.i[LS_OLS_W0] = corr ? pre - (M - 1) : pre; st.i[LS_OLS_PRE] = pre;
-        st.f[F_SCALE] = (float)(1.0 / (double)P);
-        st.imap = xm; st.omap = conv_store_map(d, g, fs, 1, k);
-        st.grid = b.lines_grid(*om, tiles);
-      }
-      b.ir.route += "lines-rconv-ols[N=" + std::to_string(P) + ",L=" + std::to_string(L) + "] ";
+      Step proto = conv_line_proto(b, d, g, *om, LM_RCONV_OLS, lines, H, P, tables, proots);
+      ols_store(proto.i, ax);
+      push_per_kernel(b, d, g, proto, LP_RCONV_SPECTRUM, G, (H + 1) * 8);
+      b.ir.route += "lines-rconv-ols[N=" + std::to_string(P) + ",L=" + std::to_string(ax.L) + "] ";
       return MI355FFT_OK;
     }
   }
-
-  // ---- overlap-save in two dimensions: real images, small kernels, one launch per kernel on pairs of P x P tiles ---------------------
-  // build_fftconv's tile block on real data: the geometry, the two maps and the geometry slots are the same (they count f32 elements here), and a work item is
-  // a PAIR of tiles that are neighbours on axis 1, one in the real and one in the imaginary parts of the complex tile (kern_tiles.hpp has the index map):
-  // B nb_0 ceil(nb_1 / 2) work items a launch.  The first launch is the kernel's forward half on the real kernels, one a work item: K complex spectra on
-  // P x P points.  In front of the rejection of strided sides: lanes, outputLayout, the kernel stride and zeroPad ride the two address maps.  The switch 0
-  // keeps the routes below for every request; 64 or 128 forces that tile on every request it fits (L_a >= 2); 1 is the rule of rconv_tiles_block
-  if (rank == 2 && linear && b.opt.rconv_ols2d != 0 && b.opt.rconv_fused != 0 && !b.opt.force_generic &&
-      fs[0] < ((int64_t)1 << 31) - 16384 && fs[1] < ((int64_t)1 << 31) - 16384) {   // (the kernel's indices are 32-bit)
-    int64_t P = 0;
-    if (b.opt.rconv_ols2d > 1) { if (b.opt.rconv_ols2d == 64 || b.opt.rconv_ols2d == 128) P = b.opt.rconv_ols2d; }
-    else P = rconv_tiles_block(fs[0], fs[1], ks[0], ks[1]);
-    const TileKernelMeta* tm = P ? find_tile_kernel((int)P, true) : nullptr;
-    const int64_t pre[2] = {ks[0] - 1, ks[1] - 1}, L[2] = {P - pre[0], P - pre[1]};
-    const int64_t nb[2] = {L[0] >= 2 ? (fs[0] + L[0] - 1) / L[0] : 0, L[1] >= 2 ? (fs[1] + L[1] - 1) / L[1] : 0};
-    const int64_t pairs1 = (nb[1] + 1) / 2;
-    const bool fits = tm && L[0] >= 2 && L[1] >= 2 && nb[0] * nb[1] < ((int64_t)1 << 31) - 16384 && B * nb[0] * pairs1 < ((int64_t)1 << 31) - 16384;
-    if (fits) {
-      const int64_t pd[2] = {P, P}, items = B * nb[0] * pairs1;
-      const PtrRef G = b.alloc_work((uint64_t)K * P * P * 8);
-      std::vector<float2h> roots;
-      for (int q = 1; q < tm->R1; ++q) for (int k = 0; k < tm->R0; ++k) roots.push_back(root_of_unity((int64_t)q * k, P));
-      const PtrRef tables = b.add_table(roots);
-      const auto both = [](int64_t a0, int64_t a1) { return (int64_t)((uint64_t)(uint32_t)a0 | ((uint64_t)(uint32_t)a1 << 32)); };
-      int64_t per_cu = std::min<int64_t>((160 * 1024) / tm->lds_bytes, 2048 / tm->threads);
-      per_cu = std::max<int64_t>(per_cu, 1);
-      const auto push = [&](LineMode mode, PtrRef src, PtrRef dst, int64_t count) -> Step& {
-        Step& st = b.push(ST_LINES);
-        st.variant = tm->id;
-        st.p[LP_IN] = src; st.p[LP_OUT] = dst; st.p[LP_TW] = tables;
-        st.i[LS_TILES] = count; st.i[LS_LINES] = count; st.i[LS_IN_S] = 1; st.i[LS_IN_OUTER] = P; st.i[LS_OUT_S] = 1; st.i[LS_OUT_OUTER] = P;
-        st.i[LS_MODE] = mode; st.i[LS_MAPPED] = 1;
-        st.grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(count, per_cu * b.opt.compute_units));
-        return st;
-      };
-      {   // the K kernel spectra: one kernel a work item (nb_1 = 1 and L_1 = P put its partner beyond the kernel map: zero imaginary parts), no overlap
-        Step& st = push(LM_TILES_RSPECTRUM, kern, G, K);
-        st.i[LS_OLS_FN] = both(P, P); st.i[LS_OLS_PLIM] = both(P, P); st.i[LS_OLS_NB] = both(1, 1); st.i[LS_OLS_L] = both(P, P);
-        st.imap = conv_kernel_map(g, pd, 2); st.omap = Builder::dense_map(pd, 2);
-        b.ir.route += "tiles-rspectrum[N=" + std::to_string(P) + "x" + std::to_string(P) + "] ";
-      }
-      const SideMap xm = conv_load_map(d, g, fs, 2);
-      for (int64_t k = 0; k < K; ++k) {
-        Step& st = push(LM_TILES_RCONV_OLS, in, out, items);
-        st.p[LP_MUL_SPECTRUM] = G.plus(k * P * P * 8);
-        st.i[LS_CONJ] = corr ? 1 : 0;
-        st.i[LS_OLS_FN] = both(fs[0], fs[1]); st.i[LS_OLS_PLIM] = corr ? both(d.shape[0], d.shape[1]) : both(fs[0], fs[1]);
-        st.i[LS_OLS_NB] = both(nb[0], nb[1]); st.i[LS_OLS_L] = both(L[0], L[1]);
-        st.i[LS_OLS_W0] = corr ? 0 : both(pre[0], pre[1]); st.i[LS_OLS_PRE] = both(pre[0], pre[1]);
-        st.f[F_SCALE] = (float)(1.0 / (double)(P * P));
-        st.imap = xm; st.omap = conv_store_map(d, g, fs, 2, k);
-      }
-      b.ir.route += "tiles-rconv-ols[N=" + std::to_string(P) + "x" + std::to_string(P) + ",L=" + std::to_string(L[0]) + "x" + std::to_string(L[1]) + "] ";
-      return MI355FFT_OK;
-    }
-  }
+  // ---- overlap-save in two dimensions on real tile pairs (emit_tiles_ols); the switch's rule is rconv_tiles_block
+  if (rank == 2 && linear && b.opt.rconv_ols2d != 0 && b.opt.rconv_fused != 0 && !b.opt.force_generic && emit_tiles_ols(b, d, g, true)) return MI355FFT_OK;
 
   // ---- route 1: one launch per kernel on the line kernels --------------------------------------------------------------------
   int64_t P1 = 0;
@@ -2206,18 +2175,9 @@ int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err
     const SideMap km = conv_kernel_map(g, fs, 1), gm = Builder::dense_map(pp, 1);
     if (!b.emit_lines_r2c(kern, G, P, K, 1.0f, false, 0, &km, &gm)) { err = "no mapped r2c line kernel"; return MI355FFT_ERR_UNSUPPORTED; }
     const PtrRef tables = b.line_tables(*rm), proots = b.rconv_roots(P);
-    const SideMap xm = conv_load_map(d, g, fs, 1);
-    const int64_t tiles = (B + rm->T - 1) / rm->T;
-    for (int64_t k = 0; k < K; ++k) {
-      Step& st = b.push(ST_LINES);
-      st.variant = rm->id;
-      st.p[LP_IN] = in; st.p[LP_OUT] = out; st.p[LP_TW] = tables; st.p[LP_TW_LO] = proots; st.p[LP_RCONV_SPECTRUM] = G.plus(k * (H + 1) * 8);
-      st.i[LS_TILES] = tiles; st.i[LS_LINES] = B; st.i[LS_IN_S] = 1; st.i[LS_IN_OUTER] = H; st.i[LS_OUT_S] = 1; st.i[LS_OUT_OUTER] = H; st.i[LS_FS_SHIFT] = 10; st.i[LS_FS_LO_MASK] = 1023;
-      st.i[LS_MODE] = LM_RCONV; st.i[LS_MAPPED] = 1; st.i[LS_CONJ] = corr ? 1 : 0; st.i[LS_RCONV_SPLIT] = g.split; st.i[LS_RCONV_PADD] = g.padD;
-      st.f[F_SCALE] = (float)(1.0 / (double)P);
-      st.imap = xm; st.omap = conv_store_map(d, g, fs, 1, k);
-      st.grid = b.lines_grid(*rm, tiles);
-    }
+    Step proto = conv_line_proto(b, d, g, *rm, LM_RCONV, B, H, P, tables, proots);
+    proto.i[LS_RCONV_SPLIT] = g.split; proto.i[LS_RCONV_PADD] = g.padD;
+    push_per_kernel(b, d, g, proto, LP_RCONV_SPECTRUM, G, (H + 1) * 8);
     b.ir.route += "lines-rconv[N=" + std::to_string(P) + "] ";
     return MI355FFT_OK;
   }

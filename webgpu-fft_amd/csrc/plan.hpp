@@ -173,13 +173,28 @@ enum LinesSlot {
   LS_MAPPED = 10,                            // sides through Step::imap / omap
   LS_H16 = 11,                               // binary16 sides (f16-storage)
   LS_CONJ = 12,                              // LM_RCONV, LM_RCONV_OLS, LM_CONV_OLS, LM_TILES_CONV_OLS, LM_TILES_RCONV_OLS: correlation
-  LS_RCONV_SPLIT = 13, LS_OLS_FN = 13,       // LM_RCONV: ConvGeom split / padD;  LM_RCONV_OLS, LM_CONV_OLS: the block geometry (kern_lines.hpp RconvOls)
-                                             // LM_TILES_*: the same six per axis (kern_tiles.hpp TileAxis), axis 0 in the low 32 bits of a slot and axis 1 in the high
-  LS_RCONV_PADD = 14, LS_OLS_PLIM = 14,
+  LS_RCONV_SPLIT = 13, LS_OLS_FN = 13,       // LM_RCONV: ConvGeom split / padD;  the overlap-save modes: the block geometry, written and read by ols_store / ols_axis_of
+  LS_RCONV_PADD = 14, LS_OLS_PLIM = 14,      // below and by nothing else
   LS_OLS_NB = 15, LS_OLS_L = 16, LS_OLS_W0 = 17, LS_OLS_PRE = 18,
   LS_LAST = LS_OLS_PRE
 };
 static_assert(LS_LAST < STEP_INTS, "ST_LINES slots");
+// The block geometry of one axis of an overlap-save launch, host side (the kernels take it as RconvOls, kern_lines.hpp, or per axis as TileAxis, kern_tiles.hpp,
+// where the index map is): fN logical points cut into nb blocks, block j holding signal indices [j L - pre, j L - pre + P) and giving L results from its
+// window [w0, w0 + L), signal indices kept below plim
+struct OlsAxis { int64_t fN = 0, plim = 0, nb = 0, L = 0, w0 = 0, pre = 0; };
+// The six LS_OLS slots of a step's i[]: each holds axis 0 in its low 32 bits and axis 1 in its high (the line modes have one axis: the value itself)
+inline void ols_store(int64_t (&i)[STEP_INTS], const OlsAxis& a0, const OlsAxis& a1 = OlsAxis()) {
+  const auto both = [](int64_t v0, int64_t v1) { return (int64_t)((uint64_t)(uint32_t)v0 | ((uint64_t)(uint32_t)v1 << 32)); };
+  i[LS_OLS_FN] = both(a0.fN, a1.fN); i[LS_OLS_PLIM] = both(a0.plim, a1.plim); i[LS_OLS_NB] = both(a0.nb, a1.nb);
+  i[LS_OLS_L] = both(a0.L, a1.L); i[LS_OLS_W0] = both(a0.w0, a1.w0); i[LS_OLS_PRE] = both(a0.pre, a1.pre);
+}
+inline OlsAxis ols_axis_of(const int64_t (&i)[STEP_INTS], int axis) {
+  const auto half = [axis](int64_t v) { return (int64_t)(int)(uint32_t)((uint64_t)v >> (32 * axis)); };
+  OlsAxis a;
+  a.fN = half(i[LS_OLS_FN]); a.plim = half(i[LS_OLS_PLIM]); a.nb = half(i[LS_OLS_NB]); a.L = half(i[LS_OLS_L]); a.w0 = half(i[LS_OLS_W0]); a.pre = half(i[LS_OLS_PRE]);
+  return a;
+}
 enum LinesPtr {
   LP_IN = 0, LP_OUT = 1, LP_TW = 2,
   LP_TW_LO = 3, LP_MUL_SPECTRUM = 3,         // four-step / split LO roots (LM_RCONV*: LO and HI in one table); LM_MUL, LM_CONV_OLS, LM_TILES_CONV_OLS, LM_TILES_RCONV_OLS: the spectrum multiplied in
