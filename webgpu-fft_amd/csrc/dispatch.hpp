@@ -22,6 +22,7 @@
 #include "kern_regtile.hpp"
 #include "kern_xcd_res.hpp"
 #include "kern_tiles.hpp"
+#include "kern_bricks.hpp"
 #include "plan.hpp"
 
 namespace mi355 {
@@ -148,6 +149,58 @@ template <class L> bool launch_tiles_rconv_ols(int id, const TilesArgs& a, unsig
   }                                                                                                   \
   ++cur;
   MI355_TILE_KERNEL_LIST(X)
+#undef X
+  (void)cur; (void)a; (void)grid; (void)l;
+  return false;
+}
+#endif
+
+// overlap-save on rank-3 bricks (kern_bricks.hpp fft_bricks_conv_ols_kernel, routes bricks-spectrum / bricks-conv-ols and, on an RBrickCfg, bricks-rspectrum /
+// bricks-rconv-ols): the instances of MI355_BRICK_KERNEL_LIST, each form in a unit of its own (bricks_conv_ols.hip, bricks_rconv_ols.hip).  `id`: position in
+// that list (plan.cpp find_brick_kernel)
+template <class L> bool launch_bricks_conv_ols(int id, const BricksArgs& a, unsigned grid, L& l);
+template <class L> bool launch_bricks_rconv_ols(int id, const BricksArgs& a, unsigned grid, L& l);
+// its argument block from an ST_LINES step of the four brick modes: axes 0 and 1 in the halves of the LS_OLS slots, axis 2 in the LS_OLS2 slots (ols_axis_of)
+inline BricksArgs bricks_args_of(const Step& s, void* const ptr[STEP_PTRS]) {
+  BricksArgs ba{};
+  ba.in = (const cf*)ptr[LP_IN]; ba.out = (cf*)ptr[LP_OUT]; ba.spectrum = (const cf*)ptr[LP_MUL_SPECTRUM];
+  ba.num_items = s.i[LS_TILES]; ba.scale = s.f[F_SCALE];
+  ba.conj = (int)s.i[LS_CONJ]; ba.spectrum_only = s.i[LS_MODE] == LM_BRICKS_SPECTRUM || s.i[LS_MODE] == LM_BRICKS_RSPECTRUM;
+  for (int x = 0; x < 3; ++x) {
+    const OlsAxis g = ols_axis_of(s.i, x);
+    ba.ax[x] = TileAxis{(int)g.fN, (int)g.plim, (int)g.nb, (int)g.L, (int)g.w0, (int)g.pre};
+  }
+  ba.imap = s.imap; ba.omap = s.omap;
+  return ba;
+}
+#if defined(MI355_BRICKS_DEFINE_INSTANCES) || defined(MI355_HOST_EMU)
+template <class L> bool launch_bricks_conv_ols(int id, const BricksArgs& a, unsigned grid, L& l) {
+  int cur = 0;
+#define X(P, TH)                                                                                      \
+  if (id == cur) {                                                                                    \
+    using C = BrickCfg<P, TH>;                                                                        \
+    l.launch(fft_bricks_conv_ols_kernel<C>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a);   \
+    return true;                                                                                      \
+  }                                                                                                   \
+  ++cur;
+  MI355_BRICK_KERNEL_LIST(X)
+#undef X
+  (void)cur; (void)a; (void)grid; (void)l;
+  return false;
+}
+#endif
+
+#if defined(MI355_RBRICKS_DEFINE_INSTANCES) || defined(MI355_HOST_EMU)
+template <class L> bool launch_bricks_rconv_ols(int id, const BricksArgs& a, unsigned grid, L& l) {
+  int cur = 0;
+#define X(P, TH)                                                                                      \
+  if (id == cur) {                                                                                    \
+    using C = RBrickCfg<P, TH>;                                                                       \
+    l.launch(fft_bricks_conv_ols_kernel<C>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a);   \
+    return true;                                                                                      \
+  }                                                                                                   \
+  ++cur;
+  MI355_BRICK_KERNEL_LIST(X)
 #undef X
   (void)cur; (void)a; (void)grid; (void)l;
   return false;
@@ -439,6 +492,8 @@ bool dispatch_step(const Step& s, void* const ptr[STEP_PTRS], L& l, LinesFn&& li
       }
       if (a.real_mode == LM_TILES_CONV_OLS || a.real_mode == LM_TILES_SPECTRUM) return launch_tiles_conv_ols(s.variant, tiles_args_of(s, ptr), s.grid, l);   // rank-2 overlap-save tiles
       if (a.real_mode == LM_TILES_RCONV_OLS || a.real_mode == LM_TILES_RSPECTRUM) return launch_tiles_rconv_ols(s.variant, tiles_args_of(s, ptr), s.grid, l);   // and on real tile pairs
+      if (a.real_mode == LM_BRICKS_CONV_OLS || a.real_mode == LM_BRICKS_SPECTRUM) return launch_bricks_conv_ols(s.variant, bricks_args_of(s, ptr), s.grid, l);   // rank-3 overlap-save bricks
+      if (a.real_mode == LM_BRICKS_RCONV_OLS || a.real_mode == LM_BRICKS_RSPECTRUM) return launch_bricks_rconv_ols(s.variant, bricks_args_of(s, ptr), s.grid, l);   // and on real brick pairs
       const LineKernelMeta& m = line_kernel_registry()[(size_t)s.variant];
       return lines_fn(family_of_line_kernel(m), s.variant, a, s.grid);
     }

@@ -102,6 +102,21 @@ const TileKernelMeta* find_tile_kernel(int P, bool real) {
   return nullptr;
 }
 
+const BrickKernelMeta* find_brick_kernel(int P, bool real) {
+  static const std::vector<BrickKernelMeta> reg = [] {
+    std::vector<BrickKernelMeta> r;
+    for (int real = 0; real < 2; ++real) {   // both forms instantiate the whole list: an id is the position in it
+      int id = 0;
+#define X(P, TH) r.push_back(BrickKernelMeta{id++, P, TH, brick_kernel_lds_bytes(P), real != 0});
+      MI355_BRICK_KERNEL_LIST(X)
+#undef X
+    }
+    return r;
+  }();
+  for (const auto& m : reg) if (m.P == P && m.real == real) return &m;
+  return nullptr;
+}
+
 namespace {
 // launch shape of an XCD-fused instance: host copies of the Cfg constants its case in dispatch.hpp launches with (kern_xcd.hpp
 // XcdFusedCfg, kern_regtile.hpp), checked against them by tests/emu (emu_check_xcd_registry)
@@ -176,6 +191,8 @@ PlannerOptions planner_options_from_env() {
   if (const char* s = std::getenv("MI355FFT_CONV_OLS")) o.conv_ols = std::atoi(s);
   if (const char* s = std::getenv("MI355FFT_CONV_OLS2D")) o.conv_ols2d = std::atoi(s);
   if (const char* s = std::getenv("MI355FFT_RCONV_OLS2D")) o.rconv_ols2d = std::atoi(s);
+  if (const char* s = std::getenv("MI355FFT_CONV_OLS3D")) o.conv_ols3d = std::atoi(s);
+  if (const char* s = std::getenv("MI355FFT_RCONV_OLS3D")) o.rconv_ols3d = std::atoi(s);
   if (const char* s = std::getenv("MI355FFT_SOLO_MAX_KB")) { const int v = std::atoi(s); if (v >= 0) o.solo_max_kb = v; }
   if (const char* s = std::getenv("MI355FFT_SOLO_CAP_MB")) { const int v = std::atoi(s); if (v >= 1) o.solo_cap_mb = v; }
   if (const char* s = std::getenv("MI355FFT_XCD_SLOTS")) { const int v = std::atoi(s); if (v >= 0 && v <= 2) o.xcd_slots = v; }
@@ -1793,16 +1810,44 @@ int64_t conv_tiles_block(int64_t fN0, int64_t fN1, int64_t M0, int64_t M1) {
 // 113-118): the complex route's boundary.  Kernels of 18 .. 32 points were not measured: they take the larger tile, as there
 int64_t rconv_tiles_block(int64_t fN0, int64_t fN1, int64_t M0, int64_t M1) { return conv_tiles_block(fN0, fN1, M0, M1); }
 
-// ---- overlap-save: what its four routes share ------------------------------------------------------------------------------------------
-// Linear modes only.  A line (rank 1) or an image (rank 2) is cut into blocks of P points per axis, and each block runs forward transform, product with a kernel
+// The brick edge the default rule (PlannerOptions::conv_ols3d == 1) gives to overlap-save on a rank-3 volume of fN0 x fN1 x fN2 = shape + M - 1 logical points
+// and a kernel of M0 x M1 x M2 points; 0: the request keeps its earlier route.  Left alone: domains of at most 32768 points and axes below 32 points (the
+// small requests whose routes the tests pin; a brick would be mostly padding) and kernels beyond 9 points on an axis (a brick returns less than 1/8 of its
+// points; not measured: 10 .. 15 points stay on the switch alone).
+// Measured (profiles/fftconv_bricks_ab.log: 256^3 (*) {3^3, 5^3, 7^3, 9^3}, 8 x 128^3 (*) 5^3, 64 x 64^3 (*) 3^3, 500x300x200 (*) 5x5x3 and, for the domain 256^3
+// of the power-of-two lines and columns, {252^3 (*) 5^3, 250^3 (*) 7^3, 248^3 (*) 9^3} linear-full, K = 1 and 4; spread between repeated samples <= 1.4 % for
+// the brick and <= 0.4 % for the old plans): the brick is ahead on every request in every class: 3^3 66-85x and 7^3 31-41x the Bluestein plans of 256^3
+// (133-140 and 63 G points/s per kernel), 3^3 7.0-11.3x, 5^3 6.1-12.9x and 9^3 3.9-5.2x the mixed-radix plans (132-134, 101-107 and 39-40), 500x300x200
+// 37-49x, and against the power-of-two domain 256^3 2.95-3.37x at 5^3, 1.93-2.22x at 7^3 and 1.19-1.39x at 9^3 (the nearest).  So kernel edges up to 9 enter
+// the rule; the even edges between the measured odd ones take their neighbours' verdict
+constexpr int64_t CONV_BRICKS_MIN_POINTS = 32768, CONV_BRICKS_MIN_AXIS = 32, CONV_BRICKS_MAX_KERNEL = 9, RCONV_BRICKS_MAX_KERNEL = 9;
+int64_t bricks_block(const int64_t* fs, const int64_t* ks, int64_t max_kernel) {
+  const int64_t M = std::max(ks[0], std::max(ks[1], ks[2]));
+  if (std::min(fs[0], std::min(fs[1], fs[2])) < CONV_BRICKS_MIN_AXIS || M > max_kernel) return 0;
+  // fN0 fN1 fN2 <= MIN_POINTS, without forming a product that could leave 64 bits (an axis may hold 2^31 points): every axis is >= 32 here, so the domain
+  // is small only if each axis is at most MIN_POINTS / 32^2, and then the product fits
+  const int64_t cap = CONV_BRICKS_MIN_POINTS / (CONV_BRICKS_MIN_AXIS * CONV_BRICKS_MIN_AXIS);
+  if (fs[0] <= cap && fs[1] <= cap && fs[2] <= cap && fs[0] * fs[1] * fs[2] <= CONV_BRICKS_MIN_POINTS) return 0;
+  return 16;
+}
+int64_t conv_bricks_block(const int64_t* fs, const int64_t* ks) { return bricks_block(fs, ks, CONV_BRICKS_MAX_KERNEL); }
+// The same for real volumes (PlannerOptions::rconv_ols3d == 1): conv_bricks_block's bounds (they also keep the small real rank-3 requests on rconv[K], whose
+// routes the tests pin) and, as measured, its largest kernel edge.
+// Measured (profiles/fftconv_rbricks_ab.log: conv_bricks_block's requests as real data; spread <= 2.8 % for the brick, <= 0.2 % for the old plans): ahead of
+// rconv[K] on every request in every class: 3^3 48-59x (64 x 64^3: 6.7-10.6x), 7^3 25-33x, 5^3 5.8-12.1x, 9^3 3.9-5.2x, 500x300x200 29-38x, and against
+// the domain 256^3 3.5-4.7x at 5^3, 2.5-3.4x at 7^3 and 1.65-2.26x at 9^3: the complex route's boundary.  66-205 G real points/s per kernel
+int64_t rconv_bricks_block(const int64_t* fs, const int64_t* ks) { return bricks_block(fs, ks, RCONV_BRICKS_MAX_KERNEL); }
+
+// ---- overlap-save: what its six routes share --------------------------------------------------------------------------------------------
+// Linear modes only.  A line (rank 1), an image (rank 2) or a volume (rank 3) is cut into blocks of P points per axis, and each block runs forward transform, product with a kernel
 // spectrum on P points and inverse transform inside one workgroup: no padded or exact-length domain, no transform of a whole line, no Bluestein or column
 // launch.  One launch writes the K kernel spectra into the workspace, then one launch per kernel follows: 1 + K launches for any length.  Strided lanes,
 // channel-policy lanes, zeroPad and the crop ride the two address maps (the real routes stand in front of build_fftconv_real's rejection of strided sides
 // for that reason).  The kernels' indices are 32-bit: every route bounds its axes and its block count by 2^31 less a margin.
 //
-// A route's switch (PlannerOptions::conv_ols, rconv_ols, conv_ols2d, rconv_ols2d; `sw` nonzero here): 0 keeps the earlier routes for every request (the
+// A route's switch (PlannerOptions::conv_ols, rconv_ols, conv_ols2d, rconv_ols2d, conv_ols3d, rconv_ols3d; `sw` nonzero here): 0 keeps the earlier routes for every request (the
 // caller's gate); 1 is the route's measured rule, `rule`; any other value forces that block on every request it fits (L >= 2 per axis) where it is a legal
-// block of the route (`legal`: complex lines a power of two 128 .. 4096, real lines 128 .. 8192, tiles 64 or 128), and gives none where it is not
+// block of the route (`legal`: complex lines a power of two 128 .. 4096, real lines 128 .. 8192, tiles 64 or 128, bricks 16), and gives none where it is not
 int64_t ols_switch(int64_t sw, bool legal, int64_t rule) { return sw > 1 ? (legal ? sw : 0) : rule; }
 
 // The geometry of one axis of fN = shape + M - 1 logical points under a kernel of M points and blocks of P.  Block j holds signal indices [s0, s0 + P),
@@ -1897,6 +1942,56 @@ bool emit_tiles_ols(Builder& b, const mi355fft_plan_desc& d, const ConvGeom& g, 
   return true;
 }
 
+// Overlap-save in three dimensions: volumes, small kernels, one launch per kernel on 16^3 bricks (kern_bricks.hpp has the index map): emit_tiles_ols with a
+// third axis.  Brick (j0, j1, j2) holds signal indices [s0_a, s0_a + 16) on axis a and gives L0 x L1 x L2 results; K 16^3 8 bytes of workspace for any volume.
+// The first launch is the brick kernel's forward half on the kernels, zero-padded into a brick by conv_kernel_map.  `real`: f32 data; a work item is a PAIR
+// of bricks that are neighbours on axis 2: B nb_0 nb_1 ceil(nb_2 / 2) work items a launch, and in the spectrum launch one real kernel (nb_2 = 1 and L_2 = 16
+// put its partner beyond the kernel map).  False: the request keeps its earlier route
+bool emit_bricks_ols(Builder& b, const mi355fft_plan_desc& d, const ConvGeom& g, bool real) {
+  const int64_t *ks = g.ks, *fs = g.fs, lim = ((int64_t)1 << 31) - 16384;   // (the kernel's indices are 32-bit)
+  if (fs[0] >= lim || fs[1] >= lim || fs[2] >= lim) return false;
+  const int64_t sw = real ? b.opt.rconv_ols3d : b.opt.conv_ols3d;
+  const int64_t P = ols_switch(sw, sw == 16, real ? rconv_bricks_block(fs, ks) : conv_bricks_block(fs, ks));
+  const BrickKernelMeta* bm = P ? find_brick_kernel((int)P, real) : nullptr;
+  OlsAxis ax[3];
+  for (int a = 0; a < 3; ++a) ax[a] = ols_axis(fs[a], d.shape[a], ks[a], P, g.corr, false);
+  if (!bm || ax[0].L < 2 || ax[1].L < 2 || ax[2].L < 2) return false;
+  const int64_t n01 = ax[0].nb * ax[1].nb;                                  // (each nb < 2^31: the products below stay inside 64 bits step by step)
+  if (n01 >= lim || n01 * ax[2].nb >= lim) return false;
+  const int64_t items = g.B * n01 * (real ? (ax[2].nb + 1) / 2 : ax[2].nb);
+  if (g.B >= lim || items >= lim) return false;
+  const int64_t pd[3] = {P, P, P}, V = P * P * P;
+  const PtrRef G = b.alloc_work((uint64_t)g.K * V * 8);
+  int64_t per_cu = std::min<int64_t>((160 * 1024) / bm->lds_bytes, 2048 / bm->threads);
+  per_cu = std::max<int64_t>(per_cu, 1);
+  const auto launch = [&](LineMode mode, PtrRef src, PtrRef dst, int64_t count) {
+    Step st;
+    st.kind = ST_LINES;
+    st.variant = bm->id;
+    st.p[LP_IN] = src; st.p[LP_OUT] = dst;
+    st.i[LS_TILES] = count; st.i[LS_LINES] = count; st.i[LS_IN_S] = 1; st.i[LS_IN_OUTER] = P; st.i[LS_OUT_S] = 1; st.i[LS_OUT_OUTER] = P;
+    st.i[LS_MODE] = mode; st.i[LS_MAPPED] = 1;
+    st.grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(count, per_cu * b.opt.compute_units));
+    return st;
+  };
+  const std::string brick = "[N=" + std::to_string(P) + "x" + std::to_string(P) + "x" + std::to_string(P);
+  Step sp = launch(real ? LM_BRICKS_RSPECTRUM : LM_BRICKS_SPECTRUM, PtrRef(BUF_KERNEL, 0), G, g.K);
+  OlsAxis whole;
+  whole.fN = whole.plim = whole.L = P; whole.nb = 1;
+  ols_store(sp.i, whole, whole, &whole);
+  sp.imap = conv_kernel_map(g, pd, 3); sp.omap = Builder::dense_map(pd, 3);
+  b.ir.steps.push_back(sp);
+  b.ir.route += (real ? "bricks-rspectrum" : "bricks-spectrum") + brick + "] ";
+  Step proto = launch(real ? LM_BRICKS_RCONV_OLS : LM_BRICKS_CONV_OLS, PtrRef(BUF_INPUT, 0), PtrRef(BUF_OUTPUT, 0), items);
+  proto.i[LS_CONJ] = g.corr ? 1 : 0;
+  ols_store(proto.i, ax[0], ax[1], &ax[2]);
+  proto.f[F_SCALE] = (float)(1.0 / (double)V);
+  proto.imap = conv_load_map(d, g, fs, 3);
+  push_per_kernel(b, d, g, proto, LP_MUL_SPECTRUM, G, V * 8);
+  b.ir.route += (real ? "bricks-rconv-ols" : "bricks-conv-ols") + brick + ",L=" + std::to_string(ax[0].L) + "x" + std::to_string(ax[1].L) + "x" + std::to_string(ax[2].L) + "] ";
+  return true;
+}
+
 // y_k = IFFT( FFT(x) .* (conj?)FFT(h_k) ) / Nfft, cropped per boundary, written per output layout / lanes
 // (runtime/plans/fftconv.js:308-709, exec :1415-1712; reference semantics: src/utils/math.js:469-603)
 int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
@@ -1927,6 +2022,8 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
   }
   // ---- overlap-save in two dimensions (emit_tiles_ols); the switch's rule is conv_tiles_block
   if (rank == 2 && g.linear && b.opt.conv_ols2d != 0 && b.opt.conv_lines && !b.opt.force_generic && b.opt.fuse_views && emit_tiles_ols(b, d, g, false)) return MI355FFT_OK;
+  // ---- overlap-save in three dimensions (emit_bricks_ols); the switch's rule is conv_bricks_block
+  if (rank == 3 && g.linear && b.opt.conv_ols3d != 0 && b.opt.conv_lines && !b.opt.force_generic && b.opt.fuse_views && emit_bricks_ols(b, d, g, false)) return MI355FFT_OK;
   // Long rank-1 linear modes: the next power of two keeps the transforms off the Bluestein / mixed-radix routes (ConvGeom)
   if (b.opt.conv_pad && rank == 1 && g.linear && g.lfN > 16384 && g.lfN <= ((int64_t)1 << 22) && !is_pow2(g.lfN)) {
     int64_t P = 32768;
@@ -2095,7 +2192,9 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
 
 // ---- fftconv over real data (type MI355FFT_FFTCONV_REAL) ------------------------------------------------------------------------
 // Signals, kernels and results are f32 reals; the values are the real parts of what build_fftconv's plan returns for the same data
-// with zero imaginary parts.  Every option keeps its meaning; side layouts and the kernel stride count f32 elements.  Five routes:
+// with zero imaginary parts.  Every option keeps its meaning; side layouts and the kernel stride count f32 elements.  Six routes:
+//   bricks-rconv-ols[N=16x16x16,L=L0xL1xL2]  rank 3, linear modes, volumes with small kernels by default (rconv_bricks_block; MI355FFT_RCONV_OLS3D): overlap-save
+//                     on pairs of 16^3 bricks (emit_bricks_ols)
 //   tiles-rconv-ols[N=PxP,L=L0xL1]  rank 2, linear modes, images with small kernels by default (rconv_tiles_block; MI355FFT_RCONV_OLS2D): overlap-save on
 //                     pairs of P x P tiles (emit_tiles_ols)
 //   lines-rconv-ols[N=P,L=L]  rank 1, linear modes, shape + kernelShape - 1 > 8192 and kernelShape <= 4096 by default (MI355FFT_RCONV_OLS): overlap-save
@@ -2154,6 +2253,8 @@ int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err
   }
   // ---- overlap-save in two dimensions on real tile pairs (emit_tiles_ols); the switch's rule is rconv_tiles_block
   if (rank == 2 && linear && b.opt.rconv_ols2d != 0 && b.opt.rconv_fused != 0 && !b.opt.force_generic && emit_tiles_ols(b, d, g, true)) return MI355FFT_OK;
+  // ---- overlap-save in three dimensions on real brick pairs (emit_bricks_ols); the switch's rule is rconv_bricks_block
+  if (rank == 3 && linear && b.opt.rconv_ols3d != 0 && b.opt.rconv_fused != 0 && !b.opt.force_generic && emit_bricks_ols(b, d, g, true)) return MI355FFT_OK;
 
   // ---- route 1: one launch per kernel on the line kernels --------------------------------------------------------------------
   int64_t P1 = 0;

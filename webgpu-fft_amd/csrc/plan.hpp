@@ -46,6 +46,12 @@ struct TileKernelMeta { int id, P, R0, R1, threads, lds_bytes; bool real; };
 // `real`: the same list as instances of fft_tiles_conv_ols_kernel on an RTileCfg (real fftconv: two real tiles as re / im of a complex one), a unit of their own
 // (tiles_rconv_ols.hip); an id counts positions in the list for both forms, and the step's line mode says which form is launched
 const TileKernelMeta* find_tile_kernel(int P, bool real = false);
+// overlap-save brick kernels of rank-3 fftconv (kern_bricks.hpp fft_bricks_conv_ols_kernel): X(P, threads), id = position in the list.  LDS: the P^3 brick
+// at pitches of P + 1 and P (P + 1) elements.  `real`: the same list on an RBrickCfg (bricks_rconv_ols.hip), as with the tiles
+#define MI355_BRICK_KERNEL_LIST(X) X(16, 256)
+constexpr int brick_kernel_lds_bytes(int P) { return P * P * (P + 1) * 8; }
+struct BrickKernelMeta { int id, P, threads, lds_bytes; bool real; };
+const BrickKernelMeta* find_brick_kernel(int P, bool real = false);
 // mixed-radix line kernels with compile-time plans (kern_mixed_ct.hpp): id = position in the list
 // instances: X(N, lines per workgroup, threads, radices...).  Tile shapes keep every stage's butterfly count (T * N / R) at or
 // above the thread count and two workgroups per CU inside the LDS.
@@ -158,7 +164,11 @@ enum LineMode : int {
   LM_TILES_CONV_OLS = 12,   // overlap-save on rank-2 complex tiles (kern_tiles.hpp fft_tiles_conv_ols_kernel): `variant` is a TileKernelMeta id, not a line kernel's
   LM_TILES_SPECTRUM = 13,   // its forward half on the zero-padded kernels: the K spectra in the order the product reads them
   LM_TILES_RCONV_OLS = 14,  // overlap-save on rank-2 real tiles, two of them as re / im of a complex tile (kern_tiles.hpp fft_tiles_conv_ols_kernel on an RTileCfg); `variant` as above
-  LM_TILES_RSPECTRUM = 15   // its forward half on the zero-padded real kernels, one a work item: the K complex spectra as LM_TILES_SPECTRUM stores them
+  LM_TILES_RSPECTRUM = 15,  // its forward half on the zero-padded real kernels, one a work item: the K complex spectra as LM_TILES_SPECTRUM stores them
+  LM_BRICKS_CONV_OLS = 16,  // overlap-save on rank-3 complex bricks (kern_bricks.hpp fft_bricks_conv_ols_kernel): `variant` is a BrickKernelMeta id
+  LM_BRICKS_SPECTRUM = 17,  // its forward half on the zero-padded kernels: the K spectra in the order the product reads them
+  LM_BRICKS_RCONV_OLS = 18, // overlap-save on rank-3 real bricks, two of them as re / im of a complex brick (the kernel on an RBrickCfg)
+  LM_BRICKS_RSPECTRUM = 19  // its forward half on the zero-padded real kernels, one a work item
 };
 // Bluestein's two mapped launches: bits of i[LS_CHIRP_FLAGS] (LineArgs::fs_lo_mask)
 enum : unsigned { LINES_CHIRP = 1, LINES_CHIRP_SWAP = 2 };   // multiply by the chirp in p[LP_CHIRP]; inverse transform: the chirp's conjugate
@@ -166,9 +176,9 @@ enum : unsigned { LINES_CHIRP = 1, LINES_CHIRP_SWAP = 2 };   // multiply by the 
 // ST_LINES
 enum LinesSlot {
   LS_TILES = 0, LS_LINES, LS_IN_S, LS_IN_OUTER, LS_OUT_S, LS_OUT_OUTER,
-  LS_FS_SHIFT = 6, LS_MUL_CONJ = 6,          // four-step roots: HI[m >> shift]; LM_MUL: multiply by the spectrum's conjugate
-  LS_FS_LO_MASK = 7, LS_CHIRP_FLAGS = 7,     // ... LO[m & mask]; mapped LM_C2C / LM_MUL of Bluestein: LINES_CHIRP bits
-  LS_FS_GROUP = 8,                           // PASS_B: rows per transform; COL_RAGGED: tiles per group (0 reads as 1)
+  LS_FS_SHIFT = 6, LS_MUL_CONJ = 6, LS_OLS2_FN_PLIM = 6,   // four-step roots: HI[m >> shift]; LM_MUL: multiply by the spectrum's conjugate; the brick modes: axis 2's fN (low 32 bits) and plim
+  LS_FS_LO_MASK = 7, LS_CHIRP_FLAGS = 7, LS_OLS2_NB_L = 7, // ... LO[m & mask]; mapped LM_C2C / LM_MUL of Bluestein: LINES_CHIRP bits; the brick modes: axis 2's nb and L
+  LS_FS_GROUP = 8, LS_OLS2_W0_PRE = 8,       // PASS_B: rows per transform; COL_RAGGED: tiles per group (0 reads as 1); the brick modes: axis 2's w0 and pre
   LS_MODE = 9,                               // LineMode
   LS_MAPPED = 10,                            // sides through Step::imap / omap
   LS_H16 = 11,                               // binary16 sides (f16-storage)
@@ -179,25 +189,37 @@ enum LinesSlot {
   LS_LAST = LS_OLS_PRE
 };
 static_assert(LS_LAST < STEP_INTS, "ST_LINES slots");
+// axis 2 of the brick modes sits on the four-step slots, which no tile or brick kernel reads (they have no root tables), outside the six LS_OLS slots
+static_assert(LS_OLS2_FN_PLIM == LS_FS_SHIFT && LS_OLS2_FN_PLIM < LS_MODE, "axis 2: fN, plim");
+static_assert(LS_OLS2_NB_L == LS_FS_LO_MASK && LS_OLS2_NB_L < LS_MODE, "axis 2: nb, L");
+static_assert(LS_OLS2_W0_PRE == LS_FS_GROUP && LS_OLS2_W0_PRE < LS_MODE && LS_MODE < LS_OLS_FN, "axis 2: w0, pre");
 // The block geometry of one axis of an overlap-save launch, host side (the kernels take it as RconvOls, kern_lines.hpp, or per axis as TileAxis, kern_tiles.hpp,
 // where the index map is): fN logical points cut into nb blocks, block j holding signal indices [j L - pre, j L - pre + P) and giving L results from its
 // window [w0, w0 + L), signal indices kept below plim
 struct OlsAxis { int64_t fN = 0, plim = 0, nb = 0, L = 0, w0 = 0, pre = 0; };
-// The six LS_OLS slots of a step's i[]: each holds axis 0 in its low 32 bits and axis 1 in its high (the line modes have one axis: the value itself)
-inline void ols_store(int64_t (&i)[STEP_INTS], const OlsAxis& a0, const OlsAxis& a1 = OlsAxis()) {
+// The six LS_OLS slots of a step's i[]: each holds axis 0 in its low 32 bits and axis 1 in its high (the line modes have one axis: the value itself).
+// The brick modes pass a third axis: its six values, two a slot, in the three LS_OLS2 slots, which are written for them alone
+inline void ols_store(int64_t (&i)[STEP_INTS], const OlsAxis& a0, const OlsAxis& a1 = OlsAxis(), const OlsAxis* a2 = nullptr) {
   const auto both = [](int64_t v0, int64_t v1) { return (int64_t)((uint64_t)(uint32_t)v0 | ((uint64_t)(uint32_t)v1 << 32)); };
   i[LS_OLS_FN] = both(a0.fN, a1.fN); i[LS_OLS_PLIM] = both(a0.plim, a1.plim); i[LS_OLS_NB] = both(a0.nb, a1.nb);
   i[LS_OLS_L] = both(a0.L, a1.L); i[LS_OLS_W0] = both(a0.w0, a1.w0); i[LS_OLS_PRE] = both(a0.pre, a1.pre);
+  if (a2) { i[LS_OLS2_FN_PLIM] = both(a2->fN, a2->plim); i[LS_OLS2_NB_L] = both(a2->nb, a2->L); i[LS_OLS2_W0_PRE] = both(a2->w0, a2->pre); }
 }
 inline OlsAxis ols_axis_of(const int64_t (&i)[STEP_INTS], int axis) {
-  const auto half = [axis](int64_t v) { return (int64_t)(int)(uint32_t)((uint64_t)v >> (32 * axis)); };
+  const auto half = [](int64_t v, int h) { return (int64_t)(int)(uint32_t)((uint64_t)v >> (32 * h)); };
   OlsAxis a;
-  a.fN = half(i[LS_OLS_FN]); a.plim = half(i[LS_OLS_PLIM]); a.nb = half(i[LS_OLS_NB]); a.L = half(i[LS_OLS_L]); a.w0 = half(i[LS_OLS_W0]); a.pre = half(i[LS_OLS_PRE]);
+  if (axis == 2) {
+    a.fN = half(i[LS_OLS2_FN_PLIM], 0); a.plim = half(i[LS_OLS2_FN_PLIM], 1); a.nb = half(i[LS_OLS2_NB_L], 0); a.L = half(i[LS_OLS2_NB_L], 1);
+    a.w0 = half(i[LS_OLS2_W0_PRE], 0); a.pre = half(i[LS_OLS2_W0_PRE], 1);
+    return a;
+  }
+  a.fN = half(i[LS_OLS_FN], axis); a.plim = half(i[LS_OLS_PLIM], axis); a.nb = half(i[LS_OLS_NB], axis); a.L = half(i[LS_OLS_L], axis);
+  a.w0 = half(i[LS_OLS_W0], axis); a.pre = half(i[LS_OLS_PRE], axis);
   return a;
 }
 enum LinesPtr {
   LP_IN = 0, LP_OUT = 1, LP_TW = 2,
-  LP_TW_LO = 3, LP_MUL_SPECTRUM = 3,         // four-step / split LO roots (LM_RCONV*: LO and HI in one table); LM_MUL, LM_CONV_OLS, LM_TILES_CONV_OLS, LM_TILES_RCONV_OLS: the spectrum multiplied in
+  LP_TW_LO = 3, LP_MUL_SPECTRUM = 3,         // four-step / split LO roots (LM_RCONV*: LO and HI in one table); LM_MUL, LM_CONV_OLS, the tile and brick modes: the spectrum multiplied in
   LP_TW_HI = 4, LP_CHIRP = 4, LP_RCONV_SPECTRUM = 4,   // HI roots; Bluestein: the chirp; LM_RCONV*: the packed kernel spectrum
   LP_LAST = LP_RCONV_SPECTRUM
 };
@@ -376,6 +398,16 @@ struct PlannerOptions {
                                        // per kernel whatever the image's size (kern_tiles.hpp fft_tiles_conv_ols_kernel on an RTileCfg); 1: where measured ahead (plan.cpp
                                        // rconv_tiles_block); 0: never; 64 or 128: that tile on every request it fits (tests and measurement).  rconv_fused = 0 and
                                        // force_generic come first
+#ifdef MI355_HOST_EMU
+  int conv_ols3d = std::getenv("MI355_EMU_CONV_OLS3D") ? std::atoi(std::getenv("MI355_EMU_CONV_OLS3D")) : 1;
+  int rconv_ols3d = std::getenv("MI355_EMU_RCONV_OLS3D") ? std::atoi(std::getenv("MI355_EMU_RCONV_OLS3D")) : 1;
+#else
+  int conv_ols3d = 1, rconv_ols3d = 1;
+#endif
+                                       // fftconv / real fftconv, rank 3, linear boundaries: overlap-save on 16^3 complex bricks (real: two real bricks as re / im of one),
+                                       // one launch per kernel whatever the volume's size (kern_bricks.hpp fft_bricks_conv_ols_kernel); 1: where measured ahead (plan.cpp
+                                       // conv_bricks_block, rconv_bricks_block); 0: never; 16: the brick on every request it fits (tests and measurement).  conv_lines = 0
+                                       // and force_generic (complex), rconv_fused = 0 and force_generic (real) come first
   int conv_lines = 1;                  // fftconv: kernel-spectrum product fused behind the forward line FFT (1-D, power-of-two FFT length <= max_line)
   int trig_fused = 1;                  // dct2 / dst2 of dense lines (half length a line-kernel size): permutation + real FFT + phase in one launch
   int trig_real = 1;                   // dct2/dst2/dct3/dst3 along a dense even axis through a real FFT of length N (kern_trig.hpp)
