@@ -53,6 +53,8 @@ enum { MI355FFT_FORWARD = 0, MI355FFT_INVERSE = 1 };
 enum { MI355FFT_NORM_NONE = 0, MI355FFT_NORM_BACKWARD = 1, MI355FFT_NORM_UNITARY = 2 };
 /* opts.fftConv.mode / boundary / outputLayout (runtime/plans/fftconv.js:329-338) */
 enum { MI355FFT_CONVOLUTION = 0, MI355FFT_CORRELATION = 1 };
+/* conv_boundary.  MI355FFT_CIRCULAR with short kernels on domains that are no power of two (and on lines above 2^22 points) is planned on the
+   overlap-save routes, whose blocks take the signal modulo shape (route tags ending in ",wrap]"; MI355FFT_OLS_CIRCULAR=0|1|2, README.md) */
 enum { MI355FFT_CIRCULAR = 0, MI355FFT_LINEAR_FULL = 1, MI355FFT_LINEAR_SAME = 2, MI355FFT_LINEAR_VALID = 3 };
 enum { MI355FFT_KERNEL_MAJOR = 0, MI355FFT_BATCH_MAJOR = 1 };
 

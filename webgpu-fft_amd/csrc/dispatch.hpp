@@ -73,6 +73,36 @@ template <class L> bool launch_lines_rconv_ols(int id, const RconvOlsArgs& a, un
 }
 #endif
 
+// its circular form (the kernel on OlsWrap<C>, route lines-rconv-ols[..,wrap]): the block lengths the route's rule names, P = 1024, 2048 and 8192 (half lengths
+// 512, 1024 and 4096), in a unit of their own (lines_rconv_ols_wrap.hip)
+template <class L> bool launch_lines_rconv_ols_wrap(int id, const RconvOlsArgs& a, unsigned grid, L& l);
+#if defined(MI355_RCONV_OLS_WRAP_DEFINE_INSTANCES) || defined(MI355_HOST_EMU)
+template <class L> bool launch_lines_rconv_ols_wrap(int id, const RconvOlsArgs& a, unsigned grid, L& l) {
+  int cur = 0;
+#define LINE_ROW(N, R0, R1, R2, T)                                                                          \
+  if (id == cur) {                                                                                          \
+    using C = OlsWrap<LineCfg<N, R0, R1, R2, T, false, false, false, false, 0>>;                            \
+    if constexpr ((N) == 512 || (N) == 1024 || (N) == 4096) {                                               \
+      l.launch(fft_lines_rconv_ols_kernel<C>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a);       \
+      return true;                                                                                          \
+    } else return false;                                                                                    \
+  }                                                                                                         \
+  cur += 2;
+#define LINE_ROW_TRIG(N, R0, R1, R2, T) cur += 1;
+#define LINE_PASS_A(N, R0, R1, R2, T) cur += 3;
+#define LINE_PASS_B(N, R0, R1, R2, T) cur += 2;
+#define LINE_COL_RAGGED(N, R0, R1, R2, T) cur += 2;
+#include "line_kernels.def"
+#undef LINE_ROW
+#undef LINE_ROW_TRIG
+#undef LINE_PASS_A
+#undef LINE_PASS_B
+#undef LINE_COL_RAGGED
+  (void)cur; (void)a; (void)grid; (void)l;
+  return false;
+}
+#endif
+
 // complex overlap-save (kern_lines.hpp fft_lines_conv_ols_kernel, route lines-conv-ols): block lengths P = 128 .. 4096, in a unit of their own
 // (lines_conv_ols.hip).  `id`: the registry id of the forward ROW configuration of P points
 template <class L> bool launch_lines_conv_ols(int id, const RconvOlsArgs& a, unsigned grid, L& l);
@@ -83,6 +113,36 @@ template <class L> bool launch_lines_conv_ols(int id, const RconvOlsArgs& a, uns
   if (id == cur) {                                                                                          \
     using C = LineCfg<N, R0, R1, R2, T, false, false, false, false, 0>;                                     \
     if constexpr (C::NSTAGES >= 2 && (N) >= 128 && (N) <= 4096) {                                           \
+      l.launch(fft_lines_conv_ols_kernel<C>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a);        \
+      return true;                                                                                          \
+    } else return false;                                                                                    \
+  }                                                                                                         \
+  cur += 2;
+#define LINE_ROW_TRIG(N, R0, R1, R2, T) cur += 1;
+#define LINE_PASS_A(N, R0, R1, R2, T) cur += 3;
+#define LINE_PASS_B(N, R0, R1, R2, T) cur += 2;
+#define LINE_COL_RAGGED(N, R0, R1, R2, T) cur += 2;
+#include "line_kernels.def"
+#undef LINE_ROW
+#undef LINE_ROW_TRIG
+#undef LINE_PASS_A
+#undef LINE_PASS_B
+#undef LINE_COL_RAGGED
+  (void)cur; (void)a; (void)grid; (void)l;
+  return false;
+}
+#endif
+
+// its circular form (the kernel on OlsWrap<C>, route lines-conv-ols[..,wrap]): the block lengths plan.cpp conv_ols_block names, 2048 and 4096, in a unit of
+// their own again (lines_conv_ols_wrap.hip)
+template <class L> bool launch_lines_conv_ols_wrap(int id, const RconvOlsArgs& a, unsigned grid, L& l);
+#if defined(MI355_CONV_OLS_WRAP_DEFINE_INSTANCES) || defined(MI355_HOST_EMU)
+template <class L> bool launch_lines_conv_ols_wrap(int id, const RconvOlsArgs& a, unsigned grid, L& l) {
+  int cur = 0;
+#define LINE_ROW(N, R0, R1, R2, T)                                                                          \
+  if (id == cur) {                                                                                          \
+    using C = OlsWrap<LineCfg<N, R0, R1, R2, T, false, false, false, false, 0>>;                            \
+    if constexpr ((N) == 2048 || (N) == 4096) {                                                             \
       l.launch(fft_lines_conv_ols_kernel<C>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a);        \
       return true;                                                                                          \
     } else return false;                                                                                    \
@@ -154,6 +214,41 @@ template <class L> bool launch_tiles_rconv_ols(int id, const TilesArgs& a, unsig
   return false;
 }
 #endif
+
+// the circular forms of both (the kernel on WTileCfg / WRTileCfg, routes tiles-conv-ols[..,wrap] / tiles-rconv-ols[..,wrap]; the spectrum launches stay on
+// the linear instances): the same list, each form in a unit of its own (tiles_conv_ols_wrap.hip, tiles_rconv_ols_wrap.hip)
+template <class L> bool launch_tiles_conv_ols_wrap(int id, const TilesArgs& a, unsigned grid, L& l);
+template <class L> bool launch_tiles_rconv_ols_wrap(int id, const TilesArgs& a, unsigned grid, L& l);
+#define MI355_TILE_WRAP_LAUNCHER(NAME, CFG)                                                           \
+  template <class L> bool NAME(int id, const TilesArgs& a, unsigned grid, L& l) {                     \
+    int cur = 0;                                                                                      \
+    MI355_TILE_KERNEL_LIST(X)                                                                         \
+    (void)cur; (void)a; (void)grid; (void)l;                                                          \
+    return false;                                                                                     \
+  }
+#if defined(MI355_TILES_WRAP_DEFINE_INSTANCES) || defined(MI355_HOST_EMU)
+#define X(P, R0, R1, TH)                                                                              \
+  if (id == cur) {                                                                                    \
+    using C = WTileCfg<P, R0, R1, TH>;                                                                \
+    l.launch(fft_tiles_conv_ols_kernel<C>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a);    \
+    return true;                                                                                      \
+  }                                                                                                   \
+  ++cur;
+MI355_TILE_WRAP_LAUNCHER(launch_tiles_conv_ols_wrap, WTileCfg)
+#undef X
+#endif
+#if defined(MI355_RTILES_WRAP_DEFINE_INSTANCES) || defined(MI355_HOST_EMU)
+#define X(P, R0, R1, TH)                                                                              \
+  if (id == cur) {                                                                                    \
+    using C = WRTileCfg<P, R0, R1, TH>;                                                               \
+    l.launch(fft_tiles_conv_ols_kernel<C>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a);    \
+    return true;                                                                                      \
+  }                                                                                                   \
+  ++cur;
+MI355_TILE_WRAP_LAUNCHER(launch_tiles_rconv_ols_wrap, WRTileCfg)
+#undef X
+#endif
+#undef MI355_TILE_WRAP_LAUNCHER
 
 // overlap-save on rank-3 bricks (kern_bricks.hpp fft_bricks_conv_ols_kernel, routes bricks-spectrum / bricks-conv-ols and, on an RBrickCfg, bricks-rspectrum /
 // bricks-rconv-ols): the instances of MI355_BRICK_KERNEL_LIST, each form in a unit of its own (bricks_conv_ols.hip, bricks_rconv_ols.hip).  `id`: position in
@@ -442,6 +537,41 @@ template <class L> bool launch_stage(int radix, const StageArgs& a, unsigned gri
 
 // LinesFn: bool(int family, int id, const LineArgs&, unsigned grid) — supplied by the caller because the
 // per-family instantiations live in different translation units in the product build.
+// the circular forms of both (the kernel on WBrickCfg / WRBrickCfg, routes bricks-conv-ols[..,wrap] / bricks-rconv-ols[..,wrap]): each in a unit of its own
+// (bricks_conv_ols_wrap.hip, bricks_rconv_ols_wrap.hip)
+template <class L> bool launch_bricks_conv_ols_wrap(int id, const BricksArgs& a, unsigned grid, L& l);
+template <class L> bool launch_bricks_rconv_ols_wrap(int id, const BricksArgs& a, unsigned grid, L& l);
+#define MI355_BRICK_WRAP_LAUNCHER(NAME)                                                               \
+  template <class L> bool NAME(int id, const BricksArgs& a, unsigned grid, L& l) {                    \
+    int cur = 0;                                                                                      \
+    MI355_BRICK_KERNEL_LIST(X)                                                                        \
+    (void)cur; (void)a; (void)grid; (void)l;                                                          \
+    return false;                                                                                     \
+  }
+#if defined(MI355_BRICKS_WRAP_DEFINE_INSTANCES) || defined(MI355_HOST_EMU)
+#define X(P, TH)                                                                                      \
+  if (id == cur) {                                                                                    \
+    using C = WBrickCfg<P, TH>;                                                                       \
+    l.launch(fft_bricks_conv_ols_kernel<C>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a);   \
+    return true;                                                                                      \
+  }                                                                                                   \
+  ++cur;
+MI355_BRICK_WRAP_LAUNCHER(launch_bricks_conv_ols_wrap)
+#undef X
+#endif
+#if defined(MI355_RBRICKS_WRAP_DEFINE_INSTANCES) || defined(MI355_HOST_EMU)
+#define X(P, TH)                                                                                      \
+  if (id == cur) {                                                                                    \
+    using C = WRBrickCfg<P, TH>;                                                                      \
+    l.launch(fft_bricks_conv_ols_kernel<C>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a);   \
+    return true;                                                                                      \
+  }                                                                                                   \
+  ++cur;
+MI355_BRICK_WRAP_LAUNCHER(launch_bricks_rconv_ols_wrap)
+#undef X
+#endif
+#undef MI355_BRICK_WRAP_LAUNCHER
+
 template <class L, class LinesFn, class XcdFn>
 bool dispatch_step(const Step& s, void* const ptr[STEP_PTRS], L& l, LinesFn&& lines_fn, XcdFn&& xcd_fn) {
   switch (s.kind) {
@@ -488,7 +618,15 @@ bool dispatch_step(const Step& s, void* const ptr[STEP_PTRS], L& l, LinesFn&& li
         oa.a = a;
         const OlsAxis g = ols_axis_of(s.i, 0);
         oa.o.fN = (int)g.fN; oa.o.plim = (int)g.plim; oa.o.nb = (int)g.nb; oa.o.L = (int)g.L; oa.o.w0 = (int)g.w0; oa.o.pre = (int)g.pre;
+        if (s.i[LS_OLS_WRAP]) return a.real_mode == LM_RCONV_OLS ? launch_lines_rconv_ols_wrap(s.variant, oa, s.grid, l) : launch_lines_conv_ols_wrap(s.variant, oa, s.grid, l);   // circular: the WRAP instances
         return a.real_mode == LM_RCONV_OLS ? launch_lines_rconv_ols(s.variant, oa, s.grid, l) : launch_lines_conv_ols(s.variant, oa, s.grid, l);
+      }
+      if (s.i[LS_OLS_WRAP]) {   // circular tiles and bricks (the spectrum launches never carry the flag)
+        if (a.real_mode == LM_TILES_CONV_OLS) return launch_tiles_conv_ols_wrap(s.variant, tiles_args_of(s, ptr), s.grid, l);
+        if (a.real_mode == LM_TILES_RCONV_OLS) return launch_tiles_rconv_ols_wrap(s.variant, tiles_args_of(s, ptr), s.grid, l);
+        if (a.real_mode == LM_BRICKS_CONV_OLS) return launch_bricks_conv_ols_wrap(s.variant, bricks_args_of(s, ptr), s.grid, l);
+        if (a.real_mode == LM_BRICKS_RCONV_OLS) return launch_bricks_rconv_ols_wrap(s.variant, bricks_args_of(s, ptr), s.grid, l);
+        return false;
       }
       if (a.real_mode == LM_TILES_CONV_OLS || a.real_mode == LM_TILES_SPECTRUM) return launch_tiles_conv_ols(s.variant, tiles_args_of(s, ptr), s.grid, l);   // rank-2 overlap-save tiles
       if (a.real_mode == LM_TILES_RCONV_OLS || a.real_mode == LM_TILES_RSPECTRUM) return launch_tiles_rconv_ols(s.variant, tiles_args_of(s, ptr), s.grid, l);   // and on real tile pairs

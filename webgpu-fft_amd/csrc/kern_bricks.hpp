@@ -69,6 +69,7 @@ template <int P_, int THREADS_>
 struct BrickCfg {
   static constexpr int P = P_, THREADS = THREADS_;
   static constexpr bool REAL = false;               // RBrickCfg: real brick pairs
+  static constexpr bool WRAP = false;               // WBrickCfg, WRBrickCfg: circular boundary, signal indices modulo fN_a
   static_assert(P == 16 && THREADS == P * P, "a thread per line, a line per radix-16 butterfly");
   static constexpr int P1 = P + 1, P2 = P * P1;     // the pitches of axes 1 and 2 (see the header)
   static constexpr int VOLUME = P * P * P;
@@ -108,7 +109,40 @@ __global__ void __launch_bounds__(C::THREADS, C::WAVES_PER_SIMD) fft_bricks_conv
     const int q0 = s00 + tl, q1 = s01 + th;         // pass 2: this lane's line
     cf v[P];
     // ---- forward, pass 2: from global memory ----
-    {
+    if constexpr (C::WRAP) {
+      // circular: signal index (s0_a + i_a) mod fN_a on the three axes, as in kern_tiles.hpp: fN_a >= 2 P, one conditional add and one conditional subtract.
+      // Axes 0 and 1 are the lane's line, wrapped once per item; on axis 2 the head's wrap moves the brick's origin, the same for every lane, and past the
+      // seam the index falls back by fN_2.  The map's bounds apply to the wrapped indices, the only ones that are dereferenced.  REAL: an absent partner b
+      // (odd nb_2) loads nothing, under a predicate every lane shares
+      const int N0 = A0.fN, N1 = A1.fN, N2 = A2.fN;
+      const int h0 = q0 < 0 ? q0 + N0 : q0, c0 = h0 >= N0 ? h0 - N0 : h0, h1 = q1 < 0 ? q1 + N1 : q1, c1 = h1 >= N1 ? h1 - N1 : h1;
+      const bool ok = c0 >= im.lo[0] && c0 < im.hi[0] && c1 >= im.lo[1] && c1 < im.hi[1];
+      const long long base = im.offset + (long long)sb * im.batch_stride + (long long)c0 * im.stride[0] + (long long)c1 * im.stride[1];
+      const long long s2 = im.stride[2];
+      const int lo2 = im.lo[2], hi2 = im.hi[2], s02w = s02 < 0 ? s02 + N2 : s02;
+      if constexpr (REAL) {
+        const float* x = reinterpret_cast<const float*>(a.in) + base;
+        const int s02bw = s02b < 0 ? s02b + N2 : (s02b >= N2 ? s02b - N2 : s02b);
+        const bool okb = ok && 2u * j2 + 1u < (unsigned)A2.nb;
+#pragma unroll
+        for (int r = 0; r < P; ++r) {
+          const int ta = s02w + r, qa = ta >= N2 ? ta - N2 : ta, tb = s02bw + r, qb = tb >= N2 ? tb - N2 : tb;
+          cf xv = {0.0f, 0.0f};
+          if (ok && qa >= lo2 && qa < hi2) xv.x = x[(long long)qa * s2];
+          if (okb && qb >= lo2 && qb < hi2) xv.y = x[(long long)qb * s2];
+          v[r] = xv;
+        }
+      } else {
+        const cf* x = a.in + base;
+#pragma unroll
+        for (int r = 0; r < P; ++r) {
+          const int t2 = s02w + r, q2 = t2 >= N2 ? t2 - N2 : t2;
+          cf xv = {0.0f, 0.0f};
+          if (ok && q2 >= lo2 && q2 < hi2) xv = x[(long long)q2 * s2];
+          v[r] = xv;
+        }
+      }
+    } else {
       const bool ok = q0 >= im.lo[0] && q0 < im.hi[0] && q1 >= im.lo[1] && q1 < im.hi[1];
       const long long base = im.offset + (long long)sb * im.batch_stride + (long long)q0 * im.stride[0] + (long long)q1 * im.stride[1];   // (dereferenced inside [lo, hi) only)
       const long long s2 = im.stride[2];
@@ -221,5 +255,8 @@ __global__ void __launch_bounds__(C::THREADS, C::WAVES_PER_SIMD) fft_bricks_conv
 
 // the real form: instantiated in a unit of its own (bricks_rconv_ols.hip)
 template <int P_, int THREADS_> struct RBrickCfg : BrickCfg<P_, THREADS_> { static constexpr bool REAL = true; };
+// the circular forms of both (routes bricks-conv-ols[..,wrap], bricks-rconv-ols[..,wrap]): units of their own again (bricks_conv_ols_wrap.hip, bricks_rconv_ols_wrap.hip)
+template <int P_, int THREADS_> struct WBrickCfg : BrickCfg<P_, THREADS_> { static constexpr bool WRAP = true; };
+template <int P_, int THREADS_> struct WRBrickCfg : RBrickCfg<P_, THREADS_> { static constexpr bool WRAP = true; };
 
 }  // namespace mi355

@@ -1109,6 +1109,14 @@ __global__ void __launch_bounds__(C::THREADS, C::THREADS == 256 && C::T == 1 ? 2
 // (the planner keeps fN and the number of block-lines well below 2^31: 32-bit index arithmetic)
 struct RconvOls { int nb, fN, L, w0, pre, plim; };
 struct RconvOlsArgs { LineArgs a; RconvOls o; };     // LineArgs itself stays as it is: every other line kernel takes it by value
+// Circular boundary (the routes' ",wrap" forms): the two overlap-save kernels on a configuration wrapped in OlsWrap take a block's signal indices modulo
+// fN = N = shape: the halo of the blocks at the edge of the domain comes from the other end of the signal, not from zeros.  The planner takes the route
+// only where N >= 2 P, so that s0 + i, with s0 in (-P, N), wraps at most once.  Only the first load differs: the windows of the blocks partition [0, N)
+// without a wrap (plan.cpp ols_axis), and the store is the linear one.  A property of the configuration, not a run-time branch: the linear instances keep
+// their names and their code
+template <class C> struct OlsWrap : C { static constexpr bool OLS_WRAP = true; };
+template <class C, class = void> struct ols_wraps { static constexpr bool value = false; };
+template <class C> struct ols_wraps<C, decltype((void)C::OLS_WRAP)> { static constexpr bool value = C::OLS_WRAP; };
 // The stages and the pair step are the kernel's above, repeated rather than shared: with the body in one template the register allocation
 // of the existing instances moved (P = 16384: 41 -> 43 VGPRs spilt), and those stay what they were (profiles/fftconv_ols_resource_usage.log)
 template <class C>
@@ -1135,7 +1143,66 @@ __global__ void __launch_bounds__(C::THREADS, C::THREADS == 256 && C::T == 1 ? 2
   float* y = reinterpret_cast<float*>(a.out);
   for (long long tile = blockIdx.x; tile < a.num_tiles; tile += gridDim.x) {
     cf v[C::E];
-    {
+    if constexpr (ols_wraps<C>::value) {
+      // circular: block position j is signal index (s0 + j) mod fN.  The head's wrap (s0 < 0) moves the block's origin by fN; a block that holds the seam
+      // has two pieces: positions below c = fN - s0 on the origin A, and positions from c on, which are signal indices j - c, on the origin B = A - fN.
+      // The map's bounds [lo, hi) (on the wrapped index) become one range of block positions per piece, [aLo, aHi) and [bLo, bHi), the same for the whole
+      // line; a block without a seam has an empty B and is the linear case.  z[n] is one 8-byte load where its pair (2n, 2n + 1) lies inside one piece
+      // whose origin is even.  With odd fN the two origins differ in parity and the pair (c - 1, c) straddles the seam: whatever is not a legal pair (that
+      // pair, the odd piece, pairs cut by lo or hi, strided lanes) goes through the rolled 4-byte path of the linear form, sample by sample
+      const SideMap& im = a.imap;
+      int line, u; thread_map<C, 0>(t, line, u);
+      const long long sa = im.stride[im.ax];
+      const unsigned G = (unsigned)(tile * C::T + line), sb = G / (unsigned)o.nb;
+      const int s0 = (int)(G - sb * (unsigned)o.nb) * o.L - o.pre, s0w = s0 < 0 ? s0 + o.fN : s0;
+      const int c = o.fN - s0w < 2 * H ? o.fN - s0w : 2 * H;          // the seam's block position; 2 H: none in this block
+      const bool ok = G < a.num_lines;
+      long long base = im.offset + (long long)sb * im.batch_stride + (long long)s0w * sa;      // origin A
+#ifndef MI355_HOST_EMU
+      if constexpr (C::T == 1) base = (long long)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(base >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)base));
+#endif
+      const int l0 = im.lo[im.ax] - s0w, h0 = im.hi[im.ax] - s0w;
+      const int aLo = l0 < 0 ? 0 : l0, aHi = h0 > c ? c : h0;
+      const int l1 = im.lo[im.ax] + c, h1 = im.hi[im.ax] + c;         // (c <= 2 H <= 8192 and the bounds lie below 2^31 - 16384: no overflow)
+      const int bLo = l1 > 2 * H ? 2 * H : l1, bHi = h1 > 2 * H ? 2 * H : h1;                       // (c = 2 H: empty)
+      const bool pairsA = ok && sa == 1 && (base & 1) == 0, pairsB = ok && sa == 1 && ((base - o.fN) & 1) == 0;
+      const float* xa = xin + base;
+      // `paired`: z[n] is one 8-byte load; a position from c on is read fN samples below origin A
+      const auto paired = [&](int j) { return (pairsA && j >= aLo && j + 1 < aHi) || (pairsB && j >= bLo && j + 1 < bHi); };
+      const auto inside = [&](int j) { return (j >= aLo && j < aHi) || (j >= bLo && j < bHi); };
+      bool rest = false;
+#pragma unroll
+      for (int b = 0; b < I0::NB; ++b) {
+#pragma unroll
+        for (int q = 0; q < I0::R; ++q) {
+          const int n = u + b * C::TPL + q * (H / I0::R), j = 2 * n;
+          cf x = {0.0f, 0.0f};
+          if (paired(j)) x = *reinterpret_cast<const cf*>(xa + (j >= c ? j - o.fN : j));
+          else rest = rest || (ok && (inside(j) || inside(j + 1)));
+          v[b * I0::R + q] = x;
+        }
+      }
+      if (rest) {
+#pragma unroll 4
+        for (int e = 0; e < C::E; ++e) {
+          const int n = u + (e / I0::R) * C::TPL + (e % I0::R) * (H / I0::R), j = 2 * n;
+          cf x = {0.0f, 0.0f};
+          if (!paired(j)) {
+            if (inside(j)) x.x = xa[(long long)(j >= c ? j - o.fN : j) * sa];
+            if (inside(j + 1)) x.y = xa[(long long)(j + 1 >= c ? j + 1 - o.fN : j + 1) * sa];
+          }
+          lds[lds_index<C>(line, n)] = x;
+        }
+#pragma unroll
+        for (int b = 0; b < I0::NB; ++b) {
+#pragma unroll
+          for (int q = 0; q < I0::R; ++q) {
+            const int n = u + b * C::TPL + q * (H / I0::R);
+            if (!paired(2 * n)) v[b * I0::R + q] = lds[lds_index<C>(line, n)];
+          }
+        }
+      }
+    } else {
       const SideMap& im = a.imap;
       int line, u; thread_map<C, 0>(t, line, u);
       const long long sa = im.stride[im.ax];
@@ -1350,7 +1417,23 @@ __global__ void __launch_bounds__(C::THREADS) fft_lines_conv_ols_kernel(const Rc
     const int s0 = (int)(G - sb * (unsigned)o.nb) * o.L - o.pre;       // the block's first signal index
     const bool ok = G < a.num_lines;
     cf v[C::E];
-    {
+    if constexpr (ols_wraps<C>::value) {
+      // circular: position idx of the block is signal index (s0 + idx) mod fN.  The head's wrap (s0 < 0: the first block of a convolution) moves the
+      // block's origin by fN, the same for the whole line; past the seam the index falls back by fN, one conditional subtract.  The map's bounds
+      // ([lo, hi): the data, cut by zeroPad.read) apply to the wrapped index, which is the only one that is dereferenced
+      const cf* x = a.in + (im.offset + (long long)sb * im.batch_stride);
+      const int lo = im.lo[im.ax], hi = im.hi[im.ax], s0w = s0 < 0 ? s0 + o.fN : s0;
+#pragma unroll
+      for (int b = 0; b < I0::NB; ++b) {
+#pragma unroll
+        for (int q = 0; q < I0::R; ++q) {
+          const int at = s0w + u + b * C::TPL + q * (C::N / I0::R), m = at >= o.fN ? at - o.fN : at;
+          cf xv = {0.0f, 0.0f};
+          if (ok && m >= lo && m < hi) xv = x[(long long)m * sa];
+          v[b * I0::R + q] = xv;
+        }
+      }
+    } else {
       const cf* x = a.in + (im.offset + (long long)sb * im.batch_stride + (long long)s0 * sa);    // (dereferenced inside [lo, hi) only)
       const int l0 = im.lo[im.ax] - s0, h0 = im.hi[im.ax] - s0;
       const int lo = l0 < 0 ? 0 : l0, hi = h0 > C::N ? C::N : h0;     // the block's share of [lo, hi)

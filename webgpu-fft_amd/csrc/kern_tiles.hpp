@@ -67,6 +67,7 @@ template <int P_, int R0_, int R1_, int THREADS_>
 struct TileCfg {
   static constexpr int P = P_, R0 = R0_, R1 = R1_, THREADS = THREADS_;
   static constexpr bool REAL = false;               // RTileCfg: real tile pairs
+  static constexpr bool WRAP = false;               // WTileCfg, WRTileCfg: circular boundary, signal indices modulo fN_a
   static_assert(R0 * R1 == P, "radix product");
   static_assert(THREADS % P == 0 && THREADS <= 1024, "a thread stays on one line");
   static constexpr int TPL = THREADS / P;           // threads per line
@@ -155,7 +156,48 @@ __global__ void __launch_bounds__(C::THREADS, C::WAVES_PER_SIMD) fft_tiles_conv_
     const int s00 = (int)j0 * A0.L - A0.pre, s01 = (int)(REAL ? 2u * j1 : j1) * A1.L - A1.pre;      // the tile's first signal index on each axis (REAL: partner a's)
     cf v[C::E];
     // ---- forward, columns: stage 0 from global memory (this lane: column i0 = line) ----
-    if constexpr (REAL) {
+    if constexpr (C::WRAP) {
+      // circular: signal index (s0_a + i_a) mod fN_a on both axes; fN_a >= 2 P, so one conditional add (the head of a convolution's first tile) and one
+      // conditional subtract (past the seam) wrap it.  Axis 0 is the lane's: its wrapped column once per tile.  On axis 1 the head's wrap moves the tile's
+      // origin, the same for every lane; past the seam the index falls back by fN_1.  The map's bounds apply to the wrapped indices, the only ones that
+      // are dereferenced.  REAL: the two partners wrap independently; an absent partner b (odd nb_1) loads nothing, under a predicate every lane shares
+      const int N0 = A0.fN, N1 = A1.fN, p0 = s00 + line, h0 = p0 < 0 ? p0 + N0 : p0, q0 = h0 >= N0 ? h0 - N0 : h0;
+      const bool ok0 = q0 >= im.lo[0] && q0 < im.hi[0];
+      const long long base = im.offset + (long long)sb * im.batch_stride + (long long)q0 * im.stride[0];
+      const int lo1 = im.lo[1], hi1 = im.hi[1], s01w = s01 < 0 ? s01 + N1 : s01;
+      const long long s1 = im.stride[1];
+      int ul = u;
+      if constexpr (C::REFORM_POSITIONS) MI_TILE_OPAQUE_LANE(ul);
+      if constexpr (REAL) {
+        const float* x = reinterpret_cast<const float*>(a.in) + base;
+        const int s01b = s01 + A1.L, s01bw = s01b < 0 ? s01b + N1 : (s01b >= N1 ? s01b - N1 : s01b);
+        const bool okb = ok0 && 2u * j1 + 1u < (unsigned)A1.nb;
+#pragma unroll
+        for (int b = 0; b < I0::NB; ++b) {
+#pragma unroll
+          for (int q = 0; q < I0::R; ++q) {
+            const int i1 = ul + b * C::TPL + q * (C::P / I0::R);
+            const int ta = s01w + i1, qa = ta >= N1 ? ta - N1 : ta, tb = s01bw + i1, qb = tb >= N1 ? tb - N1 : tb;
+            cf xv = {0.0f, 0.0f};
+            if (ok0 && qa >= lo1 && qa < hi1) xv.x = x[(long long)qa * s1];
+            if (okb && qb >= lo1 && qb < hi1) xv.y = x[(long long)qb * s1];
+            v[b * I0::R + q] = xv;
+          }
+        }
+      } else {
+        const cf* x = a.in + base;
+#pragma unroll
+        for (int b = 0; b < I0::NB; ++b) {
+#pragma unroll
+          for (int q = 0; q < I0::R; ++q) {
+            const int t1 = s01w + ul + b * C::TPL + q * (C::P / I0::R), q1 = t1 >= N1 ? t1 - N1 : t1;
+            cf xv = {0.0f, 0.0f};
+            if (ok0 && q1 >= lo1 && q1 < hi1) xv = x[(long long)q1 * s1];
+            v[b * I0::R + q] = xv;
+          }
+        }
+      }
+    } else if constexpr (REAL) {
       const int q0 = s00 + line;
       const bool ok0 = q0 >= im.lo[0] && q0 < im.hi[0];
       const float* x = reinterpret_cast<const float*>(a.in) + (im.offset + (long long)sb * im.batch_stride + (long long)q0 * im.stride[0]);   // (dereferenced inside [lo, hi) only)
@@ -311,5 +353,8 @@ __global__ void __launch_bounds__(C::THREADS, C::WAVES_PER_SIMD) fft_tiles_conv_
 
 // the real form: instantiated in a unit of its own (tiles_rconv_ols.hip)
 template <int P_, int R0_, int R1_, int THREADS_> struct RTileCfg : TileCfg<P_, R0_, R1_, THREADS_> { static constexpr bool REAL = true; };
+// the circular forms of both (routes tiles-conv-ols[..,wrap], tiles-rconv-ols[..,wrap]): units of their own again (tiles_conv_ols_wrap.hip, tiles_rconv_ols_wrap.hip)
+template <int P_, int R0_, int R1_, int THREADS_> struct WTileCfg : TileCfg<P_, R0_, R1_, THREADS_> { static constexpr bool WRAP = true; };
+template <int P_, int R0_, int R1_, int THREADS_> struct WRTileCfg : RTileCfg<P_, R0_, R1_, THREADS_> { static constexpr bool WRAP = true; };
 
 }  // namespace mi355

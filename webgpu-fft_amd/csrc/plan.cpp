@@ -193,6 +193,7 @@ PlannerOptions planner_options_from_env() {
   if (const char* s = std::getenv("MI355FFT_RCONV_OLS2D")) o.rconv_ols2d = std::atoi(s);
   if (const char* s = std::getenv("MI355FFT_CONV_OLS3D")) o.conv_ols3d = std::atoi(s);
   if (const char* s = std::getenv("MI355FFT_RCONV_OLS3D")) o.rconv_ols3d = std::atoi(s);
+  if (const char* s = std::getenv("MI355FFT_OLS_CIRCULAR")) o.ols_circular = std::atoi(s);
   if (const char* s = std::getenv("MI355FFT_SOLO_MAX_KB")) { const int v = std::atoi(s); if (v >= 0) o.solo_max_kb = v; }
   if (const char* s = std::getenv("MI355FFT_SOLO_CAP_MB")) { const int v = std::atoi(s); if (v >= 1) o.solo_cap_mb = v; }
   if (const char* s = std::getenv("MI355FFT_XCD_SLOTS")) { const int v = std::atoi(s); if (v >= 0 && v <= 2) o.xcd_slots = v; }
@@ -1839,7 +1840,7 @@ int64_t conv_bricks_block(const int64_t* fs, const int64_t* ks) { return bricks_
 int64_t rconv_bricks_block(const int64_t* fs, const int64_t* ks) { return bricks_block(fs, ks, RCONV_BRICKS_MAX_KERNEL); }
 
 // ---- overlap-save: what its six routes share --------------------------------------------------------------------------------------------
-// Linear modes only.  A line (rank 1), an image (rank 2) or a volume (rank 3) is cut into blocks of P points per axis, and each block runs forward transform, product with a kernel
+// Linear modes, and circular boundaries in the WRAP form described above ols_circular_take.  A line (rank 1), an image (rank 2) or a volume (rank 3) is cut into blocks of P points per axis, and each block runs forward transform, product with a kernel
 // spectrum on P points and inverse transform inside one workgroup: no padded or exact-length domain, no transform of a whole line, no Bluestein or column
 // launch.  One launch writes the K kernel spectra into the workspace, then one launch per kernel follows: 1 + K launches for any length.  Strided lanes,
 // channel-policy lanes, zeroPad and the crop ride the two address maps (the real routes stand in front of build_fftconv_real's rejection of strided sides
@@ -1854,13 +1855,32 @@ int64_t ols_switch(int64_t sw, bool legal, int64_t rule) { return sw > 1 ? (lega
 // s0 = j L - pre, pre = M - 1, and gives L = P - pre results.  A real line is transformed as P / 2 complex points, so pre and L stay even there:
 // pre = M - 1 + e, e = (M - 1) & 1, L = (P - pre) & ~1.  The result window of a block starts at w0 = pre convolving and at e correlating (the conjugated
 // spectrum puts the wrap-around at the top of the block); signal indices stay below plim.  nb = 0: the block does not fit (P = 0 included)
-OlsAxis ols_axis(int64_t fN, int64_t shape, int64_t M, int64_t P, bool corr, bool real_line) {
+//
+// `wrap` (circular boundary: fN = shape = N, the output has N points and no crop offset): L is the linear form's, nb = ceil(N / L), fN = plim = N, and
+// block j holds signal indices j L - pre .. j L - pre + P - 1 TAKEN MODULO N.  Convolving, pre = w0 = M - 1 (+ e): block j stores the results of signal
+// positions [j L, j L + L) below N.  Correlating, y[m] = sum_t conj(h[t]) x[(m + t) mod N] looks forward only, so the blocks need no head: pre = w0 = 0
+// (no head of M - 1 points with a wrapping store), block j starts at j L, only its tail wraps, and its wrap-free window is again [j L, j L + L) below N.  In both
+// modes the windows of the nb blocks partition [0, N): every output element is stored by exactly one block, and the store rule is the linear one
+// (q = s0 + i is never negative inside a window, so m = q)
+OlsAxis ols_axis(int64_t fN, int64_t shape, int64_t M, int64_t P, bool corr, bool real_line, bool wrap = false) {
   OlsAxis a;
   a.pre = real_line ? M - 1 + ((M - 1) & 1) : M - 1;
   a.L = real_line ? (P - a.pre) & ~(int64_t)1 : P - a.pre;
   a.nb = a.L >= 2 ? (fN + a.L - 1) / a.L : 0;
   a.fN = fN; a.plim = corr ? shape : fN; a.w0 = corr ? a.pre - (M - 1) : a.pre;
+  if (wrap) { a.plim = fN; if (corr) a.pre = 0; a.w0 = a.pre; }
   return a;
+}
+
+// Circular boundaries on the six routes (PlannerOptions::ols_circular; `P` is the block the route's own rule names for the domain `shape`, 0: none).  The
+// route is taken only where shape[a] >= 2 P on every axis: any index a block (or the absent partner of a real pair) forms then wraps at most once.  2: every
+// such request; 1: those with an axis that is no power of two (their earlier plans hold Bluestein, mixed-radix or per-radix stage launches) and lines above
+// 2^22 points; power-of-two domains keep the routes the tests pin them to
+bool ols_circular_take(const PlannerOptions& opt, const int64_t* shape, int rank, int64_t P) {
+  if (!opt.ols_circular || P <= 0) return false;
+  bool pow2 = true;
+  for (int a = 0; a < rank; ++a) { if (shape[a] < 2 * P) return false; pow2 = pow2 && is_pow2(shape[a]); }
+  return opt.ols_circular >= 2 || !pow2 || (rank == 1 && shape[0] > ((int64_t)1 << 22));
 }
 
 // One launch per kernel: K copies of the prepared step `proto`, launch k with kernel k's spectrum (`spectra` + k * `bytes`) in p[slot] and kernel k's
@@ -1901,10 +1921,11 @@ Step conv_line_proto(const Builder& b, const mi355fft_plan_desc& d, const ConvGe
 bool emit_tiles_ols(Builder& b, const mi355fft_plan_desc& d, const ConvGeom& g, bool real) {
   const int64_t *ks = g.ks, *fs = g.fs, lim = ((int64_t)1 << 31) - 16384;   // (the kernel's indices are 32-bit)
   if (fs[0] >= lim || fs[1] >= lim) return false;
-  const int64_t sw = real ? b.opt.rconv_ols2d : b.opt.conv_ols2d;
-  const int64_t P = ols_switch(sw, sw == 64 || sw == 128, real ? rconv_tiles_block(fs[0], fs[1], ks[0], ks[1]) : conv_tiles_block(fs[0], fs[1], ks[0], ks[1]));
+  const int64_t sw = real ? b.opt.rconv_ols2d : b.opt.conv_ols2d, rule = real ? rconv_tiles_block(fs[0], fs[1], ks[0], ks[1]) : conv_tiles_block(fs[0], fs[1], ks[0], ks[1]);
+  const bool wrap = !g.linear;                                              // (circular: the rule's tile alone, a forced tile moves linear requests only)
+  const int64_t P = wrap ? (ols_circular_take(b.opt, d.shape, 2, rule) ? rule : 0) : ols_switch(sw, sw == 64 || sw == 128, rule);
   const TileKernelMeta* tm = P ? find_tile_kernel((int)P, real) : nullptr;
-  const OlsAxis ax[2] = {ols_axis(fs[0], d.shape[0], ks[0], P, g.corr, false), ols_axis(fs[1], d.shape[1], ks[1], P, g.corr, false)};
+  const OlsAxis ax[2] = {ols_axis(fs[0], d.shape[0], ks[0], P, g.corr, false, wrap), ols_axis(fs[1], d.shape[1], ks[1], P, g.corr, false, wrap)};
   const int64_t items = g.B * ax[0].nb * (real ? (ax[1].nb + 1) / 2 : ax[1].nb);
   if (!tm || ax[0].L < 2 || ax[1].L < 2 || ax[0].nb * ax[1].nb >= lim || items >= lim) return false;
   const int64_t pd[2] = {P, P};
@@ -1933,12 +1954,12 @@ bool emit_tiles_ols(Builder& b, const mi355fft_plan_desc& d, const ConvGeom& g, 
   b.ir.steps.push_back(sp);
   b.ir.route += (real ? "tiles-rspectrum" : "tiles-spectrum") + tile + "] ";
   Step proto = launch(real ? LM_TILES_RCONV_OLS : LM_TILES_CONV_OLS, PtrRef(BUF_INPUT, 0), PtrRef(BUF_OUTPUT, 0), items);
-  proto.i[LS_CONJ] = g.corr ? 1 : 0;
+  proto.i[LS_CONJ] = g.corr ? 1 : 0; proto.i[LS_OLS_WRAP] = wrap ? 1 : 0;
   ols_store(proto.i, ax[0], ax[1]);
   proto.f[F_SCALE] = (float)(1.0 / (double)(P * P));
   proto.imap = conv_load_map(d, g, fs, 2);
   push_per_kernel(b, d, g, proto, LP_MUL_SPECTRUM, G, P * P * 8);
-  b.ir.route += (real ? "tiles-rconv-ols" : "tiles-conv-ols") + tile + ",L=" + std::to_string(ax[0].L) + "x" + std::to_string(ax[1].L) + "] ";
+  b.ir.route += (real ? "tiles-rconv-ols" : "tiles-conv-ols") + tile + ",L=" + std::to_string(ax[0].L) + "x" + std::to_string(ax[1].L) + (wrap ? ",wrap] " : "] ");
   return true;
 }
 
@@ -1950,11 +1971,12 @@ bool emit_tiles_ols(Builder& b, const mi355fft_plan_desc& d, const ConvGeom& g, 
 bool emit_bricks_ols(Builder& b, const mi355fft_plan_desc& d, const ConvGeom& g, bool real) {
   const int64_t *ks = g.ks, *fs = g.fs, lim = ((int64_t)1 << 31) - 16384;   // (the kernel's indices are 32-bit)
   if (fs[0] >= lim || fs[1] >= lim || fs[2] >= lim) return false;
-  const int64_t sw = real ? b.opt.rconv_ols3d : b.opt.conv_ols3d;
-  const int64_t P = ols_switch(sw, sw == 16, real ? rconv_bricks_block(fs, ks) : conv_bricks_block(fs, ks));
+  const int64_t sw = real ? b.opt.rconv_ols3d : b.opt.conv_ols3d, rule = real ? rconv_bricks_block(fs, ks) : conv_bricks_block(fs, ks);
+  const bool wrap = !g.linear;                                              // (circular: as in emit_tiles_ols)
+  const int64_t P = wrap ? (ols_circular_take(b.opt, d.shape, 3, rule) ? rule : 0) : ols_switch(sw, sw == 16, rule);
   const BrickKernelMeta* bm = P ? find_brick_kernel((int)P, real) : nullptr;
   OlsAxis ax[3];
-  for (int a = 0; a < 3; ++a) ax[a] = ols_axis(fs[a], d.shape[a], ks[a], P, g.corr, false);
+  for (int a = 0; a < 3; ++a) ax[a] = ols_axis(fs[a], d.shape[a], ks[a], P, g.corr, false, wrap);
   if (!bm || ax[0].L < 2 || ax[1].L < 2 || ax[2].L < 2) return false;
   const int64_t n01 = ax[0].nb * ax[1].nb;                                  // (each nb < 2^31: the products below stay inside 64 bits step by step)
   if (n01 >= lim || n01 * ax[2].nb >= lim) return false;
@@ -1983,12 +2005,12 @@ bool emit_bricks_ols(Builder& b, const mi355fft_plan_desc& d, const ConvGeom& g,
   b.ir.steps.push_back(sp);
   b.ir.route += (real ? "bricks-rspectrum" : "bricks-spectrum") + brick + "] ";
   Step proto = launch(real ? LM_BRICKS_RCONV_OLS : LM_BRICKS_CONV_OLS, PtrRef(BUF_INPUT, 0), PtrRef(BUF_OUTPUT, 0), items);
-  proto.i[LS_CONJ] = g.corr ? 1 : 0;
+  proto.i[LS_CONJ] = g.corr ? 1 : 0; proto.i[LS_OLS_WRAP] = wrap ? 1 : 0;
   ols_store(proto.i, ax[0], ax[1], &ax[2]);
   proto.f[F_SCALE] = (float)(1.0 / (double)V);
   proto.imap = conv_load_map(d, g, fs, 3);
   push_per_kernel(b, d, g, proto, LP_MUL_SPECTRUM, G, V * 8);
-  b.ir.route += (real ? "bricks-rconv-ols" : "bricks-conv-ols") + brick + ",L=" + std::to_string(ax[0].L) + "x" + std::to_string(ax[1].L) + "x" + std::to_string(ax[2].L) + "] ";
+  b.ir.route += (real ? "bricks-rconv-ols" : "bricks-conv-ols") + brick + ",L=" + std::to_string(ax[0].L) + "x" + std::to_string(ax[1].L) + "x" + std::to_string(ax[2].L) + (wrap ? ",wrap] " : "] ");
   return true;
 }
 
@@ -2003,10 +2025,12 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
   const bool zpad = d.zero_read.enabled || d.zero_write.enabled;
   // ---- overlap-save: long complex lines, short kernels, one launch per kernel on blocks of P points (kern_lines.hpp fft_lines_conv_ols_kernel has the
   // index map); K P 8 bytes of workspace for any length.  The switch's rule is conv_ols_block
-  if (rank == 1 && g.linear && b.opt.conv_ols != 0 && b.opt.conv_lines && !b.opt.force_generic && g.lfN < ((int64_t)1 << 31) - 16384) {
-    const int64_t sw = b.opt.conv_ols;
-    const int64_t P = ols_switch(sw, is_pow2(sw) && sw >= 128 && sw <= 4096, conv_ols_block(g.lfN, ks[0]));
-    const OlsAxis ax = ols_axis(g.lfN, d.shape[0], ks[0], P, g.corr, false);
+  // Circular requests (PlannerOptions::ols_circular, ols_circular_take) run the kernel's WRAP instances on the rule's block alone
+  if (rank == 1 && b.opt.conv_ols != 0 && b.opt.conv_lines && !b.opt.force_generic && g.lfN < ((int64_t)1 << 31) - 16384) {
+    const int64_t sw = b.opt.conv_ols, rule = conv_ols_block(g.lfN, ks[0]);
+    const bool wrap = !g.linear;
+    const int64_t P = wrap ? (ols_circular_take(b.opt, d.shape, 1, rule) ? rule : 0) : ols_switch(sw, is_pow2(sw) && sw >= 128 && sw <= 4096, rule);
+    const OlsAxis ax = ols_axis(g.lfN, d.shape[0], ks[0], P, g.corr, false, wrap);
     const int64_t lines = B * ax.nb;
     const LineKernelMeta* om = (P && ax.L >= 2 && lines < ((int64_t)1 << 31) - 64 && b.axis_mappable(P, 1, false)) ? find_line_kernel((int)P, false, false, false, false, 0) : nullptr;
     if (om && om->lds_bytes > 0 && om->R1 > 1) {
@@ -2015,15 +2039,16 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
       if (int rv = b.emit_axis_mapped(PtrRef(BUF_KERNEL, 0), G, P, 1, K, false, 1.0f, conv_kernel_map(g, pd, 1), Builder::dense_map(pd, 1), 0)) return rv;
       Step proto = conv_line_proto(b, d, g, *om, LM_CONV_OLS, lines, P, P, b.line_tables(*om));
       ols_store(proto.i, ax);
+      proto.i[LS_OLS_WRAP] = wrap ? 1 : 0;
       push_per_kernel(b, d, g, proto, LP_MUL_SPECTRUM, G, P * 8);
-      b.ir.route += "lines-conv-ols[N=" + std::to_string(P) + ",L=" + std::to_string(ax.L) + "] ";
+      b.ir.route += "lines-conv-ols[N=" + std::to_string(P) + ",L=" + std::to_string(ax.L) + (wrap ? ",wrap] " : "] ");
       return MI355FFT_OK;
     }
   }
   // ---- overlap-save in two dimensions (emit_tiles_ols); the switch's rule is conv_tiles_block
-  if (rank == 2 && g.linear && b.opt.conv_ols2d != 0 && b.opt.conv_lines && !b.opt.force_generic && b.opt.fuse_views && emit_tiles_ols(b, d, g, false)) return MI355FFT_OK;
+  if (rank == 2 && b.opt.conv_ols2d != 0 && b.opt.conv_lines && !b.opt.force_generic && b.opt.fuse_views && emit_tiles_ols(b, d, g, false)) return MI355FFT_OK;
   // ---- overlap-save in three dimensions (emit_bricks_ols); the switch's rule is conv_bricks_block
-  if (rank == 3 && g.linear && b.opt.conv_ols3d != 0 && b.opt.conv_lines && !b.opt.force_generic && b.opt.fuse_views && emit_bricks_ols(b, d, g, false)) return MI355FFT_OK;
+  if (rank == 3 && b.opt.conv_ols3d != 0 && b.opt.conv_lines && !b.opt.force_generic && b.opt.fuse_views && emit_bricks_ols(b, d, g, false)) return MI355FFT_OK;
   // Long rank-1 linear modes: the next power of two keeps the transforms off the Bluestein / mixed-radix routes (ConvGeom)
   if (b.opt.conv_pad && rank == 1 && g.linear && g.lfN > 16384 && g.lfN <= ((int64_t)1 << 22) && !is_pow2(g.lfN)) {
     int64_t P = 32768;
@@ -2209,6 +2234,8 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
 //                     emitters on kernels and data, then per kernel a pointwise pass over the packed bins, the inverse, zeroPad.write
 //                     and the real crop
 //   rconv-widened     circular with odd shape[0] (no even domain is allowed): the complex plan between widening / narrowing passes
+// The three overlap-save routes also take circular requests inside their bounds (tags ending in ",wrap]": ols_circular_take), odd lines and strided sides
+// of rank 2 and 3 among them, which then have a direct plan
 // Validation, shapes, lanes and the padded-domain index map are ConvGeom's, shared with build_fftconv; each route hands it the
 // axis-0 length it transforms on.
 constexpr int64_t OLS_MAX_KERNEL = 4096;   // the longest kernel the default rule gives to overlap-save: the longest one measured (3.8x / 2.5x ahead at K = 1 / 4)
@@ -2224,16 +2251,18 @@ int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err
 
   // ---- overlap-save: long real lines, short kernels, one launch per kernel on blocks of P points, each running the pipeline of lines-rconv
   // (kern_lines.hpp fft_lines_rconv_ols_kernel has the index map).  The switch's rule, whatever the line's length when a block is forced:
-  if (rank == 1 && linear && b.opt.rconv_fused == 1 && b.opt.rconv_ols != 0 && lfN < ((int64_t)1 << 31) - 16384) {
+  // Circular requests (PlannerOptions::ols_circular, ols_circular_take) run the kernel's WRAP instances on the rule's block alone
+  if (rank == 1 && b.opt.rconv_fused == 1 && b.opt.rconv_ols != 0 && !(b.opt.force_generic && !linear) && lfN < ((int64_t)1 << 31) - 16384) {
     const int64_t M = ks[0], sw = b.opt.rconv_ols;
+    const bool wrap = !linear;
     // measured (profiles/fftconv_ols_ab.log, 256 x 2^20 (*) {31, 255, 1024, 4096}, K = 1 and 4, and three longer / shorter lines): every block length
     // 1024 .. 8192 is 2.5-8x ahead of pad[..] rconv[K] and 46-66x ahead of the Bluestein plans above 2^22; the fastest P is the smallest power of two
     // >= 8 (M - 1) from 1024 on (M = 31: 1024, 255: 2048, 1024 and 4096: 8192), except that P = 4096 is behind 8192 on every request (its instance
     // holds 190 VGPRs: two workgroups per CU where the LDS would take three) and is never chosen
     int64_t rule = 0;
     if (lfN > 8192 && M <= OLS_MAX_KERNEL) { rule = 1024; while (rule < 8 * (M - 1) && rule < 8192) rule <<= 1; if (rule == 4096) rule = 8192; }
-    const int64_t P = ols_switch(sw, is_pow2(sw) && sw >= 128 && sw <= 8192, rule);
-    const OlsAxis ax = ols_axis(lfN, d.shape[0], M, P, corr, true);
+    const int64_t P = wrap ? (ols_circular_take(b.opt, d.shape, 1, rule) ? rule : 0) : ols_switch(sw, is_pow2(sw) && sw >= 128 && sw <= 8192, rule);
+    const OlsAxis ax = ols_axis(lfN, d.shape[0], M, P, corr, true, wrap);
     const int64_t lines = B * ax.nb;
     const LineKernelMeta* om = (P && ax.L >= 2 && lines < ((int64_t)1 << 31) - 64) ? b.lines_r2c_kernel(P, false, true) : nullptr;
     if (om) {
@@ -2246,15 +2275,16 @@ int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err
       const PtrRef tables = b.line_tables(*om), proots = b.rconv_roots(P);
       Step proto = conv_line_proto(b, d, g, *om, LM_RCONV_OLS, lines, H, P, tables, proots);
       ols_store(proto.i, ax);
+      proto.i[LS_OLS_WRAP] = wrap ? 1 : 0;
       push_per_kernel(b, d, g, proto, LP_RCONV_SPECTRUM, G, (H + 1) * 8);
-      b.ir.route += "lines-rconv-ols[N=" + std::to_string(P) + ",L=" + std::to_string(ax.L) + "] ";
+      b.ir.route += "lines-rconv-ols[N=" + std::to_string(P) + ",L=" + std::to_string(ax.L) + (wrap ? ",wrap] " : "] ");
       return MI355FFT_OK;
     }
   }
   // ---- overlap-save in two dimensions on real tile pairs (emit_tiles_ols); the switch's rule is rconv_tiles_block
-  if (rank == 2 && linear && b.opt.rconv_ols2d != 0 && b.opt.rconv_fused != 0 && !b.opt.force_generic && emit_tiles_ols(b, d, g, true)) return MI355FFT_OK;
+  if (rank == 2 && (linear || b.opt.fuse_views) && b.opt.rconv_ols2d != 0 && b.opt.rconv_fused != 0 && !b.opt.force_generic && emit_tiles_ols(b, d, g, true)) return MI355FFT_OK;
   // ---- overlap-save in three dimensions on real brick pairs (emit_bricks_ols); the switch's rule is rconv_bricks_block
-  if (rank == 3 && linear && b.opt.rconv_ols3d != 0 && b.opt.rconv_fused != 0 && !b.opt.force_generic && emit_bricks_ols(b, d, g, true)) return MI355FFT_OK;
+  if (rank == 3 && (linear || b.opt.fuse_views) && b.opt.rconv_ols3d != 0 && b.opt.rconv_fused != 0 && !b.opt.force_generic && emit_bricks_ols(b, d, g, true)) return MI355FFT_OK;
 
   // ---- route 1: one launch per kernel on the line kernels --------------------------------------------------------------------
   int64_t P1 = 0;

@@ -186,7 +186,8 @@ enum LinesSlot {
   LS_RCONV_SPLIT = 13, LS_OLS_FN = 13,       // LM_RCONV: ConvGeom split / padD;  the overlap-save modes: the block geometry, written and read by ols_store / ols_axis_of
   LS_RCONV_PADD = 14, LS_OLS_PLIM = 14,      // below and by nothing else
   LS_OLS_NB = 15, LS_OLS_L = 16, LS_OLS_W0 = 17, LS_OLS_PRE = 18,
-  LS_LAST = LS_OLS_PRE
+  LS_OLS_WRAP = 19,                          // the overlap-save modes: circular boundary, a block's signal indices are taken modulo fN (the kernels' WRAP instances)
+  LS_LAST = LS_OLS_WRAP
 };
 static_assert(LS_LAST < STEP_INTS, "ST_LINES slots");
 // axis 2 of the brick modes sits on the four-step slots, which no tile or brick kernel reads (they have no root tables), outside the six LS_OLS slots
@@ -408,6 +409,14 @@ struct PlannerOptions {
                                        // one launch per kernel whatever the volume's size (kern_bricks.hpp fft_bricks_conv_ols_kernel); 1: where measured ahead (plan.cpp
                                        // conv_bricks_block, rconv_bricks_block); 0: never; 16: the brick on every request it fits (tests and measurement).  conv_lines = 0
                                        // and force_generic (complex), rconv_fused = 0 and force_generic (real) come first
+#ifdef MI355_HOST_EMU
+  int ols_circular = std::getenv("MI355_EMU_OLS_CIRCULAR") ? std::atoi(std::getenv("MI355_EMU_OLS_CIRCULAR")) : 1;
+#else
+  int ols_circular = 1;
+#endif
+                                       // fftconv / real fftconv, circular boundary: the wrapping form of the overlap-save routes above (block sizes and kernel bounds of their rules,
+                                       // shape[a] >= 2 P on every axis); 1: where measured ahead (plan.cpp ols_circular_block); 0: never; 2: every request inside those bounds,
+                                       // power-of-two domains included (tests and measurement).  A route's own switch at 0 and the switches in front of it turn its circular form off too
   int conv_lines = 1;                  // fftconv: kernel-spectrum product fused behind the forward line FFT (1-D, power-of-two FFT length <= max_line)
   int trig_fused = 1;                  // dct2 / dst2 of dense lines (half length a line-kernel size): permutation + real FFT + phase in one launch
   int trig_real = 1;                   // dct2/dst2/dct3/dst3 along a dense even axis through a real FFT of length N (kern_trig.hpp)
