@@ -19,6 +19,9 @@ where the plan's contract leaves the output alone), and the bound is built from 
   global      rel_l2(got, exact) <= 4 Y          (4: the ratio test_gpu_parity.test_accuracy_against_f64 uses against the same oracle)
   worst class rms of the error over a class / rms of exact over everything <= 8 Y.  The classes: every batch line, and for rank-1 lines
               of L >= 4096 points the sets k mod s and k div s with s from both factors of the route's N1xN2 tag (none: s = 2^floor(log2(L) / 2)).
+              For every case of rank > 1 that is no fftconv, for every axis a of the output (the packed axis of r2c has N0 / 2 + 1 indices)
+              and every index i, the written elements with index i on axis a: one column-tile lane, one ragged last tile, one index of a
+              strided axis (logged as [axis a idx i]).
               Classes of fewer than 256 written real values are left out (256 values scatter by less than 20 %).
 
 Both metrics run over the elements the plan writes.  f16-storage plans are not here: their error is the final binary16 rounding, which
@@ -153,10 +156,18 @@ def exact_r2c(o, x):
 
 
 def exact_c2r(o, x):
-    """rank 1; ioView as test_r2c_c2r_ioview_and_zeropad uses it (the first bins in, a window of a larger real array out)"""
-    n, batch = o["shape"][0], o["batch"]
-    assert len(o["shape"]) == 1 and not o.get("zeroPad")
+    """any rank without views: numpy's irfftn over the plan's axes of the packed spectrum (the halved axis is numpy's last: the plan's
+    axis 0).  rank 1 also with ioView as test_r2c_c2r_ioview_and_zeropad uses it (the first bins in, a window of a larger real array out)"""
+    shape, batch = o["shape"], o["batch"]
+    assert not o.get("zeroPad")
     view = o.get("ioView")
+    if len(shape) > 1:
+        assert not view
+        n = int(np.prod(shape))
+        spec = _cplx(x, batch, [shape[0] // 2 + 1] + list(shape[1:]))
+        sig = np.fft.irfftn(spec, s=tuple(reversed(shape)), axes=tuple(range(1, len(shape) + 1))) * n * _scale(o, n)
+        return sig.reshape(-1)
+    n = shape[0]
     bins = view["input"]["shape"][0] if view else n // 2 + 1
     spec = np.zeros((batch, n // 2 + 1), np.complex128)
     spec[:, :bins] = _cplx(x, batch, [bins])
@@ -206,9 +217,14 @@ def trig1d_exact(x, kind):
 
 
 def exact_trig(oracle, o, x):
-    assert len(o["shape"]) == 1
-    n, batch = o["shape"][0], o["batch"]
-    return (trig1d_exact(np.asarray(x, np.float64).reshape(batch, n), oracle.trig_kind(o["type"], o["direction"])) * _scale(o, n)).reshape(-1)
+    """any rank: trig1d_exact along every axis in turn, one final scale by prod(shape) (as oracle.trig_ref_batch, without its f32 stores)"""
+    shape, batch, n = o["shape"], o["batch"], int(np.prod(o["shape"]))
+    kind = oracle.trig_kind(o["type"], o["direction"])
+    v = np.asarray(x, np.float64).reshape(batch, *reversed(shape))
+    for a in range(len(shape)):
+        m = np.moveaxis(v, len(shape) - a, -1)          # the plan's axis a, last
+        v = np.moveaxis(trig1d_exact(m.reshape(-1, shape[a]), kind).reshape(m.shape), -1, len(shape) - a)
+    return (v * _scale(o, n)).reshape(-1)
 
 
 def exact_fftconv(o, x, kern):
@@ -281,8 +297,9 @@ def _in_real(seed):
 def _in_spectrum(seed):
     """the float64 spectrum of seeded real noise, scaled to the signal's rms and rounded to f32: Hermitian input of a c2r plan"""
     def f(oracle, o):
-        n, batch = o["shape"][0], o["batch"]
-        spec = np.fft.rfft(oracle.random_real_batch(n, batch, seed).astype(np.float64), axis=1) / np.sqrt(n)
+        shape, batch, n = o["shape"], o["batch"], int(np.prod(o["shape"]))
+        sig = oracle.random_real_batch(n, batch, seed).astype(np.float64).reshape(batch, *reversed(shape))
+        spec = np.fft.rfftn(sig, axes=tuple(range(1, len(shape) + 1))) / np.sqrt(n)      # any rank; the halved axis is the plan's axis 0
         return _inter(spec).astype(np.float32).reshape(-1), None
     return f
 
@@ -448,18 +465,23 @@ def forget(case):
 
 
 # ---- the metrics --------------------------------------------------------------------------------------------------------------------
+def _out_shape(o):
+    """the shape of a batch item of the output of a plan that is no fftconv: the output view's, the packed one of r2c, else the plan's"""
+    view = (o.get("ioView") or {}).get("output")
+    return list(view["shape"] if view else [o["shape"][0] // 2 + 1] + list(o["shape"][1:]) if o["type"] == "r2c" else o["shape"])
+
+
 def _line_geometry(case):
     """(lines, points a line, reals a point, rank-1) of the plan's output"""
     o = case.opts
     typ, rank1 = o["type"], len(o["shape"]) == 1
-    view = (o.get("ioView") or {}).get("output")
     if typ == "fftconv":
         fc = o["fftConv"]
         ks, b = fc.get("kernelShape") or o["shape"], fc.get("boundary", "circular")
         shape = {"circular": o["shape"], "linear-same": o["shape"], "linear-full": [s + k - 1 for s, k in zip(o["shape"], ks)],
                  "linear-valid": [s - k + 1 for s, k in zip(o["shape"], ks)]}[b]
         return o["batch"] * fc.get("kernelCount", 1), int(np.prod(shape)), 1 if o.get("layout", {}).get("interleavedComplex") is False else 2, rank1
-    shape = view["shape"] if view else [o["shape"][0] // 2 + 1] + list(o["shape"][1:]) if typ == "r2c" else o["shape"]
+    shape = _out_shape(o)
     if _lanes(o):       # every lane of the buffer is a line; the untouched ones hold no written value and form no class
         return o["batch"] * _lanes(o)[0], int(np.prod(shape)), 2, rank1
     return o["batch"], int(np.prod(shape)), 2 if typ in ("c2c", "r2c") else 1, rank1
@@ -472,8 +494,8 @@ def _splits(route, L):
     return [1 << ((L.bit_length() - 1) // 2)]
 
 
-def measure(oracle, case, route, got, want, keep):
-    """asserts both bounds; returns the log line of the case"""
+def measure(oracle, case, route, got, want, keep, prefix=""):
+    """asserts both bounds; returns the log line of the case (prefix: what a caller's log puts in front of it)"""
     what = f"{case.name} ({route.strip()})"
     a = np.asarray(got, np.float32).astype(np.float64)
     w = ~keep
@@ -493,6 +515,12 @@ def measure(oracle, case, route, got, want, keep):
             e2 = np.pad(e3.sum(axis=(0, 2)), (0, pad)).reshape(-1, s)
             n2 = np.pad(w3.sum(axis=(0, 2)), (0, pad)).reshape(-1, s)
             groups += [(f"k mod {s}", e2.sum(axis=0), n2.sum(axis=0)), (f"k div {s}", e2.sum(axis=1), n2.sum(axis=1))]
+    if not rank1 and case.opts["type"] != "fftconv":       # every index of every axis of the output, over the batch and the other axes
+        oshape = _out_shape(case.opts)
+        eN, wN = err2.reshape(lines, *reversed(oshape), per), w.reshape(lines, *reversed(oshape), per)
+        for a in range(len(oshape)):
+            others = tuple(d for d in range(eN.ndim) if d != len(oshape) - a)
+            groups.append((f"axis {a} idx", eN.sum(axis=others), wN.sum(axis=others)))
     worst, where = 0.0, "-"
     for name, e, n in groups:
         ok = n >= MIN_CLASS
@@ -500,9 +528,9 @@ def measure(oracle, case, route, got, want, keep):
             v = np.sqrt(e[ok] / n[ok] / ref_ms)
             i = int(np.argmax(v))
             if float(v[i]) > worst:
-                worst, where = float(v[i]), f"{name}={int(np.flatnonzero(ok)[i])}"
+                worst, where = float(v[i]), f"{name}{' ' if name.endswith('idx') else '='}{int(np.flatnonzero(ok)[i])}"
     Y = yardstick(oracle, case, route)
-    line = (f"accuracy {case.name}: route={route.strip()} rel_l2={rel:.3e} worst_class={worst:.3e} [{where}] Y={Y:.3e} "
+    line = (f"{prefix}accuracy {case.name}: route={route.strip()} rel_l2={rel:.3e} worst_class={worst:.3e} [{where}] Y={Y:.3e} "
             f"global={rel / Y:.2f} class={worst / Y:.2f}")
     print(line)
     assert rel <= GLOBAL_FACTOR * Y, line

@@ -33,6 +33,41 @@ def test_trig_reference_is_the_oracles_sum(oracle, typ, direction):
     assert np.all(np.abs(got - want) <= 2.0 ** -23 * np.abs(want) + 1e-10)
 
 
+@pytest.mark.parametrize("shape", [[6, 5], [8, 3, 4]])
+@pytest.mark.parametrize("typ", TRIG_TYPES)
+def test_nd_trig_reference_is_the_oracles(oracle, typ, shape):
+    """exact_trig of rank > 1 (trig1d_exact along every axis) against oracle.trig_ref_batch, which stores f32 after every axis: each of the
+    rank stores adds at most 2^-24 of the array's rms, amplified by no more than 2 by the later axes (the types I - III are no isometries)"""
+    for direction, normalize in (("forward", "unitary"), ("inverse", "backward")):
+        opts = t._o(typ, shape, 3, direction, normalize, layout=dict(t.REAL))
+        x = oracle.random_real_batch(int(np.prod(shape)), 3, 0x7B80 + len(shape)).reshape(-1)
+        want = oracle.trig_ref_batch(x, shape, 3, typ, direction, normalize).astype(np.float64)
+        got = acc.exact_trig(oracle, opts, x)
+        assert float(oracle.rel_l2(got, want)) <= 2 * len(shape) * 2.0 ** -24, (typ, shape, direction)
+
+
+@pytest.mark.parametrize("shape", [[6, 5], [8, 3, 4], [7, 4]])
+def test_nd_c2r_reference_is_the_oracles(oracle, shape):
+    """exact_c2r of rank > 1 against the oracle's full complex inverse (fftnd_ref) of the Hermitian extension of the same packed spectrum,
+    and the rank-general _in_spectrum against the signal it was made from.  Bars: the O(N^2) f32 oracle's own error (below 2^-20 at
+    these sizes); the f32 rounding of the spectrum (2^-24 a bin, a unitary map) for the round trip"""
+    batch, n, p = 2, int(np.prod(shape)), shape[0] // 2 + 1
+    opts = t._o("c2r", shape, batch, "inverse", "backward")
+    x, _ = acc._in_spectrum(0x7B90)(oracle, opts)
+    got = acc.exact_c2r(opts, x).reshape(batch, n)
+    sig = oracle.random_real_batch(n, batch, 0x7B90).astype(np.float64)
+    assert float(oracle.rel_l2(got * np.sqrt(n), sig)) <= 2.0 ** -23
+    spec = acc._cplx(x, batch, [p] + shape[1:])
+    mirror = spec[np.ix_(np.arange(batch), *((-np.arange(s)) % s for s in reversed(shape[1:])), np.arange(p))]      # X[k0, -k1, -k2]
+    full = np.zeros((batch, *reversed(shape)), np.complex128)
+    full[..., :p] = spec
+    for k0 in range(p, shape[0]):
+        full[..., k0] = np.conj(mirror[..., shape[0] - k0])
+    for b in range(batch):
+        ref = oracle.fftnd_ref(acc._inter(full[b]).astype(np.float32).reshape(-1), shape, "inverse", "backward", anysize=True).reshape(-1, 2)
+        assert float(oracle.rel_l2(got[b], ref[:, 0].astype(np.float64))) <= 2.0 ** -20, (shape, b)
+
+
 def test_view_and_fftconv_references_are_the_tables_oracles(oracle):
     """the float64 restatements of ioView / zeroPad and of fftconv (modes, boundaries, layouts) agree with the f32 oracles of
     exec_contract_cases.py on the same inputs, element for element, at the parity bar; the untouched elements are the same ones"""

@@ -2,7 +2,8 @@
 of the same f32 input.
 
 One case per test: the plan must take the route the table names, its output must be finite, and its error is held to 4 Y in rel_l2 and to
-8 Y over the worst class of outputs (every batch line; for long rank-1 lines the residues and blocks of the four-step split), Y being the
+8 Y over the worst class of outputs (every batch line; for long rank-1 lines the residues and blocks of the four-step split; for rank > 1
+every index of every axis), Y being the
 f32 oracle's own error against float64 measured in this process (accuracy_cases.py).  Output elements the plan's contract leaves alone
 start as NaN and are left out.  Every case prints one line: route, both values, Y, both ratios (profiles/accuracy_ladder.log)."""
 import numpy as np
