@@ -62,7 +62,14 @@ enum { MI355FFT_KERNEL_MAJOR = 0, MI355FFT_BATCH_MAJOR = 1 };
  * batchStrideElements}, layout.whdcn and fftConv.channelPolicy (runtime/layout_semantics.js:178-232,
  * runtime/plans/fftconv.js:213-281).  Units are ELEMENTS of the side's element type (complex for c2c,
  * real for the real side of r2c/c2r).  strided == 0 means dense: axis 0 fastest, batch outermost
- * (kernels/nd_line_base.js:9-12). */
+ * (kernels/nd_line_base.js:9-12).
+ *
+ * `reserved` of the INPUT side of an MI355FFT_FFTCONV / MI355FFT_FFTCONV_REAL plan carries fftConv.inputChannels C (0 or 1: no reduction).
+ * With C > 1 the input side is that of the same request with batch * C lines (line b * C + c is channel c of item b; dense
+ * [batch][C][shape]; batch_stride_elements is the step between consecutive LINES, there is no channel stride), the kernel buffer holds
+ * kernelCount * C packed kernels, kernel (k, c) at (k * C + c) * prod(kernelShape), and result (k, b) is sum_c x[b][c] (*) h[k][c]; the
+ * output side is unchanged.  zero_read applies to every channel, zero_write to the sum.  The word must be 0 on every other side and on
+ * every other plan type: the planner rejects a non-zero value there. */
 typedef struct mi355fft_side_layout {
   int32_t strided;
   int32_t reserved;

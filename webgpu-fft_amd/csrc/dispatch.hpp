@@ -250,6 +250,43 @@ MI355_TILE_WRAP_LAUNCHER(launch_tiles_rconv_ols_wrap, WRTileCfg)
 #endif
 #undef MI355_TILE_WRAP_LAUNCHER
 
+// the sum forms (fftConv.inputChannels > 1: fft_tiles_conv_ols_sum_kernel on STileCfg / SRTileCfg, routes tiles-conv-ols-sum / tiles-rconv-ols-sum; the spectrum launches stay on
+// the single-channel instances): the instances of MI355_TILE_SUM_KERNEL_LIST, each form in a unit of its own (tiles_conv_ols_sum.hip, tiles_rconv_ols_sum.hip).
+// `id`: position in that list (plan.cpp find_tile_kernel with `sum`)
+template <class L> bool launch_tiles_conv_ols_sum(int id, const TilesSumArgs& a, unsigned grid, L& l);
+template <class L> bool launch_tiles_rconv_ols_sum(int id, const TilesSumArgs& a, unsigned grid, L& l);
+inline TilesSumArgs tiles_sum_args_of(const Step& s, void* const ptr[STEP_PTRS]) { return TilesSumArgs{tiles_args_of(s, ptr), (int)s.i[LS_TILES_CHANNELS]}; }
+#define MI355_TILE_SUM_LAUNCHER(NAME)                                                                 \
+  template <class L> bool NAME(int id, const TilesSumArgs& a, unsigned grid, L& l) {                  \
+    int cur = 0;                                                                                      \
+    MI355_TILE_SUM_KERNEL_LIST(X)                                                                     \
+    (void)cur; (void)a; (void)grid; (void)l;                                                          \
+    return false;                                                                                     \
+  }
+#if defined(MI355_TILES_SUM_DEFINE_INSTANCES) || defined(MI355_HOST_EMU)
+#define X(P, R0, R1, TH)                                                                              \
+  if (id == cur) {                                                                                    \
+    using C = STileCfg<P, R0, R1, TH>;                                                                \
+    l.launch(fft_tiles_conv_ols_sum_kernel<C>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a); \
+    return true;                                                                                      \
+  }                                                                                                   \
+  ++cur;
+MI355_TILE_SUM_LAUNCHER(launch_tiles_conv_ols_sum)
+#undef X
+#endif
+#if defined(MI355_RTILES_SUM_DEFINE_INSTANCES) || defined(MI355_HOST_EMU)
+#define X(P, R0, R1, TH)                                                                              \
+  if (id == cur) {                                                                                    \
+    using C = SRTileCfg<P, R0, R1, TH>;                                                               \
+    l.launch(fft_tiles_conv_ols_sum_kernel<C>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a); \
+    return true;                                                                                      \
+  }                                                                                                   \
+  ++cur;
+MI355_TILE_SUM_LAUNCHER(launch_tiles_rconv_ols_sum)
+#undef X
+#endif
+#undef MI355_TILE_SUM_LAUNCHER
+
 // overlap-save on rank-3 bricks (kern_bricks.hpp fft_bricks_conv_ols_kernel, routes bricks-spectrum / bricks-conv-ols and, on an RBrickCfg, bricks-rspectrum /
 // bricks-rconv-ols): the instances of MI355_BRICK_KERNEL_LIST, each form in a unit of its own (bricks_conv_ols.hip, bricks_rconv_ols.hip).  `id`: position in
 // that list (plan.cpp find_brick_kernel)
@@ -628,6 +665,10 @@ bool dispatch_step(const Step& s, void* const ptr[STEP_PTRS], L& l, LinesFn&& li
         if (a.real_mode == LM_BRICKS_RCONV_OLS) return launch_bricks_rconv_ols_wrap(s.variant, bricks_args_of(s, ptr), s.grid, l);
         return false;
       }
+      if (s.i[LS_TILES_CHANNELS] > 1) {   // the sum over input channels (linear tiles only; the spectrum launches never carry the count)
+        if (a.real_mode == LM_TILES_CONV_OLS) return launch_tiles_conv_ols_sum(s.variant, tiles_sum_args_of(s, ptr), s.grid, l);
+        if (a.real_mode == LM_TILES_RCONV_OLS) return launch_tiles_rconv_ols_sum(s.variant, tiles_sum_args_of(s, ptr), s.grid, l);
+      }
       if (a.real_mode == LM_TILES_CONV_OLS || a.real_mode == LM_TILES_SPECTRUM) return launch_tiles_conv_ols(s.variant, tiles_args_of(s, ptr), s.grid, l);   // rank-2 overlap-save tiles
       if (a.real_mode == LM_TILES_RCONV_OLS || a.real_mode == LM_TILES_RSPECTRUM) return launch_tiles_rconv_ols(s.variant, tiles_args_of(s, ptr), s.grid, l);   // and on real tile pairs
       if (a.real_mode == LM_BRICKS_CONV_OLS || a.real_mode == LM_BRICKS_SPECTRUM) return launch_bricks_conv_ols(s.variant, bricks_args_of(s, ptr), s.grid, l);   // rank-3 overlap-save bricks
@@ -704,6 +745,11 @@ bool dispatch_step(const Step& s, void* const ptr[STEP_PTRS], L& l, LinesFn&& li
                (long long)s.i[PH_BATCH], (long long)s.i[PH_PACKED_STRIDE]);
       return true;
     case ST_POINTWISE:
+      if (s.i[PW_CHANNELS] > 1) {    // fftConv.inputChannels: the product summed over the input channels
+        l.launch(pointwise_sum_kernel, s.grid, 256u, 0u, (const cf*)ptr[P_SRC], (cf*)ptr[P_DST], (const cf*)ptr[PWP_KERNEL], (long long)s.i[PW_L], (long long)s.i[PW_TOTAL],
+                 (int)s.i[PW_CHANNELS], (int)s.i[PW_CONJ], s.f[F_SCALE]);
+        return true;
+      }
       l.launch(pointwise_mul_kernel, s.grid, 256u, 0u, (const cf*)ptr[P_SRC], (cf*)ptr[P_DST], (const cf*)ptr[PWP_KERNEL], (long long)s.i[PW_L], (long long)s.i[PW_TOTAL],
                (int)s.i[PW_CONJ], s.f[F_SCALE]);
       return true;

@@ -363,6 +363,23 @@ static __global__ void __launch_bounds__(256) pointwise_mul_kernel(const cf* dat
   }
 }
 
+// out[b][i] = sum_c data[b C + c][i] * (conj?) kern[c][i]   — the product of fftconv with fftConv.inputChannels = C > 1 (routes fftconv-sum, rconv-sum): the
+// reduction over the input channels in the frequency domain, where it is pointwise.  `total` = batch * L output points, `kern` the C spectra of one output
+// kernel.  A thread owns a point: it reads each of the point's C data elements once and keeps the running sum in registers (8 C B read, 8 B written a point)
+static __global__ void __launch_bounds__(256) pointwise_sum_kernel(const cf* data, cf* out, const cf* kern, long long L, long long total, int channels, int conj_kernel, float s) {
+  for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (long long)gridDim.x * blockDim.x) {
+    const long long b = g / L, i = g - b * L;
+    const cf* d = data + b * channels * L + i;
+    const cf* k = kern + i;
+    cf acc = {0.0f, 0.0f};
+    for (int c = 0; c < channels; ++c) {
+      const cf dv = d[(long long)c * L], kv = k[(long long)c * L];
+      acc += conj_kernel ? cmul_conj(dv, kv) : cmul(dv, kv);
+    }
+    out[g] = acc * s;
+  }
+}
+
 // Strided physical <-> dense logical, rank <= 8 (strided_complex.js:22-106).  Logical index is axis-0
 // fastest within a batch entry; physical element = offset + b*batch_stride + sum coord_d*stride_d.
 // `sub` selects a window of the dense side: dense coords = coord + sub_offset inside dense_shape

@@ -155,109 +155,9 @@ __global__ void __launch_bounds__(C::THREADS, C::WAVES_PER_SIMD) fft_tiles_conv_
     const unsigned sb = (unsigned)tile / per_image, r = (unsigned)tile - sb * per_image, j1 = r / (unsigned)A0.nb, j0 = r - j1 * (unsigned)A0.nb;
     const int s00 = (int)j0 * A0.L - A0.pre, s01 = (int)(REAL ? 2u * j1 : j1) * A1.L - A1.pre;      // the tile's first signal index on each axis (REAL: partner a's)
     cf v[C::E];
-    // ---- forward, columns: stage 0 from global memory (this lane: column i0 = line) ----
-    if constexpr (C::WRAP) {
-      // circular: signal index (s0_a + i_a) mod fN_a on both axes; fN_a >= 2 P, so one conditional add (the head of a convolution's first tile) and one
-      // conditional subtract (past the seam) wrap it.  Axis 0 is the lane's: its wrapped column once per tile.  On axis 1 the head's wrap moves the tile's
-      // origin, the same for every lane; past the seam the index falls back by fN_1.  The map's bounds apply to the wrapped indices, the only ones that
-      // are dereferenced.  REAL: the two partners wrap independently; an absent partner b (odd nb_1) loads nothing, under a predicate every lane shares
-      const int N0 = A0.fN, N1 = A1.fN, p0 = s00 + line, h0 = p0 < 0 ? p0 + N0 : p0, q0 = h0 >= N0 ? h0 - N0 : h0;
-      const bool ok0 = q0 >= im.lo[0] && q0 < im.hi[0];
-      const long long base = im.offset + (long long)sb * im.batch_stride + (long long)q0 * im.stride[0];
-      const int lo1 = im.lo[1], hi1 = im.hi[1], s01w = s01 < 0 ? s01 + N1 : s01;
-      const long long s1 = im.stride[1];
-      int ul = u;
-      if constexpr (C::REFORM_POSITIONS) MI_TILE_OPAQUE_LANE(ul);
-      if constexpr (REAL) {
-        const float* x = reinterpret_cast<const float*>(a.in) + base;
-        const int s01b = s01 + A1.L, s01bw = s01b < 0 ? s01b + N1 : (s01b >= N1 ? s01b - N1 : s01b);
-        const bool okb = ok0 && 2u * j1 + 1u < (unsigned)A1.nb;
-#pragma unroll
-        for (int b = 0; b < I0::NB; ++b) {
-#pragma unroll
-          for (int q = 0; q < I0::R; ++q) {
-            const int i1 = ul + b * C::TPL + q * (C::P / I0::R);
-            const int ta = s01w + i1, qa = ta >= N1 ? ta - N1 : ta, tb = s01bw + i1, qb = tb >= N1 ? tb - N1 : tb;
-            cf xv = {0.0f, 0.0f};
-            if (ok0 && qa >= lo1 && qa < hi1) xv.x = x[(long long)qa * s1];
-            if (okb && qb >= lo1 && qb < hi1) xv.y = x[(long long)qb * s1];
-            v[b * I0::R + q] = xv;
-          }
-        }
-      } else {
-        const cf* x = a.in + base;
-#pragma unroll
-        for (int b = 0; b < I0::NB; ++b) {
-#pragma unroll
-          for (int q = 0; q < I0::R; ++q) {
-            const int t1 = s01w + ul + b * C::TPL + q * (C::P / I0::R), q1 = t1 >= N1 ? t1 - N1 : t1;
-            cf xv = {0.0f, 0.0f};
-            if (ok0 && q1 >= lo1 && q1 < hi1) xv = x[(long long)q1 * s1];
-            v[b * I0::R + q] = xv;
-          }
-        }
-      }
-    } else if constexpr (REAL) {
-      const int q0 = s00 + line;
-      const bool ok0 = q0 >= im.lo[0] && q0 < im.hi[0];
-      const float* x = reinterpret_cast<const float*>(a.in) + (im.offset + (long long)sb * im.batch_stride + (long long)q0 * im.stride[0]);   // (dereferenced inside [lo, hi) only)
-      const int s01b = s01 + A1.L;                                                 // partner b: the next tile on axis 1
-      const int l1 = im.lo[1] - s01, h1 = im.hi[1] - s01, l1b = im.lo[1] - s01b, h1b = im.hi[1] - s01b;
-      const int lo1 = l1 < 0 ? 0 : l1, hi1 = h1 > C::P ? C::P : h1;               // each partner's share of [lo, hi) on axis 1
-      const int lo1b = l1b < 0 ? 0 : l1b, hi1b = h1b > C::P ? C::P : h1b;
-      const long long s1 = im.stride[1];
-      int ul = u;
-      if constexpr (C::REFORM_POSITIONS) MI_TILE_OPAQUE_LANE(ul);
-#pragma unroll
-      for (int b = 0; b < I0::NB; ++b) {
-#pragma unroll
-        for (int q = 0; q < I0::R; ++q) {
-          const int i1 = ul + b * C::TPL + q * (C::P / I0::R);
-          cf xv = {0.0f, 0.0f};
-          if (ok0 && i1 >= lo1 && i1 < hi1) xv.x = x[(long long)(s01 + i1) * s1];
-          if (ok0 && i1 >= lo1b && i1 < hi1b) xv.y = x[(long long)(s01b + i1) * s1];
-          v[b * I0::R + q] = xv;
-        }
-      }
-    } else {
-      const int q0 = s00 + line;
-      const bool ok0 = q0 >= im.lo[0] && q0 < im.hi[0];
-      const cf* x = a.in + (im.offset + (long long)sb * im.batch_stride + (long long)q0 * im.stride[0]);   // (dereferenced inside [lo, hi) only)
-      const int l1 = im.lo[1] - s01, h1 = im.hi[1] - s01;
-      const int lo1 = l1 < 0 ? 0 : l1, hi1 = h1 > C::P ? C::P : h1;               // the tile's share of [lo, hi) on axis 1
-      const long long s1 = im.stride[1];
-      int ul = u;
-      if constexpr (C::REFORM_POSITIONS) MI_TILE_OPAQUE_LANE(ul);
-#pragma unroll
-      for (int b = 0; b < I0::NB; ++b) {
-#pragma unroll
-        for (int q = 0; q < I0::R; ++q) {
-          const int i1 = ul + b * C::TPL + q * (C::P / I0::R);
-          cf xv = {0.0f, 0.0f};
-          if (ok0 && i1 >= lo1 && i1 < hi1) xv = x[(long long)(s01 + i1) * s1];
-          v[b * I0::R + q] = xv;
-        }
-      }
-    }
-    tile_stage_compute<C, 0>(v, tw_lds, u);
-    tile_stage_write<C, 0, true>(v, lds, line, u);
-    __syncthreads();
-    tile_stage_read<C, 1, true>(v, lds, line, u);
-    __syncthreads();
-    tile_stage_compute<C, 1>(v, tw_lds, u);
-    tile_stage_write<C, 1, true>(v, lds, line, u);
-    __syncthreads();
-    // ---- forward, rows (this lane: row i1 = line) ----
-    tile_stage_read<C, 0, false>(v, lds, line, u);
-    __syncthreads();
-    tile_stage_compute<C, 0>(v, tw_lds, u);
-    tile_stage_write<C, 0, false>(v, lds, line, u);
-    __syncthreads();
-    tile_stage_read<C, 1, false>(v, lds, line, u);
-    __syncthreads();
-    tile_stage_compute<C, 1>(v, tw_lds, u);
-    tile_stage_write<C, 1, false>(v, lds, line, u);
-    __syncthreads();
+#define MI_TILE_IN_LINE (long long)sb
+#include "kern_tiles_forward.inc"
+#undef MI_TILE_IN_LINE
     if (a.spectrum_only) {      // the spectrum as the product reads it: bin (k0, k1 = line) at [k0 * P + k1]
       cf* g = a.out + (long long)sb * (C::P * C::P);
       for (int k0 = u; k0 < C::P; k0 += C::TPL) g[k0 * C::P + line] = lds[tile_index<C, false>(line, k0)];
@@ -276,78 +176,7 @@ __global__ void __launch_bounds__(C::THREADS, C::WAVES_PER_SIMD) fft_tiles_conv_
       }
     }
     __syncthreads();
-    tile_stage_compute<C, 0>(v, tw_lds, u);
-    tile_stage_write<C, 0, false>(v, lds, line, u);
-    __syncthreads();
-    tile_stage_read<C, 1, false>(v, lds, line, u);
-    __syncthreads();
-    tile_stage_compute<C, 1>(v, tw_lds, u);
-    tile_stage_write<C, 1, false>(v, lds, line, u);
-    __syncthreads();
-    // ---- inverse, columns: the last stage stores to global memory ----
-    tile_stage_read<C, 0, true>(v, lds, line, u);
-    __syncthreads();
-    tile_stage_compute<C, 0>(v, tw_lds, u);
-    tile_stage_write<C, 0, true>(v, lds, line, u);
-    __syncthreads();
-    tile_stage_read<C, 1, true>(v, lds, line, u);
-    __syncthreads();            // everyone has its inputs: LDS is free for the next tile
-    tile_stage_compute<C, 1>(v, tw_lds, u);
-    if constexpr (REAL) {
-      const int q0 = s00 + line;
-      const int m0 = q0 < 0 ? q0 + A0.fN : q0;                                   // (the negative lags of a correlation sit at the top of the domain)
-      const bool ok0 = line >= A0.w0 && line < A0.w0 + A0.L && q0 < A0.plim && m0 >= om.lo[0] && m0 < om.hi[0];
-      const bool z0 = m0 < om.zlo[0] || m0 >= om.zhi[0];
-      float* y = reinterpret_cast<float*>(a.out) + (om.offset + (long long)sb * om.batch_stride + (long long)m0 * om.stride[0]);   // (dereferenced inside the crop only)
-      const long long s1 = om.stride[1];
-      const int s01b = s01 + A1.L;
-      int wlo = A1.w0, us = u;
-      MI_TILE_OPAQUE(wlo);
-      if constexpr (C::REFORM_POSITIONS) MI_TILE_OPAQUE_LANE(us);
-      const int wend = A1.w0 + A1.L, pend = A1.plim - s01, whi = wend < pend ? wend : pend;   // each partner's window, cut at the last index the signal gives;
-      const int pendb = A1.plim - s01b, whib = wend < pendb ? wend : pendb;                    // an absent partner's is empty: s0_1(b) + w0_1 >= plim_1 in both modes
-#pragma unroll
-      for (int b = 0; b < I1::NB; ++b) {
-#pragma unroll
-        for (int q = 0; q < I1::R; ++q) {
-          const int i1 = tile_stage_out<C, 1>(us, b, q);
-          if (!ok0 || i1 < wlo) continue;
-          const cf r = cswap(v[b * I1::R + q]) * a.scale;
-          if (i1 < whi) {
-            const int q1 = s01 + i1, m1 = q1 < 0 ? q1 + A1.fN : q1;
-            if (m1 >= om.lo[1] && m1 < om.hi[1]) y[(long long)m1 * s1] = (z0 || m1 < om.zlo[1] || m1 >= om.zhi[1]) ? 0.0f : r.x;
-          }
-          if (i1 < whib) {
-            const int q1 = s01b + i1, m1 = q1 < 0 ? q1 + A1.fN : q1;
-            if (m1 >= om.lo[1] && m1 < om.hi[1]) y[(long long)m1 * s1] = (z0 || m1 < om.zlo[1] || m1 >= om.zhi[1]) ? 0.0f : r.y;
-          }
-        }
-      }
-    } else {
-      const int q0 = s00 + line;
-      const int m0 = q0 < 0 ? q0 + A0.fN : q0;                                   // (the negative lags of a correlation sit at the top of the domain)
-      const bool ok0 = line >= A0.w0 && line < A0.w0 + A0.L && q0 < A0.plim && m0 >= om.lo[0] && m0 < om.hi[0];
-      const bool z0 = m0 < om.zlo[0] || m0 >= om.zhi[0];
-      cf* y = a.out + (om.offset + (long long)sb * om.batch_stride + (long long)m0 * om.stride[0]);   // (dereferenced inside the crop only)
-      const long long s1 = om.stride[1];
-      int wlo = A1.w0, us = u;
-      MI_TILE_OPAQUE(wlo);
-      if constexpr (C::REFORM_POSITIONS) MI_TILE_OPAQUE_LANE(us);
-      const int wend = A1.w0 + A1.L, pend = A1.plim - s01, whi = wend < pend ? wend : pend;   // the window, cut at the last index the signal gives
-#pragma unroll
-      for (int b = 0; b < I1::NB; ++b) {
-#pragma unroll
-        for (int q = 0; q < I1::R; ++q) {
-          const int i1 = tile_stage_out<C, 1>(us, b, q), q1 = s01 + i1;
-          if (!ok0 || i1 < wlo || i1 >= whi) continue;
-          const int m1 = q1 < 0 ? q1 + A1.fN : q1;
-          if (m1 < om.lo[1] || m1 >= om.hi[1]) continue;
-          cf r = cswap(v[b * I1::R + q]) * a.scale;
-          if (z0 || m1 < om.zlo[1] || m1 >= om.zhi[1]) r = cf{0.0f, 0.0f};
-          y[(long long)m1 * s1] = r;
-        }
-      }
-    }
+#include "kern_tiles_inverse.inc"
   }
 }
 
@@ -356,5 +185,70 @@ template <int P_, int R0_, int R1_, int THREADS_> struct RTileCfg : TileCfg<P_, 
 // the circular forms of both (routes tiles-conv-ols[..,wrap], tiles-rconv-ols[..,wrap]): units of their own again (tiles_conv_ols_wrap.hip, tiles_rconv_ols_wrap.hip)
 template <int P_, int R0_, int R1_, int THREADS_> struct WTileCfg : TileCfg<P_, R0_, R1_, THREADS_> { static constexpr bool WRAP = true; };
 template <int P_, int R0_, int R1_, int THREADS_> struct WRTileCfg : RTileCfg<P_, R0_, R1_, THREADS_> { static constexpr bool WRAP = true; };
+
+// ---- the sum over input channels (fftConv.inputChannels = C > 1; routes tiles-conv-ols-sum, tiles-rconv-ols-sum): y[b][k] = sum_c x[b][c] (*) h[k][c], the sum
+// taken in the frequency domain of the tile.  A work item loops over c: channel c's tile from input line sb C + c (the origin, the windows and the lane's
+// positions do not depend on c), the forward passes, then acc += spectrum of the tile * H[c] in the registers the inverse's first stage starts from; after the loop
+// ONE inverse and ONE store.  Per tile position and output kernel: C tile reads and forward transforms, as C single-channel launches would take, but one inverse
+// transform and one tile-window write instead of C, and no partial results to add.  `spectrum` holds the C spectra of the launch's output kernel, channel c at
+// c P^2 (LM_TILES_SPECTRUM on K C kernels stores that order).  Real pairs need nothing new: sum_c IFFT(FFT(a_c + i b_c) H_c) keeps tile a's sum in the real parts
+// and tile b's in the imaginary parts, and an absent partner stays absent in every channel.  The load, the forward passes, the inverse and the store are the
+// single-channel kernel's text (the two .inc files).  Linear boundaries only.
+// The accumulators are E more complex values a thread: the configurations re-form the lane's positions in every tile (REFORM_POSITIONS, as P = 128 does) and
+// then hold 128 VGPRs without scratch at P = 64, four workgroups a CU as before (profiles/fftconv_sum_resource_usage.log).
+// The existing kernels take TilesArgs by value, so the channel count travels in a wrapper (as RconvOlsArgs wraps LineArgs)
+struct TilesSumArgs { TilesArgs a; int channels; };
+template <int P_, int R0_, int R1_, int THREADS_> struct STileCfg : TileCfg<P_, R0_, R1_, THREADS_> { static constexpr bool CSUM = true, REFORM_POSITIONS = true; };
+template <int P_, int R0_, int R1_, int THREADS_> struct SRTileCfg : RTileCfg<P_, R0_, R1_, THREADS_> { static constexpr bool CSUM = true, REFORM_POSITIONS = true; };
+
+template <class C>
+__global__ void __launch_bounds__(C::THREADS, C::WAVES_PER_SIMD) fft_tiles_conv_ols_sum_kernel(const TilesSumArgs sa) {
+  static_assert(C::CSUM && !C::WRAP, "the sum configurations: linear boundaries");
+  constexpr bool REAL = C::REAL;
+  const TilesArgs& a = sa.a;
+  const int channels = sa.channels;
+  MI_SMEM_DECL(smem);
+  cf* lds = reinterpret_cast<cf*>(smem);
+  cf* tw_lds = lds + C::DATA_ELEMS;
+  const int t = threadIdx.x;
+  for (int i = t; i < C::TW_ELEMS; i += C::THREADS) tw_lds[i] = a.tw[i];
+  __syncthreads();
+  const int line = t % C::P, u = t / C::P;
+  using I0 = TileStage<C, 0>;
+  using I1 = TileStage<C, 1>;
+  const SideMap& im = a.imap;
+  const SideMap& om = a.omap;
+  const TileAxis& A0 = a.ax[0];
+  const TileAxis& A1 = a.ax[1];
+  const unsigned per_image = (unsigned)A0.nb * (REAL ? ((unsigned)A1.nb + 1u) / 2u : (unsigned)A1.nb);
+  for (long long tile = blockIdx.x; tile < a.num_tiles; tile += gridDim.x) {
+    const unsigned sb = (unsigned)tile / per_image, r = (unsigned)tile - sb * per_image, j1 = r / (unsigned)A0.nb, j0 = r - j1 * (unsigned)A0.nb;
+    const int s00 = (int)j0 * A0.L - A0.pre, s01 = (int)(REAL ? 2u * j1 : j1) * A1.L - A1.pre;
+    cf v[C::E], acc[C::E];
+#pragma unroll
+    for (int i = 0; i < C::E; ++i) acc[i] = cf{0.0f, 0.0f};
+    for (int c = 0; c < channels; ++c) {
+#define MI_TILE_IN_LINE ((long long)sb * channels + c)
+#include "kern_tiles_forward.inc"
+#undef MI_TILE_IN_LINE
+      // the bins the inverse's first stage starts from, times channel c's spectrum (conjugated when correlating), into the running sums
+      const cf* hs = a.spectrum + (long long)c * (C::P * C::P);
+#pragma unroll
+      for (int b = 0; b < I0::NB; ++b) {
+#pragma unroll
+        for (int q = 0; q < I0::R; ++q) {
+          const int k0 = u + b * C::TPL + q * (C::P / I0::R);
+          cf h = hs[k0 * C::P + line];
+          if (a.conj) h.y = -h.y;
+          acc[b * I0::R + q] += cmul(lds[tile_index<C, false>(line, k0)], h);
+        }
+      }
+      __syncthreads();          // LDS is re-used by the next channel, and then by the inverse
+    }
+#pragma unroll
+    for (int i = 0; i < C::E; ++i) v[i] = cswap(acc[i]);
+#include "kern_tiles_inverse.inc"
+  }
+}
 
 }  // namespace mi355

@@ -87,18 +87,22 @@ const std::vector<ConvKernelMeta>& conv_kernel_registry() {
   return reg;
 }
 
-const TileKernelMeta* find_tile_kernel(int P, bool real) {
+const TileKernelMeta* find_tile_kernel(int P, bool real, bool sum) {
   static const std::vector<TileKernelMeta> reg = [] {
     std::vector<TileKernelMeta> r;
     for (int real = 0; real < 2; ++real) {   // both forms instantiate the whole list: an id is the position in it
       int id = 0;
-#define X(P, R0, R1, TH) r.push_back(TileKernelMeta{id++, P, R0, R1, TH, tile_kernel_lds_bytes(P, R0, R1), real != 0});
+#define X(P, R0, R1, TH) r.push_back(TileKernelMeta{id++, P, R0, R1, TH, tile_kernel_lds_bytes(P, R0, R1), real != 0, false});
       MI355_TILE_KERNEL_LIST(X)
+#undef X
+      id = 0;                                // the sum forms: ids of their own list
+#define X(P, R0, R1, TH) r.push_back(TileKernelMeta{id++, P, R0, R1, TH, tile_kernel_lds_bytes(P, R0, R1), real != 0, true});
+      MI355_TILE_SUM_KERNEL_LIST(X)
 #undef X
     }
     return r;
   }();
-  for (const auto& m : reg) if (m.P == P && m.real == real) return &m;
+  for (const auto& m : reg) if (m.P == P && m.real == real && m.sum == sum) return &m;
   return nullptr;
 }
 
@@ -191,6 +195,7 @@ PlannerOptions planner_options_from_env() {
   if (const char* s = std::getenv("MI355FFT_CONV_OLS")) o.conv_ols = std::atoi(s);
   if (const char* s = std::getenv("MI355FFT_CONV_OLS2D")) o.conv_ols2d = std::atoi(s);
   if (const char* s = std::getenv("MI355FFT_RCONV_OLS2D")) o.rconv_ols2d = std::atoi(s);
+  if (const char* s = std::getenv("MI355FFT_SUM_OLS2D")) o.sum_ols2d = std::atoi(s);
   if (const char* s = std::getenv("MI355FFT_CONV_OLS3D")) o.conv_ols3d = std::atoi(s);
   if (const char* s = std::getenv("MI355FFT_RCONV_OLS3D")) o.rconv_ols3d = std::atoi(s);
   if (const char* s = std::getenv("MI355FFT_OLS_CIRCULAR")) o.ols_circular = std::atoi(s);
@@ -1134,6 +1139,12 @@ int validate_common(const mi355fft_plan_desc& d, std::string& err) {
     if (l->strided)
       for (int i = 0; i < d.rank; ++i)
         if (l->strides[i] <= 0) { err = "layout strides must be positive ints"; return MI355FFT_ERR_INVALID; }
+  // mi355fft_side_layout.reserved: fftConv.inputChannels on the input side of the two fftconv types, zero everywhere else
+  const bool conv = d.type == MI355FFT_FFTCONV || d.type == MI355FFT_FFTCONV_REAL;
+  if (d.output.reserved != 0 || (!conv && d.input.reserved != 0)) {
+    err = "mi355fft_side_layout.reserved must be 0 (it carries fftConv.inputChannels on the input side of fftconv plans only)"; return MI355FFT_ERR_INVALID;
+  }
+  if (conv && d.input.reserved < 0) { err = "fftConv.inputChannels must be a positive integer; got " + std::to_string(d.input.reserved); return MI355FFT_ERR_INVALID; }
   return MI355FFT_OK;
 }
 
@@ -1629,6 +1640,7 @@ int build_trig(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
 struct ConvGeom {
   int rank;
   int64_t K, B;
+  int64_t C = 1;                          // fftConv.inputChannels: B * C data lines and K * C kernels, result (k, b) summed over c
   bool linear, corr;
   int64_t ks[8], fs[8], os[8], ooff[8];   // kernel shape, FFT domain (axis 0 as padded), output shape, crop offset on the logical domain
   int64_t inN, kN, oN, lfN;               // elements of a data item, a kernel and an output item; logical axis-0 length of the FFT domain
@@ -1655,7 +1667,8 @@ int conv_geometry(const mi355fft_plan_desc& d, int64_t elem, ConvGeom& g, PlanIR
   if (d.conv_boundary < 0 || d.conv_boundary > 3) { err = "fftConv.boundary must be one of \"circular\", \"linear-full\", \"linear-same\", \"linear-valid\""; return MI355FFT_ERR_INVALID; }
   if (d.conv_kernel_count <= 0) { err = "fftConv.kernelCount must be a positive integer; got " + std::to_string(d.conv_kernel_count); return MI355FFT_ERR_INVALID; }
   const int rank = g.rank = d.rank;
-  const int64_t K = g.K = d.conv_kernel_count, B = g.B = d.batch;
+  const int64_t K = g.K = d.conv_kernel_count, B = g.B = d.batch, C = g.C = std::max<int64_t>(1, d.input.reserved);
+  if (C > 1 && prodv(d.shape, rank) * B * C > ((int64_t)1 << 40)) { err = "Unsupported: more than 2^40 points in one plan"; return MI355FFT_ERR_UNSUPPORTED; }
   g.linear = d.conv_boundary != MI355FFT_CIRCULAR;
   g.corr = d.conv_mode == MI355FFT_CORRELATION;
   bool ks_given = false;
@@ -1685,8 +1698,8 @@ int conv_geometry(const mi355fft_plan_desc& d, int64_t elem, ConvGeom& g, PlanIR
   const int64_t inN = g.inN = prodv(d.shape, rank), kN = g.kN = prodv(g.ks, rank), oN = g.oN = prodv(g.os, rank);
   const int64_t kstride = d.conv_output_kernel_stride_elements;
   if (d.output.strided && K > 1 && kstride <= 0) { err = "multi-kernel strided output requires fftConv.channelPolicy.output or fftConv.outputKernelStrideElements"; return MI355FFT_ERR_INVALID; }
-  ir.kernel_bytes = (uint64_t)K * kN * elem;
-  ir.in_bytes = d.input.strided ? strided_extent_elems(d.input, d.shape, rank, B, 0) * elem : (uint64_t)inN * B * elem;
+  ir.kernel_bytes = (uint64_t)K * C * kN * elem;
+  ir.in_bytes = d.input.strided ? strided_extent_elems(d.input, d.shape, rank, B * C, 0) * elem : (uint64_t)inN * B * C * elem;
   ir.out_bytes = d.output.strided ? strided_extent_elems(d.output, g.os, rank, B, (K - 1) * kstride) * elem : (uint64_t)K * B * oN * elem;
   const bool kmajor = d.conv_output_layout == MI355FFT_KERNEL_MAJOR;
   g.lane0 = d.output.strided ? d.output.offset_elements : 0;
@@ -1811,6 +1824,16 @@ int64_t conv_tiles_block(int64_t fN0, int64_t fN1, int64_t M0, int64_t M1) {
 // 113-118): the complex route's boundary.  Kernels of 18 .. 32 points were not measured: they take the larger tile, as there
 int64_t rconv_tiles_block(int64_t fN0, int64_t fN1, int64_t M0, int64_t M1) { return conv_tiles_block(fN0, fN1, M0, M1); }
 
+// The tile edge the default rule (PlannerOptions::sum_ols2d == 1) gives to the sum form of the tile routes (fftConv.inputChannels > 1, complex and real): conv_tiles_block's
+// bounds on the domain, and the one sum instance there is, P = 64, for the kernels conv_tiles_block gives that tile (up to 17 points an axis).  Kernels of 18 .. 33
+// points take the composed routes fftconv-sum / rconv-sum: a P = 128 sum instance does not exist (MI355_TILE_SUM_KERNEL_LIST)
+// Measured (profiles/fftconv_sum_ab.log: 8 x 1024^2 (*) 9x9, 4 x 512^2 (*) 5x5 and 3 x 1920x1080 (*) 17x17 linear-same, complex and real, C = 3 / 16 / 64, K = 1 / 4, the three
+// forms timed alternately in one process; spread between a form's two medians <= 1.4 %): the tile-sum route is 10.0-38.7x (complex) and 5.9-36.0x (real) ahead of the composed
+// sum route (MI355FFT_SUM_OLS2D=0: Bluestein / mixed-radix transforms of batch * C whole images) on every request, so no class inside the instance's bounds is
+// excluded; against C single-channel tile plans run back to back WITHOUT their sum it is 1.50-1.85x at C = 3, 1.85-3.18x at C = 16 and 1.90-3.37x at C = 64 ahead
+// (98-297 / 100-534 G complex / real input points/s)
+int64_t sum_tiles_block(int64_t fN0, int64_t fN1, int64_t M0, int64_t M1) { return conv_tiles_block(fN0, fN1, M0, M1) == 64 ? 64 : 0; }
+
 // The brick edge the default rule (PlannerOptions::conv_ols3d == 1) gives to overlap-save on a rank-3 volume of fN0 x fN1 x fN2 = shape + M - 1 logical points
 // and a kernel of M0 x M1 x M2 points; 0: the request keeps its earlier route.  Left alone: domains of at most 32768 points and axes below 32 points (the
 // small requests whose routes the tests pin; a brick would be mostly padding) and kernels beyond 9 points on an axis (a brick returns less than 1/8 of its
@@ -1923,22 +1946,30 @@ bool emit_tiles_ols(Builder& b, const mi355fft_plan_desc& d, const ConvGeom& g, 
   if (fs[0] >= lim || fs[1] >= lim) return false;
   const int64_t sw = real ? b.opt.rconv_ols2d : b.opt.conv_ols2d, rule = real ? rconv_tiles_block(fs[0], fs[1], ks[0], ks[1]) : conv_tiles_block(fs[0], fs[1], ks[0], ks[1]);
   const bool wrap = !g.linear;                                              // (circular: the rule's tile alone, a forced tile moves linear requests only)
-  const int64_t P = wrap ? (ols_circular_take(b.opt, d.shape, 2, rule) ? rule : 0) : ols_switch(sw, sw == 64 || sw == 128, rule);
-  const TileKernelMeta* tm = P ? find_tile_kernel((int)P, real) : nullptr;
+  // fftConv.inputChannels C > 1: the kernel's sum form.  A work item loops over c: channel c's tile from input line sb C + c (the load map's batch stride is the
+  // line stride), forward, accumulate times spectrum (k, c); one inverse and one store a tile.  K C spectra in the workspace, launch k reads those from k C on.
+  // Linear boundaries only; its own switch (PlannerOptions::sum_ols2d, rule sum_tiles_block) behind the route's
+  const int64_t C = g.C, ssw = b.opt.sum_ols2d;
+  const bool sum = C > 1;
+  if (sum && (wrap || ssw == 0)) return false;
+  const int64_t P = sum ? ols_switch(ssw, ssw == 64 || ssw == 128, sum_tiles_block(fs[0], fs[1], ks[0], ks[1]))
+                        : wrap ? (ols_circular_take(b.opt, d.shape, 2, rule) ? rule : 0) : ols_switch(sw, sw == 64 || sw == 128, rule);
+  const TileKernelMeta* tm = P ? find_tile_kernel((int)P, real, sum) : nullptr;
+  const TileKernelMeta* sm = sum && tm ? find_tile_kernel((int)P, real) : tm;    // the spectrum launch stays on the single-channel instance
   const OlsAxis ax[2] = {ols_axis(fs[0], d.shape[0], ks[0], P, g.corr, false, wrap), ols_axis(fs[1], d.shape[1], ks[1], P, g.corr, false, wrap)};
   const int64_t items = g.B * ax[0].nb * (real ? (ax[1].nb + 1) / 2 : ax[1].nb);
-  if (!tm || ax[0].L < 2 || ax[1].L < 2 || ax[0].nb * ax[1].nb >= lim || items >= lim) return false;
+  if (!tm || !sm || ax[0].L < 2 || ax[1].L < 2 || ax[0].nb * ax[1].nb >= lim || items >= lim || g.B * C >= lim || g.K * C >= lim) return false;
   const int64_t pd[2] = {P, P};
-  const PtrRef G = b.alloc_work((uint64_t)g.K * P * P * 8);
+  const PtrRef G = b.alloc_work((uint64_t)g.K * C * P * P * 8);
   std::vector<float2h> roots;
   for (int q = 1; q < tm->R1; ++q) for (int k = 0; k < tm->R0; ++k) roots.push_back(root_of_unity((int64_t)q * k, P));
   const PtrRef tables = b.add_table(roots);
   int64_t per_cu = std::min<int64_t>((160 * 1024) / tm->lds_bytes, 2048 / tm->threads);
   per_cu = std::max<int64_t>(per_cu, 1);
-  const auto launch = [&](LineMode mode, PtrRef src, PtrRef dst, int64_t count) {
+  const auto launch = [&](const TileKernelMeta* km, LineMode mode, PtrRef src, PtrRef dst, int64_t count) {
     Step st;
     st.kind = ST_LINES;
-    st.variant = tm->id;
+    st.variant = km->id;
     st.p[LP_IN] = src; st.p[LP_OUT] = dst; st.p[LP_TW] = tables;
     st.i[LS_TILES] = count; st.i[LS_LINES] = count; st.i[LS_IN_S] = 1; st.i[LS_IN_OUTER] = P; st.i[LS_OUT_S] = 1; st.i[LS_OUT_OUTER] = P;
     st.i[LS_MODE] = mode; st.i[LS_MAPPED] = 1;
@@ -1946,20 +1977,21 @@ bool emit_tiles_ols(Builder& b, const mi355fft_plan_desc& d, const ConvGeom& g, 
     return st;
   };
   const std::string tile = "[N=" + std::to_string(P) + "x" + std::to_string(P);
-  Step sp = launch(real ? LM_TILES_RSPECTRUM : LM_TILES_SPECTRUM, PtrRef(BUF_KERNEL, 0), G, g.K);
+  Step sp = launch(sm, real ? LM_TILES_RSPECTRUM : LM_TILES_SPECTRUM, PtrRef(BUF_KERNEL, 0), G, g.K * C);
   OlsAxis whole;
   whole.fN = whole.plim = whole.L = P; whole.nb = 1;
   ols_store(sp.i, whole, whole);
   sp.imap = conv_kernel_map(g, pd, 2); sp.omap = Builder::dense_map(pd, 2);
   b.ir.steps.push_back(sp);
   b.ir.route += (real ? "tiles-rspectrum" : "tiles-spectrum") + tile + "] ";
-  Step proto = launch(real ? LM_TILES_RCONV_OLS : LM_TILES_CONV_OLS, PtrRef(BUF_INPUT, 0), PtrRef(BUF_OUTPUT, 0), items);
-  proto.i[LS_CONJ] = g.corr ? 1 : 0; proto.i[LS_OLS_WRAP] = wrap ? 1 : 0;
+  Step proto = launch(tm, real ? LM_TILES_RCONV_OLS : LM_TILES_CONV_OLS, PtrRef(BUF_INPUT, 0), PtrRef(BUF_OUTPUT, 0), items);
+  proto.i[LS_CONJ] = g.corr ? 1 : 0; proto.i[LS_OLS_WRAP] = wrap ? 1 : 0; proto.i[LS_TILES_CHANNELS] = sum ? C : 0;
   ols_store(proto.i, ax[0], ax[1]);
   proto.f[F_SCALE] = (float)(1.0 / (double)(P * P));
   proto.imap = conv_load_map(d, g, fs, 2);
-  push_per_kernel(b, d, g, proto, LP_MUL_SPECTRUM, G, P * P * 8);
-  b.ir.route += (real ? "tiles-rconv-ols" : "tiles-conv-ols") + tile + ",L=" + std::to_string(ax[0].L) + "x" + std::to_string(ax[1].L) + (wrap ? ",wrap] " : "] ");
+  push_per_kernel(b, d, g, proto, LP_MUL_SPECTRUM, G, C * P * P * 8);
+  b.ir.route += std::string(real ? "tiles-rconv-ols" : "tiles-conv-ols") + (sum ? "-sum" : "") + tile + ",L=" + std::to_string(ax[0].L) + "x" + std::to_string(ax[1].L) +
+                (sum ? ",C=" + std::to_string(C) : std::string()) + (wrap ? ",wrap] " : "] ");
   return true;
 }
 
@@ -2021,12 +2053,15 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
   if (int rv = conv_geometry(d, 8, g, b.ir, err)) return rv;
   const int rank = g.rank;
   const int64_t K = g.K, B = g.B, inN = g.inN;
+  // fftConv.inputChannels C > 1: B * C data lines and K * C kernels, result (k, b) = sum_c x[b C + c] (*) h[k C + c].  The single-channel routes below are
+  // not considered; the request takes emit_tiles_ols's sum form (rank 2, linear) or the composed route with the sum in its pointwise pass (fftconv-sum)
+  const int64_t C = g.C, BC = B * C, KC = K * C;
   const int64_t *ks = g.ks, *fs = g.fs, zero[8] = {0};
   const bool zpad = d.zero_read.enabled || d.zero_write.enabled;
   // ---- overlap-save: long complex lines, short kernels, one launch per kernel on blocks of P points (kern_lines.hpp fft_lines_conv_ols_kernel has the
   // index map); K P 8 bytes of workspace for any length.  The switch's rule is conv_ols_block
   // Circular requests (PlannerOptions::ols_circular, ols_circular_take) run the kernel's WRAP instances on the rule's block alone
-  if (rank == 1 && b.opt.conv_ols != 0 && b.opt.conv_lines && !b.opt.force_generic && g.lfN < ((int64_t)1 << 31) - 16384) {
+  if (rank == 1 && C == 1 && b.opt.conv_ols != 0 && b.opt.conv_lines && !b.opt.force_generic && g.lfN < ((int64_t)1 << 31) - 16384) {
     const int64_t sw = b.opt.conv_ols, rule = conv_ols_block(g.lfN, ks[0]);
     const bool wrap = !g.linear;
     const int64_t P = wrap ? (ols_circular_take(b.opt, d.shape, 1, rule) ? rule : 0) : ols_switch(sw, is_pow2(sw) && sw >= 128 && sw <= 4096, rule);
@@ -2048,7 +2083,7 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
   // ---- overlap-save in two dimensions (emit_tiles_ols); the switch's rule is conv_tiles_block
   if (rank == 2 && b.opt.conv_ols2d != 0 && b.opt.conv_lines && !b.opt.force_generic && b.opt.fuse_views && emit_tiles_ols(b, d, g, false)) return MI355FFT_OK;
   // ---- overlap-save in three dimensions (emit_bricks_ols); the switch's rule is conv_bricks_block
-  if (rank == 3 && b.opt.conv_ols3d != 0 && b.opt.conv_lines && !b.opt.force_generic && b.opt.fuse_views && emit_bricks_ols(b, d, g, false)) return MI355FFT_OK;
+  if (rank == 3 && C == 1 && b.opt.conv_ols3d != 0 && b.opt.conv_lines && !b.opt.force_generic && b.opt.fuse_views && emit_bricks_ols(b, d, g, false)) return MI355FFT_OK;
   // Long rank-1 linear modes: the next power of two keeps the transforms off the Bluestein / mixed-radix routes (ConvGeom)
   if (b.opt.conv_pad && rank == 1 && g.linear && g.lfN > 16384 && g.lfN <= ((int64_t)1 << 22) && !is_pow2(g.lfN)) {
     int64_t P = 32768;
@@ -2062,7 +2097,7 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
   // small 1-D circular problems: one launch, one workgroup per batch entry (kern_fftconv.hpp)
   // (throughput-sized problems do better on the line kernels below: measured 49 vs 150 GPoints/s at N=1024, batch 65536)
   const bool lines_mul_ok = b.opt.conv_lines && is_pow2(fN) && fN >= 64 && fN <= b.opt.max_line;
-  if (!b.opt.force_generic && !zpad && rank == 1 && !g.linear && K <= 15 &&
+  if (!b.opt.force_generic && !zpad && rank == 1 && C == 1 && !g.linear && K <= 15 &&
       !(lines_mul_ok && B * fN * K > b.opt.conv_fused_max_points)) {
     const ConvKernelMeta* cm = nullptr;
     for (const auto& m : conv_kernel_registry())
@@ -2096,26 +2131,26 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
   const bool map_fwd = small && fa >= 0 && b.axis_mappable(fs[fa], stride_below(fa), false);
   const bool map_inv = small && la >= 0 && b.axis_mappable(fs[la], stride_below(la), true);
   // 1. kernels: zero-padded into the FFT domain, transformed once per exec
-  PtrRef kf = b.alloc_work((uint64_t)K * fN * 8);
+  PtrRef kf = b.alloc_work((uint64_t)KC * fN * 8);
   bool kernel_embed = false;
   for (int i = 0; i < rank; ++i) if (ks[i] != fs[i]) kernel_embed = true;
   int rc;
   if (kernel_embed && map_fwd) {
     const SideMap km = conv_kernel_map(g, fs, rank);
-    rc = b.emit_nd(kern, kf, fs, rank, K, false, 1.0f, err, 0, 0, &km, nullptr);
+    rc = b.emit_nd(kern, kf, fs, rank, KC, false, 1.0f, err, 0, 0, &km, nullptr);
   } else {
     if (kernel_embed) {
-      b.zero(kf, K * fN * 2);
-      b.emit_strided(true, kern, kf, dense, ks, rank, K, fs, zero, fN, 0);
+      b.zero(kf, KC * fN * 2);
+      b.emit_strided(true, kern, kf, dense, ks, rank, KC, fs, zero, fN, 0);
     }
-    rc = b.emit_nd(kernel_embed ? kf : kern, kf, fs, rank, K, false, 1.0f, err);
+    rc = b.emit_nd(kernel_embed ? kf : kern, kf, fs, rank, KC, false, 1.0f, err);
   }
   if (rc) return rc;
   // 1b. 2^20-point circular lines, dense on both sides: forward transform, K products and K inverse transforms in ONE persistent launch
   // whose spectrum tiles never leave the registers (kern_regtile.hpp fft_xcd_conv1m_kernel): 56 + 40 (K - 1) B/point instead of 88 + 56 (K - 1)
   // The linear modes (a padded or exact 2^20-point domain) and zeroPad take the kernel's VIEW form: the embed of the data is a predicate of its
   // first loads, crop and zeroPad.write are predicates of its last stores (A reads 8 shape, C writes 8 os bytes per line and kernel)
-  if (b.opt.conv_pipeline && !b.opt.force_generic && b.opt.xcd_fused == 1 && b.opt.xcd_shared && !b.opt.only_pass && rank == 1 && fN == ((int64_t)1 << 20) &&
+  if (b.opt.conv_pipeline && !b.opt.force_generic && b.opt.xcd_fused == 1 && b.opt.xcd_shared && !b.opt.only_pass && rank == 1 && C == 1 && fN == ((int64_t)1 << 20) &&
       !d.input.strided && !d.output.strided) {
     const bool view = g.linear || zpad;
     const XcdKernelMeta* xm = nullptr;
@@ -2144,27 +2179,27 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
     }
   }
   // 2. data: gather (strided lanes) / embed (linear modes) into the dense FFT domain, forward transform once
-  PtrRef xf = b.alloc_work((uint64_t)B * fN * 8);
+  PtrRef xf = b.alloc_work((uint64_t)BC * fN * 8);
   const bool side_in = embed || d.input.strided || d.zero_read.enabled;
   const bool fuse_in = side_in && map_fwd;
   const SideMap xmap = fuse_in ? conv_load_map(d, g, fs, rank) : SideMap();
   if (!fuse_in) {
-    if (embed) b.zero(xf, B * fN * 2);
-    if (embed || d.input.strided) b.emit_strided(true, in, xf, d.input, d.shape, rank, B, fs, zero, fN, 0);
-    else if (d.zero_read.enabled) { Step& c = b.push(ST_COPY); c.p[P_SRC] = in; c.p[P_DST] = xf; c.i[S_COUNT] = B * fN * 8; }
-    if (d.zero_read.enabled) { emit_zero_outside(b, xf, d.zero_read, fs, rank, B); b.ir.route += "zero-read "; }
+    if (embed) b.zero(xf, BC * fN * 2);
+    if (embed || d.input.strided) b.emit_strided(true, in, xf, d.input, d.shape, rank, BC, fs, zero, fN, 0);
+    else if (d.zero_read.enabled) { Step& c = b.push(ST_COPY); c.p[P_SRC] = in; c.p[P_DST] = xf; c.i[S_COUNT] = BC * fN * 8; }
+    if (d.zero_read.enabled) { emit_zero_outside(b, xf, d.zero_read, fs, rank, BC); b.ir.route += "zero-read "; }
   }
   const bool staged = side_in && !fuse_in;
   // 1-D, power-of-two FFT length with an LDS-resident line kernel: the product with kernel k's spectrum rides the forward FFT's
   // last stage (kern_lines.hpp fft_lines_mul_kernel), one launch per kernel instead of forward FFT + K pointwise passes
   const LineKernelMeta* mul_m = nullptr;
-  if (b.opt.conv_lines && !b.opt.force_generic && rank == 1 && is_pow2(fN) && fN <= b.opt.max_line && !(b.opt.xcd_fused == 2 && fN == 4096)) {
+  if (b.opt.conv_lines && !b.opt.force_generic && rank == 1 && C == 1 && is_pow2(fN) && fN <= b.opt.max_line && !(b.opt.xcd_fused == 2 && fN == 4096)) {
     mul_m = find_line_kernel((int)fN, false, false, false, false, 0);
     if (mul_m && (mul_m->lds_bytes == 0 || mul_m->R1 <= 1)) mul_m = nullptr;
   }
   if (!mul_m) {
-    rc = fuse_in ? b.emit_nd(in, xf, fs, rank, B, false, 1.0f, err, 0, 0, &xmap, nullptr)
-                 : b.emit_nd(staged ? xf : in, xf, fs, rank, B, false, 1.0f, err);
+    rc = fuse_in ? b.emit_nd(in, xf, fs, rank, BC, false, 1.0f, err, 0, 0, &xmap, nullptr)
+                 : b.emit_nd(staged ? xf : in, xf, fs, rank, BC, false, 1.0f, err);
     if (rc) return rc;
   }
   const PtrRef mul_tables = mul_m ? b.line_tables(*mul_m) : PtrRef();
@@ -2188,8 +2223,8 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
       if (k == 0) b.ir.route += std::string(fuse_in ? "lines-mul-mapped[N=" : "lines-mul[N=") + std::to_string(fN) + "] ";
     } else {
       Step& pm = b.push(ST_POINTWISE);
-      pm.p[P_SRC] = xf; pm.p[P_DST] = y; pm.p[PWP_KERNEL] = kf.plus(k * fN * 8);
-      pm.i[PW_L] = fN; pm.i[PW_TOTAL] = B * fN; pm.i[PW_CONJ] = g.corr ? 1 : 0; pm.f[F_SCALE] = 1.0f;
+      pm.p[P_SRC] = xf; pm.p[P_DST] = y; pm.p[PWP_KERNEL] = kf.plus(k * C * fN * 8);
+      pm.i[PW_L] = fN; pm.i[PW_TOTAL] = B * fN; pm.i[PW_CONJ] = g.corr ? 1 : 0; pm.i[PW_CHANNELS] = C > 1 ? C : 0; pm.f[F_SCALE] = 1.0f;
       pm.grid = b.generic_grid(B * fN);
     }
     if (fuse_out) {
@@ -2211,7 +2246,7 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
     conv_staged_crop(b, d, g, out, y, k, false);
   }
   if (d.zero_write.enabled && !fuse_out) b.ir.route += "zero-write ";
-  b.ir.route += "fftconv[K=" + std::to_string(K) + "] ";
+  b.ir.route += C > 1 ? "fftconv-sum[K=" + std::to_string(K) + ",C=" + std::to_string(C) + "] " : "fftconv[K=" + std::to_string(K) + "] ";
   return MI355FFT_OK;
 }
 
@@ -2244,6 +2279,7 @@ int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err
   if (int rv = conv_geometry(d, 4, g, b.ir, err)) return rv;
   const int rank = g.rank;
   const int64_t K = g.K, B = g.B, inN = g.inN, kN = g.kN, oN = g.oN, lfN = g.lfN;
+  const int64_t C = g.C;      // fftConv.inputChannels > 1 (build_fftconv): emit_tiles_ols's sum form or rconv-sum, the composed route summing over c in its pointwise pass
   const bool linear = g.linear, corr = g.corr;
   const int64_t *ks = g.ks, *fs = g.fs, zero[8] = {0};
   const bool strided = d.input.strided || d.output.strided;
@@ -2252,7 +2288,7 @@ int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err
   // ---- overlap-save: long real lines, short kernels, one launch per kernel on blocks of P points, each running the pipeline of lines-rconv
   // (kern_lines.hpp fft_lines_rconv_ols_kernel has the index map).  The switch's rule, whatever the line's length when a block is forced:
   // Circular requests (PlannerOptions::ols_circular, ols_circular_take) run the kernel's WRAP instances on the rule's block alone
-  if (rank == 1 && b.opt.rconv_fused == 1 && b.opt.rconv_ols != 0 && !(b.opt.force_generic && !linear) && lfN < ((int64_t)1 << 31) - 16384) {
+  if (rank == 1 && C == 1 && b.opt.rconv_fused == 1 && b.opt.rconv_ols != 0 && !(b.opt.force_generic && !linear) && lfN < ((int64_t)1 << 31) - 16384) {
     const int64_t M = ks[0], sw = b.opt.rconv_ols;
     const bool wrap = !linear;
     // measured (profiles/fftconv_ols_ab.log, 256 x 2^20 (*) {31, 255, 1024, 4096}, K = 1 and 4, and three longer / shorter lines): every block length
@@ -2284,7 +2320,7 @@ int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err
   // ---- overlap-save in two dimensions on real tile pairs (emit_tiles_ols); the switch's rule is rconv_tiles_block
   if (rank == 2 && (linear || b.opt.fuse_views) && b.opt.rconv_ols2d != 0 && b.opt.rconv_fused != 0 && !b.opt.force_generic && emit_tiles_ols(b, d, g, true)) return MI355FFT_OK;
   // ---- overlap-save in three dimensions on real brick pairs (emit_bricks_ols); the switch's rule is rconv_bricks_block
-  if (rank == 3 && (linear || b.opt.fuse_views) && b.opt.rconv_ols3d != 0 && b.opt.rconv_fused != 0 && !b.opt.force_generic && emit_bricks_ols(b, d, g, true)) return MI355FFT_OK;
+  if (rank == 3 && C == 1 && (linear || b.opt.fuse_views) && b.opt.rconv_ols3d != 0 && b.opt.rconv_fused != 0 && !b.opt.force_generic && emit_bricks_ols(b, d, g, true)) return MI355FFT_OK;
 
   // ---- route 1: one launch per kernel on the line kernels --------------------------------------------------------------------
   int64_t P1 = 0;
@@ -2295,7 +2331,7 @@ int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err
   // behind barriers), so those lengths take rconv[K] unless a side is strided (only the line route's address maps carry lanes) or the
   // switch is 2 (every length: tests and measurement)
   const bool route1 = b.opt.rconv_fused == 2 || (b.opt.rconv_fused == 1 && (P1 <= 8192 || strided));
-  const LineKernelMeta* rm = (P1 && route1) ? b.lines_r2c_kernel(P1, false, true) : nullptr;
+  const LineKernelMeta* rm = (P1 && route1 && C == 1) ? b.lines_r2c_kernel(P1, false, true) : nullptr;
   if (rm) {
     const int64_t P = P1, H = P / 2;
     g.pad_axis0(P);
@@ -2316,6 +2352,7 @@ int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err
 
   // ---- route 3: circular, odd shape[0]: the complex plan between a widening and a narrowing pass ----------------------------------
   if (!linear && (lfN & 1)) {
+    if (C > 1) { err = "Unsupported: fftConv.inputChannels > 1 on real circular fftconv with odd shape[0] (no even FFT domain; use complex data)"; return MI355FFT_ERR_UNSUPPORTED; }
     mi355fft_plan_desc dc = d;
     dc.type = MI355FFT_FFTCONV;
     if (int rc = build_fftconv(dc, b, err)) return rc;
@@ -2375,18 +2412,18 @@ int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err
     if (rank > 1) return b.emit_nd(dst, dst, ps, rank, count, false, 1.0f, err, 1);
     return MI355FFT_OK;
   };
-  const PtrRef kf = b.alloc_work((uint64_t)K * pN * 8);
-  if ((rc = forward(kern, kf, ks, K, nullptr, conv_kernel_map(g, fs, 1)))) return rc;
-  const PtrRef xf = b.alloc_work((uint64_t)B * pN * 8);
-  if ((rc = forward(in, xf, d.shape, B, d.zero_read.enabled ? &d.zero_read : nullptr, conv_load_map(d, g, fs, 1)))) return rc;
+  const PtrRef kf = b.alloc_work((uint64_t)K * C * pN * 8);
+  if ((rc = forward(kern, kf, ks, K * C, nullptr, conv_kernel_map(g, fs, 1)))) return rc;
+  const PtrRef xf = b.alloc_work((uint64_t)B * C * pN * 8);
+  if ((rc = forward(in, xf, d.shape, B * C, d.zero_read.enabled ? &d.zero_read : nullptr, conv_load_map(d, g, fs, 1)))) return rc;
   const PtrRef y = b.alloc_work((uint64_t)B * pN * 8);
   const bool direct_out = !linear && d.conv_output_layout == MI355FFT_KERNEL_MAJOR;     // the real inverse can land in the output itself
   const PtrRef yr = direct_out ? PtrRef() : b.alloc_work((uint64_t)B * fN * 4);
   const float inv_n = (float)(1.0 / (double)fN);
   for (int64_t k = 0; k < K; ++k) {
     Step& pm = b.push(ST_POINTWISE);
-    pm.p[P_SRC] = xf; pm.p[P_DST] = y; pm.p[PWP_KERNEL] = kf.plus(k * pN * 8);
-    pm.i[PW_L] = pN; pm.i[PW_TOTAL] = B * pN; pm.i[PW_CONJ] = corr ? 1 : 0; pm.f[F_SCALE] = 1.0f;
+    pm.p[P_SRC] = xf; pm.p[P_DST] = y; pm.p[PWP_KERNEL] = kf.plus(k * C * pN * 8);
+    pm.i[PW_L] = pN; pm.i[PW_TOTAL] = B * pN; pm.i[PW_CONJ] = corr ? 1 : 0; pm.i[PW_CHANNELS] = C > 1 ? C : 0; pm.f[F_SCALE] = 1.0f;
     pm.grid = b.generic_grid(B * pN);
     if (rank > 1 && (rc = b.emit_nd(y, y, ps, rank, B, true, 1.0f, err, 1))) return rc;
     const PtrRef dst = direct_out ? out.plus(g.lane_offset(k) * 4) : yr;
@@ -2395,7 +2432,7 @@ int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err
     if (!direct_out) conv_staged_crop(b, d, g, out, yr, k, true);
   }
   if (d.zero_write.enabled) b.ir.route += "zero-write ";
-  b.ir.route += "rconv[K=" + std::to_string(K) + "] ";
+  b.ir.route += C > 1 ? "rconv-sum[K=" + std::to_string(K) + ",C=" + std::to_string(C) + "] " : "rconv[K=" + std::to_string(K) + "] ";
   return MI355FFT_OK;
 }
 

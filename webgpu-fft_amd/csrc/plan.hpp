@@ -42,10 +42,14 @@ struct ConvKernelMeta { int id, N, R0, R1, TL; };
 // LDS: the P x P tile at a pitch of P + 1 elements and the stage-1 roots
 #define MI355_TILE_KERNEL_LIST(X) X(64, 8, 8, 256) X(128, 16, 8, 1024)
 constexpr int tile_kernel_lds_bytes(int P, int R0, int R1) { return (P * (P + 1) + (R1 - 1) * R0) * 8; }
-struct TileKernelMeta { int id, P, R0, R1, threads, lds_bytes; bool real; };
+// the sum form (fftConv.inputChannels > 1: STileCfg / SRTileCfg, a loop over the input channels around load, forward and multiply-accumulate, one inverse and
+// one store a tile): a list, ids and units of its own (tiles_conv_ols_sum.hip, tiles_rconv_ols_sum.hip).  P = 64 alone: the accumulators are E more complex
+// registers a thread, which P = 128 on 1024 threads (124 of 128 VGPRs) cannot hold
+#define MI355_TILE_SUM_KERNEL_LIST(X) X(64, 8, 8, 256)
+struct TileKernelMeta { int id, P, R0, R1, threads, lds_bytes; bool real; bool sum; };
 // `real`: the same list as instances of fft_tiles_conv_ols_kernel on an RTileCfg (real fftconv: two real tiles as re / im of a complex one), a unit of their own
 // (tiles_rconv_ols.hip); an id counts positions in the list for both forms, and the step's line mode says which form is launched
-const TileKernelMeta* find_tile_kernel(int P, bool real = false);
+const TileKernelMeta* find_tile_kernel(int P, bool real = false, bool sum = false);
 // overlap-save brick kernels of rank-3 fftconv (kern_bricks.hpp fft_bricks_conv_ols_kernel): X(P, threads), id = position in the list.  LDS: the P^3 brick
 // at pitches of P + 1 and P (P + 1) elements.  `real`: the same list on an RBrickCfg (bricks_rconv_ols.hip), as with the tiles
 #define MI355_BRICK_KERNEL_LIST(X) X(16, 256)
@@ -178,7 +182,8 @@ enum LinesSlot {
   LS_TILES = 0, LS_LINES, LS_IN_S, LS_IN_OUTER, LS_OUT_S, LS_OUT_OUTER,
   LS_FS_SHIFT = 6, LS_MUL_CONJ = 6, LS_OLS2_FN_PLIM = 6,   // four-step roots: HI[m >> shift]; LM_MUL: multiply by the spectrum's conjugate; the brick modes: axis 2's fN (low 32 bits) and plim
   LS_FS_LO_MASK = 7, LS_CHIRP_FLAGS = 7, LS_OLS2_NB_L = 7, // ... LO[m & mask]; mapped LM_C2C / LM_MUL of Bluestein: LINES_CHIRP bits; the brick modes: axis 2's nb and L
-  LS_FS_GROUP = 8, LS_OLS2_W0_PRE = 8,       // PASS_B: rows per transform; COL_RAGGED: tiles per group (0 reads as 1); the brick modes: axis 2's w0 and pre
+  LS_FS_GROUP = 8, LS_OLS2_W0_PRE = 8, LS_TILES_CHANNELS = 8,   // PASS_B: rows per transform; COL_RAGGED: tiles per group (0 reads as 1); the brick modes: axis 2's w0 and pre;
+                                             // LM_TILES_CONV_OLS / LM_TILES_RCONV_OLS: input channels summed per tile (0, 1: none; above: the sum instances, `variant` an id of their list)
   LS_MODE = 9,                               // LineMode
   LS_MAPPED = 10,                            // sides through Step::imap / omap
   LS_H16 = 11,                               // binary16 sides (f16-storage)
@@ -294,7 +299,7 @@ enum PackSlot { PH_N = 0, PH_P, PH_BATCH, PH_PACKED_STRIDE, PH_LAST = PH_PACKED_
 static_assert(PH_LAST < STEP_INTS, "ST_PACK_HALF / ST_UNPACK_HERM slots");
 
 // ST_POINTWISE (p: P_SRC, P_DST, PWP_KERNEL)
-enum PointwiseSlot { PW_L = 0, PW_TOTAL, PW_CONJ, PW_LAST = PW_CONJ };
+enum PointwiseSlot { PW_L = 0, PW_TOTAL, PW_CONJ, PW_CHANNELS, PW_LAST = PW_CHANNELS };   // PW_CHANNELS C > 1: out[b][i] = sum_c data[b C + c][i] (conj?)kernel[c][i] (pointwise_sum_kernel)
 static_assert(PW_LAST < STEP_INTS, "ST_POINTWISE slots");
 enum PointwisePtr { PWP_KERNEL = 2, PWP_LAST = PWP_KERNEL };
 static_assert(PWP_LAST < STEP_PTRS, "ST_POINTWISE pointers");
@@ -399,6 +404,15 @@ struct PlannerOptions {
                                        // per kernel whatever the image's size (kern_tiles.hpp fft_tiles_conv_ols_kernel on an RTileCfg); 1: where measured ahead (plan.cpp
                                        // rconv_tiles_block); 0: never; 64 or 128: that tile on every request it fits (tests and measurement).  rconv_fused = 0 and
                                        // force_generic come first
+#ifdef MI355_HOST_EMU
+  int sum_ols2d = std::getenv("MI355_EMU_SUM_OLS2D") ? std::atoi(std::getenv("MI355_EMU_SUM_OLS2D")) : 1;
+#else
+  int sum_ols2d = 1;
+#endif
+                                       // fftconv / real fftconv with fftConv.inputChannels > 1, rank 2, linear boundaries: the sum form of the tile kernel, one launch per
+                                       // OUTPUT kernel (kern_tiles.hpp on an STileCfg / SRTileCfg); 1: where measured ahead (plan.cpp sum_tiles_block); 0: the composed
+                                       // routes fftconv-sum / rconv-sum; 64 or 128: that tile on every request it fits and an instance exists for (tests and measurement).
+                                       // conv_ols2d / rconv_ols2d = 0 and the switches in front of them come first
 #ifdef MI355_HOST_EMU
   int conv_ols3d = std::getenv("MI355_EMU_CONV_OLS3D") ? std::atoi(std::getenv("MI355_EMU_CONV_OLS3D")) : 1;
   int rconv_ols3d = std::getenv("MI355_EMU_RCONV_OLS3D") ? std::atoi(std::getenv("MI355_EMU_RCONV_OLS3D")) : 1;

@@ -363,6 +363,16 @@ export function resolvePlanOptions(opts) {
     assertOneOf(boundary, FFTCONV_BOUNDARIES, "fftConv.boundary");
     const kernelCount = dflt(fc.kernelCount, 1);
     if (!Number.isInteger(kernelCount) || kernelCount <= 0) throw new Error("fftConv.kernelCount must be a positive integer; got " + kernelCount);
+    // inputChannels C: the input holds batch * C lines (line b * C + c is channel c of item b), the kernel buffer kernelCount * C kernels (kernel (k, c)
+    // at k * C + c), and result (k, b) is the sum over c; the output side is that of C = 1
+    const inputChannels = dflt(fc.inputChannels, 1);
+    if (!Number.isInteger(inputChannels) || inputChannels <= 0) throw new Error("fftConv.inputChannels must be a positive integer; got " + inputChannels);
+    if (inputChannels > 1) {
+      if (fc.channelPolicy && typeof fc.channelPolicy === "object" && fc.channelPolicy.input != null) {
+        throw new Error("fftConv.inputChannels > 1 cannot be combined with fftConv.channelPolicy.input");
+      }
+      if (layout && layout.whdcn != null) throw new Error("fftConv.inputChannels > 1 cannot be combined with layout.whdcn");
+    }
     const outputLayout = dflt(fc.outputLayout, "kernel-major");
     assertOneOf(outputLayout, FFTCONV_OUTPUT_LAYOUTS, "fftConv.outputLayout");
     const kernelShape = dflt(fc.kernelShape, shape);
@@ -399,14 +409,15 @@ export function resolvePlanOptions(opts) {
       convMode: CONV_MODE_CODE[mode], convBoundary: CONV_BOUNDARY_CODE[boundary], convKernelCount: kernelCount,
       convOutputLayout: CONV_LAYOUT_CODE[outputLayout], convKernelShape: kernelShape.slice(),
       convOutputKernelStrideElements: explicitKStride || pol.kernelStride || 0,
+      convInputChannels: inputChannels > 1 ? inputChannels : 0,      // mi355fft_side_layout.reserved of the input side (include/mi355fft.h)
     });
     if (sides.input) desc.input = sides.input;
     if (sides.output) desc.output = sides.output;
-    Object.assign(meta, { mode, boundary, kernelCount, outputLayout, kernelShape: kernelShape.slice(), outputShape,
+    Object.assign(meta, { mode, boundary, kernelCount, inputChannels, outputLayout, kernelShape: kernelShape.slice(), outputShape,
       inputLayout: sides.input, outputLayoutResolved: sides.output, outputKernelStrideElements: desc.convOutputKernelStrideElements });
     if (realConv) {      // element = one f32 on both sides and in the kernel buffer
       desc.type = FFTCONV_REAL_CODE;
-      Object.assign(meta, { real: true, inputBytes: 4 * batch * prod(shape), kernelBytes: 4 * kernelCount * prod(kernelShape),
+      Object.assign(meta, { real: true, inputBytes: 4 * batch * inputChannels * prod(shape), kernelBytes: 4 * kernelCount * inputChannels * prod(kernelShape),
         outputBytes: 4 * batch * kernelCount * prod(outputShape) });
     }
     return { desc, meta };

@@ -66,20 +66,23 @@ export class Plan extends NativePlanBase {
   // one copyBufferToBuffer per kernel recorded ahead of the plan's own launches
   _prepareKernel(kernel, commandEncoder) {
     const single = (this.real ? 1 : 2) * prod(this.kernelShape);      // real fftconv plans take real kernels
-    const packed = single * this.kernelCount;
+    const channels = this.inputChannels || 1;                         // kernel (k, c) is entry k * inputChannels + c
+    const count = this.kernelCount * channels;
+    const counts = "kernelCount=" + this.kernelCount + (channels > 1 ? " x inputChannels=" + channels : "");
+    const packed = single * count;
     let payload = null;
     if (kernel instanceof Float32Array) {
-      if (this.kernelCount === 1) {
+      if (count === 1) {
         if (kernel.length !== single && kernel.length !== packed) throw new Error("kernel Float32Array length must be " + single + "; got " + kernel.length);
       } else if (kernel.length !== packed) {
-        throw new Error("kernel Float32Array length must be " + packed + " for kernelCount=" + this.kernelCount + "; got " + kernel.length);
+        throw new Error("kernel Float32Array length must be " + packed + " for " + counts + "; got " + kernel.length);
       }
       payload = kernel;
     } else if (Array.isArray(kernel)) {
-      if (kernel.length !== this.kernelCount) throw new Error("kernel array length must equal fftConv.kernelCount=" + this.kernelCount + "; got " + kernel.length);
+      if (kernel.length !== count) throw new Error("kernel array length must equal fftConv." + counts + "; got " + kernel.length);
       if (kernel.every((k) => k instanceof Float32Array)) {
         payload = new Float32Array(packed);
-        for (let i = 0; i < this.kernelCount; i++) {
+        for (let i = 0; i < count; i++) {
           if (kernel[i].length !== single) throw new Error("kernel[" + i + "] Float32Array length must be " + single + "; got " + kernel[i].length);
           payload.set(kernel[i], i * single);
         }
@@ -94,7 +97,7 @@ export class Plan extends NativePlanBase {
           return u;
         });
         this._ensureKernelUpload(packed * 4);
-        for (let i = 0; i < this.kernelCount; i++) {
+        for (let i = 0; i < count; i++) {
           native.encoderCopyBuffer(commandEncoder._h, srcs[i].buf._h, srcs[i].offset, this._kernelUpload._h, i * bytesEach, bytesEach);
         }
         return { buf: this._kernelUpload, offset: 0 };

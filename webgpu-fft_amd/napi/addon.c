@@ -332,6 +332,7 @@ static napi_value js_plan_create(napi_env env, napi_callback_info info) {
   d.conv_output_layout = (int32_t)prop_i64(env, o, "convOutputLayout", 0);
   prop_i64_array(env, o, "convKernelShape", d.conv_kernel_shape, MI355FFT_MAX_RANK);
   d.conv_output_kernel_stride_elements = prop_i64(env, o, "convOutputKernelStrideElements", 0);
+  d.input.reserved = (int32_t)prop_i64(env, o, "convInputChannels", 0);   /* fftConv.inputChannels: the input side's reserved word (mi355fft.h) */
   fill_view(env, o, "ioInput", &d.io_input);
   fill_view(env, o, "ioOutput", &d.io_output);
   fill_range(env, o, "zeroRead", &d.zero_read);

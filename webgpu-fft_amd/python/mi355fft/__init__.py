@@ -203,17 +203,20 @@ class Plan:
         conv = self._resolved["conv"]
         kn = int(np.prod(conv.get("kernelShape") or self._resolved["shape"]))
         per = 1 if self._resolved.get("real") else 2      # real fftconv plans take real kernels
-        single, packed = per * kn, per * kn * conv["kernelCount"]
+        channels = conv.get("inputChannels", 1)           # kernel (k, c) is entry k * inputChannels + c
+        count = conv["kernelCount"] * channels
+        single, packed = per * kn, per * kn * count
+        counts = f"kernelCount={conv['kernelCount']}" + (f" x inputChannels={channels}" if channels > 1 else "")
         if isinstance(kernel, (list, tuple)):
-            if len(kernel) != conv["kernelCount"]:
-                raise Mi355Error(1, f"kernel array length must equal fftConv.kernelCount={conv['kernelCount']}; got {len(kernel)}")
+            if len(kernel) != count:
+                raise Mi355Error(1, f"kernel array length must equal fftConv.{counts}; got {len(kernel)}")
             for i, k in enumerate(kernel):
                 if np.asarray(k).size != single:
                     raise Mi355Error(1, f"kernel[{i}] Float32Array length must be {single}; got {np.asarray(k).size}")
             kernel = np.concatenate([np.asarray(k, dtype=np.float32).reshape(-1) for k in kernel])
         kernel = np.ascontiguousarray(kernel, dtype=np.float32).reshape(-1)
         if kernel.size != packed:
-            raise Mi355Error(1, f"kernel Float32Array length must be {packed} for kernelCount={conv['kernelCount']}; got {kernel.size}")
+            raise Mi355Error(1, f"kernel Float32Array length must be {packed} for {counts}; got {kernel.size}")
         if self._kernel_upload is None or self._kernel_upload.size < kernel.nbytes:
             if self._kernel_upload is not None:
                 self._kernel_upload.destroy()

@@ -142,6 +142,8 @@ def make_desc(type, shape, batch=1, direction="forward", normalize="none", in_pl
             for i, s in enumerate(ks):
                 d.conv_kernel_shape[i] = int(s)
         d.conv_output_kernel_stride_elements = int(conv.get("outputKernelStrideElements", 0))
+        if int(conv.get("inputChannels", 1)) > 1:       # fftConv.inputChannels rides the input side's reserved word (include/mi355fft.h)
+            d.input.reserved = int(conv["inputChannels"])
     else:
         d.conv_kernel_count = 1
     if io_view:

@@ -458,6 +458,16 @@ def resolve_plan_options(opts):
         kernel_count = fc.get("kernelCount", 1)
         if not _is_int(kernel_count) or kernel_count <= 0:
             raise ValueError(f"fftConv.kernelCount must be a positive integer; got {kernel_count}")
+        # inputChannels C: the input holds batch * C lines (line b * C + c is channel c of item b), the kernel buffer kernelCount * C kernels
+        # (kernel (k, c) at k * C + c), and result (k, b) is the sum over c; the output side is that of C = 1
+        in_channels = fc.get("inputChannels", 1)
+        if not _is_int(in_channels) or isinstance(in_channels, bool) or in_channels <= 0:
+            raise ValueError(f"fftConv.inputChannels must be a positive integer; got {in_channels}")
+        if in_channels > 1:
+            if isinstance(fc.get("channelPolicy"), dict) and fc["channelPolicy"].get("input") is not None:
+                raise ValueError("fftConv.inputChannels > 1 cannot be combined with fftConv.channelPolicy.input")
+            if layout.get("whdcn") is not None:
+                raise ValueError("fftConv.inputChannels > 1 cannot be combined with layout.whdcn")
         output_layout = fc.get("outputLayout", "kernel-major")
         _assert_one_of(output_layout, FFTCONV_OUTPUT_LAYOUTS, "fftConv.outputLayout")
         kshape = fc.get("kernelShape") or shape
@@ -487,11 +497,12 @@ def resolve_plan_options(opts):
         inp, outl = resolve_layout_semantics(merged_layout, rank, shape, out_shape)
         out.update({"direction": "forward", "normalize": "none", "input_layout": inp, "output_layout": outl,
                     "conv": {"mode": mode, "boundary": boundary, "kernelCount": kernel_count, "outputLayout": output_layout,
-                             "kernelShape": kshape, "outputKernelStrideElements": explicit_kstride or policy_kstride or 0},
+                             "kernelShape": kshape, "outputKernelStrideElements": explicit_kstride or policy_kstride or 0,
+                             "inputChannels": in_channels},
                     "outputShape": out_shape})
         if real_conv:      # element = one f32 on both sides and in the kernel buffer
-            out.update({"abi_type": "fftconv-real", "real": True, "inputBytes": 4 * batch * _prod(shape),
-                        "kernelBytes": 4 * kernel_count * _prod(kshape), "outputBytes": 4 * batch * kernel_count * _prod(out_shape)})
+            out.update({"abi_type": "fftconv-real", "real": True, "inputBytes": 4 * batch * in_channels * _prod(shape),
+                        "kernelBytes": 4 * kernel_count * in_channels * _prod(kshape), "outputBytes": 4 * batch * kernel_count * _prod(out_shape)})
         if in_place:
             raise ValueError("fftconv inPlace=true is not supported in current implementation")
         return out
