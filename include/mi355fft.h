@@ -90,7 +90,14 @@ typedef struct mi355fft_io_view {
 } mi355fft_io_view;
 
 /* opts.zeroPad.{read,write} (runtime/zero_pad.js:11-45): logical elements outside [start, end) are zeroed — read: after
- * input load/embedding and before the transform; write: after transform + normalisation, before output extraction. */
+ * input load/embedding and before the transform; write: after transform + normalisation, before output extraction.
+ *
+ * `reserved` of zero_read of an MI355FFT_FFTCONV / MI355FFT_FFTCONV_REAL plan carries fftConv.groups G (0 or 1: none), whether or not the range
+ * is enabled.  G must divide inputChannels C (the input side's reserved word) and conv_kernel_count K.  Output kernel k belongs to group
+ * g = k / (K / G) and result (k, b) is sum_{c < C / G} x[b][g * (C / G) + c] (*) h[k][c]: G = C = K is depthwise, G = C with K = m * C depthwise
+ * with a channel multiplier.  The input side stays that of inputChannels (batch * C lines), the kernel buffer holds K * (C / G) packed
+ * kernels, kernel (k, c) at (k * (C / G) + c) * prod(kernelShape) (the [K][C / G][...] weight order), the output side is unchanged.  The word
+ * must be 0 in zero_write and on every other plan type; a negative or non-dividing value is rejected (MI355FFT_ERR_INVALID). */
 typedef struct mi355fft_zero_range {
   int32_t enabled;
   int32_t reserved;

@@ -287,6 +287,47 @@ MI355_TILE_SUM_LAUNCHER(launch_tiles_rconv_ols_sum)
 #endif
 #undef MI355_TILE_SUM_LAUNCHER
 
+// the grouped forms (fftConv.groups > 1: fft_tiles_conv_ols_group_kernel, routes tiles-conv-ols-group / tiles-rconv-ols-group, every output kernel in one launch; the spectrum
+// launches stay on the single-channel instances): the instances of MI355_TILE_GROUP_KERNEL_LIST, each data type in a unit of its own (tiles_conv_ols_group.hip,
+// tiles_rconv_ols_group.hip).  `id`: position in that list (plan.cpp find_tile_kernel with `group`)
+template <class L> bool launch_tiles_conv_ols_group(int id, const TilesGroupArgs& a, unsigned grid, L& l);
+template <class L> bool launch_tiles_rconv_ols_group(int id, const TilesGroupArgs& a, unsigned grid, L& l);
+inline TilesGroupArgs tiles_group_args_of(const Step& s, void* const ptr[STEP_PTRS]) {
+  const auto lo = [](int64_t v) { return (int)(v & 0xffffffff); };
+  const auto hi = [](int64_t v) { return (int)(v >> 32); };
+  return TilesGroupArgs{tiles_args_of(s, ptr), lo(s.i[LS_TILES_CHANNELS]), hi(s.i[LS_TILES_CHANNELS]), lo(s.i[LS_TILES_KERNELS]), hi(s.i[LS_TILES_KERNELS]), (long long)s.i[LS_TILES_LANE_K]};
+}
+#define MI355_TILE_GROUP_LAUNCHER(NAME)                                                               \
+  template <class L> bool NAME(int id, const TilesGroupArgs& a, unsigned grid, L& l) {                \
+    int cur = 0;                                                                                      \
+    MI355_TILE_GROUP_KERNEL_LIST(X)                                                                   \
+    (void)cur; (void)a; (void)grid; (void)l;                                                          \
+    return false;                                                                                     \
+  }
+#if defined(MI355_TILES_GROUP_DEFINE_INSTANCES) || defined(MI355_HOST_EMU)
+#define X(P, R0, R1, TH, DW)                                                                          \
+  if (id == cur) {                                                                                    \
+    using C = GroupTileCfg<P, R0, R1, TH, DW, false>;                                                 \
+    l.launch(fft_tiles_conv_ols_group_kernel<C>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a); \
+    return true;                                                                                      \
+  }                                                                                                   \
+  ++cur;
+MI355_TILE_GROUP_LAUNCHER(launch_tiles_conv_ols_group)
+#undef X
+#endif
+#if defined(MI355_RTILES_GROUP_DEFINE_INSTANCES) || defined(MI355_HOST_EMU)
+#define X(P, R0, R1, TH, DW)                                                                          \
+  if (id == cur) {                                                                                    \
+    using C = GroupTileCfg<P, R0, R1, TH, DW, true>;                                                  \
+    l.launch(fft_tiles_conv_ols_group_kernel<C>, grid, (unsigned)C::THREADS, (unsigned)C::LDS_BYTES, a); \
+    return true;                                                                                      \
+  }                                                                                                   \
+  ++cur;
+MI355_TILE_GROUP_LAUNCHER(launch_tiles_rconv_ols_group)
+#undef X
+#endif
+#undef MI355_TILE_GROUP_LAUNCHER
+
 // overlap-save on rank-3 bricks (kern_bricks.hpp fft_bricks_conv_ols_kernel, routes bricks-spectrum / bricks-conv-ols and, on an RBrickCfg, bricks-rspectrum /
 // bricks-rconv-ols): the instances of MI355_BRICK_KERNEL_LIST, each form in a unit of its own (bricks_conv_ols.hip, bricks_rconv_ols.hip).  `id`: position in
 // that list (plan.cpp find_brick_kernel)
@@ -665,6 +706,10 @@ bool dispatch_step(const Step& s, void* const ptr[STEP_PTRS], L& l, LinesFn&& li
         if (a.real_mode == LM_BRICKS_RCONV_OLS) return launch_bricks_rconv_ols_wrap(s.variant, bricks_args_of(s, ptr), s.grid, l);
         return false;
       }
+      if (s.i[LS_TILES_KERNELS] != 0 && (a.real_mode == LM_TILES_CONV_OLS || a.real_mode == LM_TILES_RCONV_OLS)) {   // fftConv.groups: every output kernel in this launch (linear tiles only)
+        return a.real_mode == LM_TILES_CONV_OLS ? launch_tiles_conv_ols_group(s.variant, tiles_group_args_of(s, ptr), s.grid, l)
+                                                : launch_tiles_rconv_ols_group(s.variant, tiles_group_args_of(s, ptr), s.grid, l);
+      }
       if (s.i[LS_TILES_CHANNELS] > 1) {   // the sum over input channels (linear tiles only; the spectrum launches never carry the count)
         if (a.real_mode == LM_TILES_CONV_OLS) return launch_tiles_conv_ols_sum(s.variant, tiles_sum_args_of(s, ptr), s.grid, l);
         if (a.real_mode == LM_TILES_RCONV_OLS) return launch_tiles_rconv_ols_sum(s.variant, tiles_sum_args_of(s, ptr), s.grid, l);
@@ -745,6 +790,11 @@ bool dispatch_step(const Step& s, void* const ptr[STEP_PTRS], L& l, LinesFn&& li
                (long long)s.i[PH_BATCH], (long long)s.i[PH_PACKED_STRIDE]);
       return true;
     case ST_POINTWISE:
+      if (s.i[PW_ITEM_LINES] > 0) {  // fftConv.groups: the product summed over one group's channels out of the item's PW_ITEM_LINES lines
+        l.launch(pointwise_group_sum_kernel, s.grid, 256u, 0u, (const cf*)ptr[P_SRC], (cf*)ptr[P_DST], (const cf*)ptr[PWP_KERNEL], (long long)s.i[PW_L], (long long)s.i[PW_TOTAL],
+                 (int)s.i[PW_CHANNELS], (int)s.i[PW_ITEM_LINES], (int)s.i[PW_CONJ], s.f[F_SCALE]);
+        return true;
+      }
       if (s.i[PW_CHANNELS] > 1) {    // fftConv.inputChannels: the product summed over the input channels
         l.launch(pointwise_sum_kernel, s.grid, 256u, 0u, (const cf*)ptr[P_SRC], (cf*)ptr[P_DST], (const cf*)ptr[PWP_KERNEL], (long long)s.i[PW_L], (long long)s.i[PW_TOTAL],
                  (int)s.i[PW_CHANNELS], (int)s.i[PW_CONJ], s.f[F_SCALE]);

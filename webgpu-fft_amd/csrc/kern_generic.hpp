@@ -366,10 +366,11 @@ static __global__ void __launch_bounds__(256) pointwise_mul_kernel(const cf* dat
 // out[b][i] = sum_c data[b C + c][i] * (conj?) kern[c][i]   — the product of fftconv with fftConv.inputChannels = C > 1 (routes fftconv-sum, rconv-sum): the
 // reduction over the input channels in the frequency domain, where it is pointwise.  `total` = batch * L output points, `kern` the C spectra of one output
 // kernel.  A thread owns a point: it reads each of the point's C data elements once and keeps the running sum in registers (8 C B read, 8 B written a point)
-static __global__ void __launch_bounds__(256) pointwise_sum_kernel(const cf* data, cf* out, const cf* kern, long long L, long long total, int channels, int conj_kernel, float s) {
+// The loop of both entry points: an item has `item_lines` data lines, of which the `channels` from `data` on are summed
+MI_DEV void pointwise_sum_points(const cf* data, cf* out, const cf* kern, long long L, long long total, int channels, int item_lines, int conj_kernel, float s) {
   for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (long long)gridDim.x * blockDim.x) {
     const long long b = g / L, i = g - b * L;
-    const cf* d = data + b * channels * L + i;
+    const cf* d = data + b * item_lines * L + i;
     const cf* k = kern + i;
     cf acc = {0.0f, 0.0f};
     for (int c = 0; c < channels; ++c) {
@@ -378,6 +379,16 @@ static __global__ void __launch_bounds__(256) pointwise_sum_kernel(const cf* dat
     }
     out[g] = acc * s;
   }
+}
+static __global__ void __launch_bounds__(256) pointwise_sum_kernel(const cf* data, cf* out, const cf* kern, long long L, long long total, int channels, int conj_kernel, float s) {
+  pointwise_sum_points(data, out, kern, L, total, channels, channels, conj_kernel, s);
+}
+// The same pass for fftConv.groups (routes fftconv-sum[..,G=g], rconv-sum[..,G=g]): of an item's `item_lines` data lines the `channels` of ONE group are summed,
+// `data` shifted to the group's first channel and `kern` the group-sized set of spectra of one output kernel; channels = 1 (depthwise) is a sum of one term.
+// An entry point of its own: pointwise_sum_kernel keeps the arguments its callers pass
+static __global__ void __launch_bounds__(256) pointwise_group_sum_kernel(const cf* data, cf* out, const cf* kern, long long L, long long total, int channels, int item_lines,
+                                                                         int conj_kernel, float s) {
+  pointwise_sum_points(data, out, kern, L, total, channels, item_lines, conj_kernel, s);
 }
 
 // Strided physical <-> dense logical, rank <= 8 (strided_complex.js:22-106).  Logical index is axis-0

@@ -33,6 +33,7 @@
 // The kernel spectra come from the same kernel (LM_TILES_RSPECTRUM): one kernel per work item in .x; nb_1 = 1 and L_1 = P put partner b at s0_1 = P, beyond the
 // kernel map's hi: zero imaginary parts, and the full complex P x P spectrum in the order above
 #pragma once
+#include <type_traits>
 #include "platform.hpp"
 #include "radix.hpp"
 #include "plan.hpp"
@@ -176,7 +177,9 @@ __global__ void __launch_bounds__(C::THREADS, C::WAVES_PER_SIMD) fft_tiles_conv_
       }
     }
     __syncthreads();
+#define MI_TILE_OUT_ORIGIN om.offset + (long long)sb * om.batch_stride
 #include "kern_tiles_inverse.inc"
+#undef MI_TILE_OUT_ORIGIN
   }
 }
 
@@ -247,7 +250,110 @@ __global__ void __launch_bounds__(C::THREADS, C::WAVES_PER_SIMD) fft_tiles_conv_
     }
 #pragma unroll
     for (int i = 0; i < C::E; ++i) v[i] = cswap(acc[i]);
+#define MI_TILE_OUT_ORIGIN om.offset + (long long)sb * om.batch_stride
 #include "kern_tiles_inverse.inc"
+#undef MI_TILE_OUT_ORIGIN
+  }
+}
+
+// ---- grouped and depthwise convolution (fftConv.groups = G > 1; routes tiles-conv-ols-group, tiles-rconv-ols-group): y[b][k] = sum_{c < Cg} x[b][g Cg + c] (*) h[k][c],
+// g = k / Kg, Cg = C / G, Kg = K / G, EVERY output kernel in one launch.  A work item is (sb, k, tile): item = (sb K + k) per_image + tile, tile fastest, so that
+// the items of one image and kernel are neighbours (they share the kernel's spectra) and the K kernels of an image follow each other (those of a group read the
+// same input tiles).  The decomposition is 32-bit unsigned and the same for every lane; of it only three values stay live across the item: the first input line
+// sb C + g Cg, the kernel's first spectrum k Cg P^2 and the origin of the output lane om.offset + k lane_k + sb om.batch_stride (the store map is kernel 0's).
+// Two forms:
+//   Cg > 1 (GTileCfg / GRTileCfg)  the sum kernel's item: a loop over the group's channels around load, forward and multiply-accumulate, one inverse, one store
+//   Cg = 1 (DTileCfg / DRTileCfg)  depthwise (with a channel multiplier when Kg > 1): the single-channel kernel's item, the product in the loads of the inverse's
+//                                  first stage, no accumulators
+// Linear boundaries only.  The load, the forward passes, the inverse and the store are the two .inc files' text.  All four configurations re-form the lane's
+// positions in every tile (REFORM_POSITIONS): the depthwise ones spilt 44 / 52 bytes a lane holding them, as the single-channel P = 64 instances do, and take
+// 113 / 114 VGPRs without; the sum ones sit at 128 like the sum kernel's.  No scratch, four workgroups a CU (profiles/fftconv_group_resource_usage.log)
+struct TilesGroupArgs { TilesArgs a; int channels, item_lines, kernels, kernels_per_group; long long out_kernel_stride; };   // Cg, C, K, Kg, ConvGeom::lane_k
+template <int P_, int R0_, int R1_, int THREADS_> struct GTileCfg : STileCfg<P_, R0_, R1_, THREADS_> { static constexpr bool DEPTHWISE = false; };
+template <int P_, int R0_, int R1_, int THREADS_> struct GRTileCfg : SRTileCfg<P_, R0_, R1_, THREADS_> { static constexpr bool DEPTHWISE = false; };
+template <int P_, int R0_, int R1_, int THREADS_> struct DTileCfg : TileCfg<P_, R0_, R1_, THREADS_> { static constexpr bool DEPTHWISE = true, REFORM_POSITIONS = true; };
+template <int P_, int R0_, int R1_, int THREADS_> struct DRTileCfg : RTileCfg<P_, R0_, R1_, THREADS_> { static constexpr bool DEPTHWISE = true, REFORM_POSITIONS = true; };
+template <int P_, int R0_, int R1_, int THREADS_, int DW, bool REAL> struct GroupTileCfgOf {
+  using type = typename std::conditional<DW != 0, typename std::conditional<REAL, DRTileCfg<P_, R0_, R1_, THREADS_>, DTileCfg<P_, R0_, R1_, THREADS_>>::type,
+                                         typename std::conditional<REAL, GRTileCfg<P_, R0_, R1_, THREADS_>, GTileCfg<P_, R0_, R1_, THREADS_>>::type>::type;
+};
+template <int P_, int R0_, int R1_, int THREADS_, int DW, bool REAL> using GroupTileCfg = typename GroupTileCfgOf<P_, R0_, R1_, THREADS_, DW, REAL>::type;
+
+template <class C>
+__global__ void __launch_bounds__(C::THREADS, C::WAVES_PER_SIMD) fft_tiles_conv_ols_group_kernel(const TilesGroupArgs ga) {
+  static_assert(!C::WRAP, "the grouped configurations: linear boundaries");
+  constexpr bool REAL = C::REAL;
+  const TilesArgs& a = ga.a;
+  MI_SMEM_DECL(smem);
+  cf* lds = reinterpret_cast<cf*>(smem);
+  cf* tw_lds = lds + C::DATA_ELEMS;
+  const int t = threadIdx.x;
+  for (int i = t; i < C::TW_ELEMS; i += C::THREADS) tw_lds[i] = a.tw[i];
+  __syncthreads();
+  const int line = t % C::P, u = t / C::P;
+  using I0 = TileStage<C, 0>;
+  using I1 = TileStage<C, 1>;
+  const SideMap& im = a.imap;
+  const SideMap& om = a.omap;
+  const TileAxis& A0 = a.ax[0];
+  const TileAxis& A1 = a.ax[1];
+  const unsigned per_image = (unsigned)A0.nb * (REAL ? ((unsigned)A1.nb + 1u) / 2u : (unsigned)A1.nb);
+  for (long long tile = blockIdx.x; tile < a.num_tiles; tile += gridDim.x) {
+    const unsigned sk = (unsigned)tile / per_image, r = (unsigned)tile - sk * per_image, j1 = r / (unsigned)A0.nb, j0 = r - j1 * (unsigned)A0.nb;
+    const int s00 = (int)j0 * A0.L - A0.pre, s01 = (int)(REAL ? 2u * j1 : j1) * A1.L - A1.pre;
+    // the item's image sb and kernel k, and what is kept of them: its first input line, its first spectrum, the origin of its output lane
+    long long in_line, out_origin;
+    const cf* hs;
+    {
+      const unsigned sb = sk / (unsigned)ga.kernels, k = sk - sb * (unsigned)ga.kernels, g = k / (unsigned)ga.kernels_per_group;
+      in_line = (long long)sb * ga.item_lines + (long long)g * ga.channels;
+      hs = a.spectrum + (long long)k * ga.channels * (C::P * C::P);
+      out_origin = om.offset + (long long)k * ga.out_kernel_stride + (long long)sb * om.batch_stride;
+    }
+    cf v[C::E];
+    if constexpr (C::DEPTHWISE) {
+#define MI_TILE_IN_LINE in_line
+#include "kern_tiles_forward.inc"
+#undef MI_TILE_IN_LINE
+      // ---- product in the loads of the inverse's first stage ----
+#pragma unroll
+      for (int b = 0; b < I0::NB; ++b) {
+#pragma unroll
+        for (int q = 0; q < I0::R; ++q) {
+          const int k0 = u + b * C::TPL + q * (C::P / I0::R);
+          cf h = hs[k0 * C::P + line];
+          if (a.conj) h.y = -h.y;
+          v[b * I0::R + q] = cswap(cmul(lds[tile_index<C, false>(line, k0)], h));
+        }
+      }
+      __syncthreads();
+    } else {
+      cf acc[C::E];
+#pragma unroll
+      for (int i = 0; i < C::E; ++i) acc[i] = cf{0.0f, 0.0f};
+      for (int c = 0; c < ga.channels; ++c) {
+#define MI_TILE_IN_LINE (in_line + c)
+#include "kern_tiles_forward.inc"
+#undef MI_TILE_IN_LINE
+        const cf* hc = hs + (long long)c * (C::P * C::P);
+#pragma unroll
+        for (int b = 0; b < I0::NB; ++b) {
+#pragma unroll
+          for (int q = 0; q < I0::R; ++q) {
+            const int k0 = u + b * C::TPL + q * (C::P / I0::R);
+            cf h = hc[k0 * C::P + line];
+            if (a.conj) h.y = -h.y;
+            acc[b * I0::R + q] += cmul(lds[tile_index<C, false>(line, k0)], h);
+          }
+        }
+        __syncthreads();          // LDS is re-used by the next channel, and then by the inverse
+      }
+#pragma unroll
+      for (int i = 0; i < C::E; ++i) v[i] = cswap(acc[i]);
+    }
+#define MI_TILE_OUT_ORIGIN out_origin
+#include "kern_tiles_inverse.inc"
+#undef MI_TILE_OUT_ORIGIN
   }
 }
 

@@ -1,5 +1,6 @@
 // kern_tiles_inverse.inc — a tile's inverse 2-D FFT from the products in v[] and its store, the text shared by fft_tiles_conv_ols_kernel and
-// fft_tiles_conv_ols_sum_kernel (kern_tiles.hpp; see kern_tiles_forward.inc)
+// fft_tiles_conv_ols_sum_kernel (kern_tiles.hpp; see kern_tiles_forward.inc).  MI_TILE_OUT_ORIGIN: the element the work item's output lane starts at, without
+// parentheses (om.offset + sb * om.batch_stride in the kernels whose launch has one output kernel: the tokens they always had; the grouped kernel adds its kernel's lane)
     tile_stage_compute<C, 0>(v, tw_lds, u);
     tile_stage_write<C, 0, false>(v, lds, line, u);
     __syncthreads();
@@ -22,7 +23,7 @@
       const int m0 = q0 < 0 ? q0 + A0.fN : q0;                                   // (the negative lags of a correlation sit at the top of the domain)
       const bool ok0 = line >= A0.w0 && line < A0.w0 + A0.L && q0 < A0.plim && m0 >= om.lo[0] && m0 < om.hi[0];
       const bool z0 = m0 < om.zlo[0] || m0 >= om.zhi[0];
-      float* y = reinterpret_cast<float*>(a.out) + (om.offset + (long long)sb * om.batch_stride + (long long)m0 * om.stride[0]);   // (dereferenced inside the crop only)
+      float* y = reinterpret_cast<float*>(a.out) + (MI_TILE_OUT_ORIGIN + (long long)m0 * om.stride[0]);   // (dereferenced inside the crop only)
       const long long s1 = om.stride[1];
       const int s01b = s01 + A1.L;
       int wlo = A1.w0, us = u;
@@ -52,7 +53,7 @@
       const int m0 = q0 < 0 ? q0 + A0.fN : q0;                                   // (the negative lags of a correlation sit at the top of the domain)
       const bool ok0 = line >= A0.w0 && line < A0.w0 + A0.L && q0 < A0.plim && m0 >= om.lo[0] && m0 < om.hi[0];
       const bool z0 = m0 < om.zlo[0] || m0 >= om.zhi[0];
-      cf* y = a.out + (om.offset + (long long)sb * om.batch_stride + (long long)m0 * om.stride[0]);   // (dereferenced inside the crop only)
+      cf* y = a.out + (MI_TILE_OUT_ORIGIN + (long long)m0 * om.stride[0]);   // (dereferenced inside the crop only)
       const long long s1 = om.stride[1];
       int wlo = A1.w0, us = u;
       MI_TILE_OPAQUE(wlo);

@@ -87,7 +87,7 @@ const std::vector<ConvKernelMeta>& conv_kernel_registry() {
   return reg;
 }
 
-const TileKernelMeta* find_tile_kernel(int P, bool real, bool sum) {
+const TileKernelMeta* find_tile_kernel(int P, bool real, bool sum, int group) {
   static const std::vector<TileKernelMeta> reg = [] {
     std::vector<TileKernelMeta> r;
     for (int real = 0; real < 2; ++real) {   // both forms instantiate the whole list: an id is the position in it
@@ -99,10 +99,14 @@ const TileKernelMeta* find_tile_kernel(int P, bool real, bool sum) {
 #define X(P, R0, R1, TH) r.push_back(TileKernelMeta{id++, P, R0, R1, TH, tile_kernel_lds_bytes(P, R0, R1), real != 0, true});
       MI355_TILE_SUM_KERNEL_LIST(X)
 #undef X
+      id = 0;                                // the grouped forms: ids of their own list
+#define X(P, R0, R1, TH, DW) r.push_back(TileKernelMeta{id++, P, R0, R1, TH, tile_kernel_lds_bytes(P, R0, R1), real != 0, DW == 0, DW ? 2 : 1});
+      MI355_TILE_GROUP_KERNEL_LIST(X)
+#undef X
     }
     return r;
   }();
-  for (const auto& m : reg) if (m.P == P && m.real == real && m.sum == sum) return &m;
+  for (const auto& m : reg) if (m.P == P && m.real == real && m.sum == sum && m.group == group) return &m;
   return nullptr;
 }
 
@@ -196,6 +200,7 @@ PlannerOptions planner_options_from_env() {
   if (const char* s = std::getenv("MI355FFT_CONV_OLS2D")) o.conv_ols2d = std::atoi(s);
   if (const char* s = std::getenv("MI355FFT_RCONV_OLS2D")) o.rconv_ols2d = std::atoi(s);
   if (const char* s = std::getenv("MI355FFT_SUM_OLS2D")) o.sum_ols2d = std::atoi(s);
+  if (const char* s = std::getenv("MI355FFT_GROUP_OLS2D")) o.group_ols2d = std::atoi(s);
   if (const char* s = std::getenv("MI355FFT_CONV_OLS3D")) o.conv_ols3d = std::atoi(s);
   if (const char* s = std::getenv("MI355FFT_RCONV_OLS3D")) o.rconv_ols3d = std::atoi(s);
   if (const char* s = std::getenv("MI355FFT_OLS_CIRCULAR")) o.ols_circular = std::atoi(s);
@@ -1145,6 +1150,11 @@ int validate_common(const mi355fft_plan_desc& d, std::string& err) {
     err = "mi355fft_side_layout.reserved must be 0 (it carries fftConv.inputChannels on the input side of fftconv plans only)"; return MI355FFT_ERR_INVALID;
   }
   if (conv && d.input.reserved < 0) { err = "fftConv.inputChannels must be a positive integer; got " + std::to_string(d.input.reserved); return MI355FFT_ERR_INVALID; }
+  // mi355fft_zero_range.reserved: fftConv.groups in zero_read of the two fftconv types (whether or not the range is enabled), zero everywhere else
+  if (d.zero_write.reserved != 0 || (!conv && d.zero_read.reserved != 0)) {
+    err = "mi355fft_zero_range.reserved must be 0 (it carries fftConv.groups in zero_read of fftconv plans only)"; return MI355FFT_ERR_INVALID;
+  }
+  if (conv && d.zero_read.reserved < 0) { err = "fftConv.groups must be a positive integer; got " + std::to_string(d.zero_read.reserved); return MI355FFT_ERR_INVALID; }
   return MI355FFT_OK;
 }
 
@@ -1641,6 +1651,8 @@ struct ConvGeom {
   int rank;
   int64_t K, B;
   int64_t C = 1;                          // fftConv.inputChannels: B * C data lines and K * C kernels, result (k, b) summed over c
+  int64_t G = 1, Cg = 1, Kg = 1;          // fftConv.groups: Cg = C / G channels and Kg = K / G kernels a group; K * Cg kernels, result (k, b) summed over the Cg channels
+                                          // of group k / Kg, which start at input line b C + (k / Kg) Cg
   bool linear, corr;
   int64_t ks[8], fs[8], os[8], ooff[8];   // kernel shape, FFT domain (axis 0 as padded), output shape, crop offset on the logical domain
   int64_t inN, kN, oN, lfN;               // elements of a data item, a kernel and an output item; logical axis-0 length of the FFT domain
@@ -1657,6 +1669,8 @@ struct ConvGeom {
   // the crop holds both positive and negative lags of a correlation: two pieces of the padded domain
   bool straddle() const { return padD > 0 && ooff[0] < split && ooff[0] + os[0] > split; }
   int64_t lane_offset(int64_t k) const { return lane0 + k * lane_k; }
+  bool depthwise() const { return G > 1 && Cg == 1; }      // every output kernel reads ONE input channel (Kg > 1: a channel multiplier)
+  bool one_channel() const { return C == 1 || depthwise(); }   // the single-channel routes apply (depthwise: the overlap-save ones, through push_per_kernel's load map)
 };
 
 // Validates the fftconv options and fills the geometry and the plan's extents for elements of `elem` bytes (8: complex, 4: real)
@@ -1669,6 +1683,11 @@ int conv_geometry(const mi355fft_plan_desc& d, int64_t elem, ConvGeom& g, PlanIR
   const int rank = g.rank = d.rank;
   const int64_t K = g.K = d.conv_kernel_count, B = g.B = d.batch, C = g.C = std::max<int64_t>(1, d.input.reserved);
   if (C > 1 && prodv(d.shape, rank) * B * C > ((int64_t)1 << 40)) { err = "Unsupported: more than 2^40 points in one plan"; return MI355FFT_ERR_UNSUPPORTED; }
+  const int64_t G = g.G = std::max<int64_t>(1, d.zero_read.reserved);
+  if (C % G) { err = "fftConv.groups=" + std::to_string(G) + " must divide fftConv.inputChannels=" + std::to_string(C); return MI355FFT_ERR_INVALID; }
+  if (K % G) { err = "fftConv.groups=" + std::to_string(G) + " must divide fftConv.kernelCount=" + std::to_string(K); return MI355FFT_ERR_INVALID; }
+  const int64_t Cg = g.Cg = C / G;
+  g.Kg = K / G;
   g.linear = d.conv_boundary != MI355FFT_CIRCULAR;
   g.corr = d.conv_mode == MI355FFT_CORRELATION;
   bool ks_given = false;
@@ -1698,7 +1717,7 @@ int conv_geometry(const mi355fft_plan_desc& d, int64_t elem, ConvGeom& g, PlanIR
   const int64_t inN = g.inN = prodv(d.shape, rank), kN = g.kN = prodv(g.ks, rank), oN = g.oN = prodv(g.os, rank);
   const int64_t kstride = d.conv_output_kernel_stride_elements;
   if (d.output.strided && K > 1 && kstride <= 0) { err = "multi-kernel strided output requires fftConv.channelPolicy.output or fftConv.outputKernelStrideElements"; return MI355FFT_ERR_INVALID; }
-  ir.kernel_bytes = (uint64_t)K * C * kN * elem;
+  ir.kernel_bytes = (uint64_t)K * Cg * kN * elem;
   ir.in_bytes = d.input.strided ? strided_extent_elems(d.input, d.shape, rank, B * C, 0) * elem : (uint64_t)inN * B * C * elem;
   ir.out_bytes = d.output.strided ? strided_extent_elems(d.output, g.os, rank, B, (K - 1) * kstride) * elem : (uint64_t)K * B * oN * elem;
   const bool kmajor = d.conv_output_layout == MI355FFT_KERNEL_MAJOR;
@@ -1834,6 +1853,17 @@ int64_t rconv_tiles_block(int64_t fN0, int64_t fN1, int64_t M0, int64_t M1) { re
 // (98-297 / 100-534 G complex / real input points/s)
 int64_t sum_tiles_block(int64_t fN0, int64_t fN1, int64_t M0, int64_t M1) { return conv_tiles_block(fN0, fN1, M0, M1) == 64 ? 64 : 0; }
 
+// The tile edge the default rule (PlannerOptions::group_ols2d == 1) gives to the grouped tile kernel (fftConv.groups > 1, every output kernel in one launch): sum_tiles_block's
+// bounds (conv_tiles_block's on the domain, kernels up to 17 points an axis: the one grouped tile there is, P = 64), for all four classes of request (depthwise, Cg = 1 /
+// grouped sums, Cg > 1; complex / real).  A class is in the rule only where the kernel was ahead of BOTH alternatives on every measured request of the class by more than
+// the spread between a form's two medians; all four were.  Measured (profiles/fftconv_group_ab.log, tools/fftconv_group_ab.py: linear-same, 8 x 256^2 (*) 3x3 and 5x5 with
+// C = K = G = 64, 4 x 512^2 (*) 9x9 with C = K = G = 32, 8 x 256^2 (*) 3x3 with C = K = 64, G = 4 and with C = 16, K = 32, G = 16, 3 x 1920x1080 (*) 17x17 with
+// C = K = G = 3; the three forms timed alternately in one process, spread <= 1.5 %): against MI355FFT_GROUP_OLS2D=0 (depthwise: the single-channel tile route through the
+// per-kernel load map, 1 + K launches; Cg > 1: the composed route) the one launch is 2.4-3.6x (complex) and 3.3-5.5x (real) ahead on the depthwise requests of 32 and 64
+// channels, 1.12x / 1.10x at C = 3 on 1920x1080 (3 launches saved, every launch already full) and 10.4x / 10.1x on G = 4; against G plans with inputChannels = Cg and
+// kernelCount = Kg on data already sliced per group, the slicing not counted, 3.3-5.2x / 4.8-8.2x, 1.22x / 1.26x and 2.6x / 4.5x
+int64_t group_tiles_block(int64_t fN0, int64_t fN1, int64_t M0, int64_t M1) { return sum_tiles_block(fN0, fN1, M0, M1); }
+
 // The brick edge the default rule (PlannerOptions::conv_ols3d == 1) gives to overlap-save on a rank-3 volume of fN0 x fN1 x fN2 = shape + M - 1 logical points
 // and a kernel of M0 x M1 x M2 points; 0: the request keeps its earlier route.  Left alone: domains of at most 32768 points and axes below 32 points (the
 // small requests whose routes the tests pin; a brick would be mostly padding) and kernels beyond 9 points on an axis (a brick returns less than 1/8 of its
@@ -1908,14 +1938,22 @@ bool ols_circular_take(const PlannerOptions& opt, const int64_t* shape, int rank
 
 // One launch per kernel: K copies of the prepared step `proto`, launch k with kernel k's spectrum (`spectra` + k * `bytes`) in p[slot] and kernel k's
 // lane of the output behind its store map.  (The overlap-save routes and lines-rconv[N=P]; the caller has written the mode's own slots)
+// Depthwise requests (fftConv.groups with Cg = 1, ConvGeom::depthwise) run the single-channel kernels through the load map alone: launch k reads one channel of
+// every item, input line b C + k / Kg, so the map steps C lines from item to item and starts k / Kg lines in
 void push_per_kernel(Builder& b, const mi355fft_plan_desc& d, const ConvGeom& g, const Step& proto, LinesPtr slot, PtrRef spectra, int64_t bytes) {
   for (int64_t k = 0; k < g.K; ++k) {
     Step& st = b.push(ST_LINES);
     st = proto;
     st.p[slot] = spectra.plus(k * bytes);
     st.omap = conv_store_map(d, g, g.fs, g.rank, k);
+    if (g.depthwise()) {
+      st.imap.offset += (k / g.Kg) * proto.imap.batch_stride;
+      st.imap.batch_stride = proto.imap.batch_stride * g.C;
+    }
   }
 }
+// the route tag's last field of such a request
+std::string depthwise_field(const ConvGeom& g) { return g.depthwise() ? ",G=" + std::to_string(g.G) : std::string(); }
 
 // That step for the line routes: `lines` lines (or blocks) of P points on the line kernel `m`, `outer` LDS elements a line, read through the data map.
 // The real modes carry the split roots `proots` (LO and HI in one table) as well
@@ -1949,18 +1987,31 @@ bool emit_tiles_ols(Builder& b, const mi355fft_plan_desc& d, const ConvGeom& g, 
   // fftConv.inputChannels C > 1: the kernel's sum form.  A work item loops over c: channel c's tile from input line sb C + c (the load map's batch stride is the
   // line stride), forward, accumulate times spectrum (k, c); one inverse and one store a tile.  K C spectra in the workspace, launch k reads those from k C on.
   // Linear boundaries only; its own switch (PlannerOptions::sum_ols2d, rule sum_tiles_block) behind the route's
-  const int64_t C = g.C, ssw = b.opt.sum_ols2d;
-  const bool sum = C > 1;
+  // fftConv.groups G > 1, three ways:
+  //   the grouped kernel (PlannerOptions::group_ols2d, rule group_tiles_block; linear boundaries): ONE launch of B K per_image work items, item (sb, k, tile) summing the
+  //     Cg channels of group k / Kg into kernel k's lane; K Cg spectra in the workspace
+  //   depthwise (Cg = 1) without it: the single-channel instances under their own switch and rule, circular ones included, launch k reading channel k / Kg
+  //     through its load map (push_per_kernel)
+  //   Cg > 1 without it: not here (the composed routes)
+  const int64_t C = g.C, Cg = g.Cg, ssw = b.opt.sum_ols2d, gsw = b.opt.group_ols2d;
+  const int64_t PG = g.G > 1 && !wrap ? (gsw == 64 ? 64 : gsw == 1 ? group_tiles_block(fs[0], fs[1], ks[0], ks[1]) : 0) : 0;
+  const OlsAxis gax[2] = {ols_axis(fs[0], d.shape[0], ks[0], PG, g.corr, false, false), ols_axis(fs[1], d.shape[1], ks[1], PG, g.corr, false, false)};
+  const TileKernelMeta* gm = PG && gax[0].L >= 2 && gax[1].L >= 2 ? find_tile_kernel((int)PG, real, Cg > 1, Cg > 1 ? 1 : 2) : nullptr;
+  const bool grouped = gm != nullptr;
+  if (g.G > 1 && !grouped && Cg > 1) return false;
+  const bool sum = !grouped && g.G == 1 && C > 1;
   if (sum && (wrap || ssw == 0)) return false;
-  const int64_t P = sum ? ols_switch(ssw, ssw == 64 || ssw == 128, sum_tiles_block(fs[0], fs[1], ks[0], ks[1]))
+  const int64_t P = grouped ? PG
+                  : sum ? ols_switch(ssw, ssw == 64 || ssw == 128, sum_tiles_block(fs[0], fs[1], ks[0], ks[1]))
                         : wrap ? (ols_circular_take(b.opt, d.shape, 2, rule) ? rule : 0) : ols_switch(sw, sw == 64 || sw == 128, rule);
-  const TileKernelMeta* tm = P ? find_tile_kernel((int)P, real, sum) : nullptr;
-  const TileKernelMeta* sm = sum && tm ? find_tile_kernel((int)P, real) : tm;    // the spectrum launch stays on the single-channel instance
+  const TileKernelMeta* tm = grouped ? gm : P ? find_tile_kernel((int)P, real, sum) : nullptr;
+  const TileKernelMeta* sm = (sum || grouped) && tm ? find_tile_kernel((int)P, real) : tm;    // the spectrum launch stays on the single-channel instance
   const OlsAxis ax[2] = {ols_axis(fs[0], d.shape[0], ks[0], P, g.corr, false, wrap), ols_axis(fs[1], d.shape[1], ks[1], P, g.corr, false, wrap)};
-  const int64_t items = g.B * ax[0].nb * (real ? (ax[1].nb + 1) / 2 : ax[1].nb);
-  if (!tm || !sm || ax[0].L < 2 || ax[1].L < 2 || ax[0].nb * ax[1].nb >= lim || items >= lim || g.B * C >= lim || g.K * C >= lim) return false;
+  const int64_t per_image = ax[0].nb * (real ? (ax[1].nb + 1) / 2 : ax[1].nb);
+  const int64_t items = g.B * (grouped ? g.K : 1) * per_image;
+  if (!tm || !sm || ax[0].L < 2 || ax[1].L < 2 || ax[0].nb * ax[1].nb >= lim || g.B * per_image >= lim || items >= lim || g.B * C >= lim || g.K * Cg >= lim) return false;
   const int64_t pd[2] = {P, P};
-  const PtrRef G = b.alloc_work((uint64_t)g.K * C * P * P * 8);
+  const PtrRef G = b.alloc_work((uint64_t)g.K * Cg * P * P * 8);
   std::vector<float2h> roots;
   for (int q = 1; q < tm->R1; ++q) for (int k = 0; k < tm->R0; ++k) roots.push_back(root_of_unity((int64_t)q * k, P));
   const PtrRef tables = b.add_table(roots);
@@ -1977,7 +2028,7 @@ bool emit_tiles_ols(Builder& b, const mi355fft_plan_desc& d, const ConvGeom& g, 
     return st;
   };
   const std::string tile = "[N=" + std::to_string(P) + "x" + std::to_string(P);
-  Step sp = launch(sm, real ? LM_TILES_RSPECTRUM : LM_TILES_SPECTRUM, PtrRef(BUF_KERNEL, 0), G, g.K * C);
+  Step sp = launch(sm, real ? LM_TILES_RSPECTRUM : LM_TILES_SPECTRUM, PtrRef(BUF_KERNEL, 0), G, g.K * Cg);
   OlsAxis whole;
   whole.fN = whole.plim = whole.L = P; whole.nb = 1;
   ols_store(sp.i, whole, whole);
@@ -1989,9 +2040,19 @@ bool emit_tiles_ols(Builder& b, const mi355fft_plan_desc& d, const ConvGeom& g, 
   ols_store(proto.i, ax[0], ax[1]);
   proto.f[F_SCALE] = (float)(1.0 / (double)(P * P));
   proto.imap = conv_load_map(d, g, fs, 2);
-  push_per_kernel(b, d, g, proto, LP_MUL_SPECTRUM, G, C * P * P * 8);
-  b.ir.route += std::string(real ? "tiles-rconv-ols" : "tiles-conv-ols") + (sum ? "-sum" : "") + tile + ",L=" + std::to_string(ax[0].L) + "x" + std::to_string(ax[1].L) +
-                (sum ? ",C=" + std::to_string(C) : std::string()) + (wrap ? ",wrap] " : "] ");
+  const std::string tiles = ",L=" + std::to_string(ax[0].L) + "x" + std::to_string(ax[1].L);
+  if (grouped) {      // one launch: the kernel forms each item's lane from kernel 0's store map and ConvGeom::lane_k, uniform for every output layout, explicit kernel stride and channel policy
+    const auto both = [](int64_t lo, int64_t hi) { return (int64_t)((uint64_t)lo | ((uint64_t)hi << 32)); };
+    proto.i[LS_TILES_CHANNELS] = both(Cg, C); proto.i[LS_TILES_KERNELS] = both(g.K, g.Kg); proto.i[LS_TILES_LANE_K] = g.lane_k;
+    proto.p[LP_MUL_SPECTRUM] = G;
+    proto.omap = conv_store_map(d, g, g.fs, g.rank, 0);
+    b.ir.steps.push_back(proto);
+    b.ir.route += std::string(real ? "tiles-rconv-ols-group" : "tiles-conv-ols-group") + tile + tiles + ",C=" + std::to_string(C) + ",G=" + std::to_string(g.G) + ",K=" + std::to_string(g.K) + "] ";
+    return true;
+  }
+  push_per_kernel(b, d, g, proto, LP_MUL_SPECTRUM, G, Cg * P * P * 8);
+  b.ir.route += std::string(real ? "tiles-rconv-ols" : "tiles-conv-ols") + (sum ? "-sum" : "") + tile + tiles +
+                (sum ? ",C=" + std::to_string(C) : std::string()) + depthwise_field(g) + (wrap ? ",wrap] " : "] ");
   return true;
 }
 
@@ -2042,7 +2103,7 @@ bool emit_bricks_ols(Builder& b, const mi355fft_plan_desc& d, const ConvGeom& g,
   proto.f[F_SCALE] = (float)(1.0 / (double)V);
   proto.imap = conv_load_map(d, g, fs, 3);
   push_per_kernel(b, d, g, proto, LP_MUL_SPECTRUM, G, V * 8);
-  b.ir.route += (real ? "bricks-rconv-ols" : "bricks-conv-ols") + brick + ",L=" + std::to_string(ax[0].L) + "x" + std::to_string(ax[1].L) + "x" + std::to_string(ax[2].L) + (wrap ? ",wrap] " : "] ");
+  b.ir.route += (real ? "bricks-rconv-ols" : "bricks-conv-ols") + brick + ",L=" + std::to_string(ax[0].L) + "x" + std::to_string(ax[1].L) + "x" + std::to_string(ax[2].L) + depthwise_field(g) + (wrap ? ",wrap] " : "] ");
   return true;
 }
 
@@ -2055,13 +2116,13 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
   const int64_t K = g.K, B = g.B, inN = g.inN;
   // fftConv.inputChannels C > 1: B * C data lines and K * C kernels, result (k, b) = sum_c x[b C + c] (*) h[k C + c].  The single-channel routes below are
   // not considered; the request takes emit_tiles_ols's sum form (rank 2, linear) or the composed route with the sum in its pointwise pass (fftconv-sum)
-  const int64_t C = g.C, BC = B * C, KC = K * C;
+  const int64_t C = g.C, BC = B * C, KC = K * g.Cg;      // (fftConv.groups: K Cg kernels, each output kernel summing its group's Cg channels)
   const int64_t *ks = g.ks, *fs = g.fs, zero[8] = {0};
   const bool zpad = d.zero_read.enabled || d.zero_write.enabled;
   // ---- overlap-save: long complex lines, short kernels, one launch per kernel on blocks of P points (kern_lines.hpp fft_lines_conv_ols_kernel has the
   // index map); K P 8 bytes of workspace for any length.  The switch's rule is conv_ols_block
   // Circular requests (PlannerOptions::ols_circular, ols_circular_take) run the kernel's WRAP instances on the rule's block alone
-  if (rank == 1 && C == 1 && b.opt.conv_ols != 0 && b.opt.conv_lines && !b.opt.force_generic && g.lfN < ((int64_t)1 << 31) - 16384) {
+  if (rank == 1 && g.one_channel() && b.opt.conv_ols != 0 && b.opt.conv_lines && !b.opt.force_generic && g.lfN < ((int64_t)1 << 31) - 16384) {
     const int64_t sw = b.opt.conv_ols, rule = conv_ols_block(g.lfN, ks[0]);
     const bool wrap = !g.linear;
     const int64_t P = wrap ? (ols_circular_take(b.opt, d.shape, 1, rule) ? rule : 0) : ols_switch(sw, is_pow2(sw) && sw >= 128 && sw <= 4096, rule);
@@ -2076,14 +2137,14 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
       ols_store(proto.i, ax);
       proto.i[LS_OLS_WRAP] = wrap ? 1 : 0;
       push_per_kernel(b, d, g, proto, LP_MUL_SPECTRUM, G, P * 8);
-      b.ir.route += "lines-conv-ols[N=" + std::to_string(P) + ",L=" + std::to_string(ax.L) + (wrap ? ",wrap] " : "] ");
+      b.ir.route += "lines-conv-ols[N=" + std::to_string(P) + ",L=" + std::to_string(ax.L) + depthwise_field(g) + (wrap ? ",wrap] " : "] ");
       return MI355FFT_OK;
     }
   }
   // ---- overlap-save in two dimensions (emit_tiles_ols); the switch's rule is conv_tiles_block
   if (rank == 2 && b.opt.conv_ols2d != 0 && b.opt.conv_lines && !b.opt.force_generic && b.opt.fuse_views && emit_tiles_ols(b, d, g, false)) return MI355FFT_OK;
   // ---- overlap-save in three dimensions (emit_bricks_ols); the switch's rule is conv_bricks_block
-  if (rank == 3 && C == 1 && b.opt.conv_ols3d != 0 && b.opt.conv_lines && !b.opt.force_generic && b.opt.fuse_views && emit_bricks_ols(b, d, g, false)) return MI355FFT_OK;
+  if (rank == 3 && g.one_channel() && b.opt.conv_ols3d != 0 && b.opt.conv_lines && !b.opt.force_generic && b.opt.fuse_views && emit_bricks_ols(b, d, g, false)) return MI355FFT_OK;
   // Long rank-1 linear modes: the next power of two keeps the transforms off the Bluestein / mixed-radix routes (ConvGeom)
   if (b.opt.conv_pad && rank == 1 && g.linear && g.lfN > 16384 && g.lfN <= ((int64_t)1 << 22) && !is_pow2(g.lfN)) {
     int64_t P = 32768;
@@ -2223,8 +2284,8 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
       if (k == 0) b.ir.route += std::string(fuse_in ? "lines-mul-mapped[N=" : "lines-mul[N=") + std::to_string(fN) + "] ";
     } else {
       Step& pm = b.push(ST_POINTWISE);
-      pm.p[P_SRC] = xf; pm.p[P_DST] = y; pm.p[PWP_KERNEL] = kf.plus(k * C * fN * 8);
-      pm.i[PW_L] = fN; pm.i[PW_TOTAL] = B * fN; pm.i[PW_CONJ] = g.corr ? 1 : 0; pm.i[PW_CHANNELS] = C > 1 ? C : 0; pm.f[F_SCALE] = 1.0f;
+      pm.p[P_SRC] = xf.plus((k / g.Kg) * g.Cg * fN * 8); pm.p[P_DST] = y; pm.p[PWP_KERNEL] = kf.plus(k * g.Cg * fN * 8);     // (the group's first channel: a shift of the data pointer)
+      pm.i[PW_L] = fN; pm.i[PW_TOTAL] = B * fN; pm.i[PW_CONJ] = g.corr ? 1 : 0; pm.i[PW_CHANNELS] = C > 1 ? g.Cg : 0; pm.i[PW_ITEM_LINES] = g.G > 1 ? C : 0; pm.f[F_SCALE] = 1.0f;
       pm.grid = b.generic_grid(B * fN);
     }
     if (fuse_out) {
@@ -2246,7 +2307,7 @@ int build_fftconv(const mi355fft_plan_desc& d, Builder& b, std::string& err) {
     conv_staged_crop(b, d, g, out, y, k, false);
   }
   if (d.zero_write.enabled && !fuse_out) b.ir.route += "zero-write ";
-  b.ir.route += C > 1 ? "fftconv-sum[K=" + std::to_string(K) + ",C=" + std::to_string(C) + "] " : "fftconv[K=" + std::to_string(K) + "] ";
+  b.ir.route += C > 1 ? "fftconv-sum[K=" + std::to_string(K) + ",C=" + std::to_string(C) + (g.G > 1 ? ",G=" + std::to_string(g.G) : std::string()) + "] " : "fftconv[K=" + std::to_string(K) + "] ";
   return MI355FFT_OK;
 }
 
@@ -2288,7 +2349,7 @@ int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err
   // ---- overlap-save: long real lines, short kernels, one launch per kernel on blocks of P points, each running the pipeline of lines-rconv
   // (kern_lines.hpp fft_lines_rconv_ols_kernel has the index map).  The switch's rule, whatever the line's length when a block is forced:
   // Circular requests (PlannerOptions::ols_circular, ols_circular_take) run the kernel's WRAP instances on the rule's block alone
-  if (rank == 1 && C == 1 && b.opt.rconv_fused == 1 && b.opt.rconv_ols != 0 && !(b.opt.force_generic && !linear) && lfN < ((int64_t)1 << 31) - 16384) {
+  if (rank == 1 && g.one_channel() && b.opt.rconv_fused == 1 && b.opt.rconv_ols != 0 && !(b.opt.force_generic && !linear) && lfN < ((int64_t)1 << 31) - 16384) {
     const int64_t M = ks[0], sw = b.opt.rconv_ols;
     const bool wrap = !linear;
     // measured (profiles/fftconv_ols_ab.log, 256 x 2^20 (*) {31, 255, 1024, 4096}, K = 1 and 4, and three longer / shorter lines): every block length
@@ -2313,14 +2374,14 @@ int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err
       ols_store(proto.i, ax);
       proto.i[LS_OLS_WRAP] = wrap ? 1 : 0;
       push_per_kernel(b, d, g, proto, LP_RCONV_SPECTRUM, G, (H + 1) * 8);
-      b.ir.route += "lines-rconv-ols[N=" + std::to_string(P) + ",L=" + std::to_string(ax.L) + (wrap ? ",wrap] " : "] ");
+      b.ir.route += "lines-rconv-ols[N=" + std::to_string(P) + ",L=" + std::to_string(ax.L) + depthwise_field(g) + (wrap ? ",wrap] " : "] ");
       return MI355FFT_OK;
     }
   }
   // ---- overlap-save in two dimensions on real tile pairs (emit_tiles_ols); the switch's rule is rconv_tiles_block
   if (rank == 2 && (linear || b.opt.fuse_views) && b.opt.rconv_ols2d != 0 && b.opt.rconv_fused != 0 && !b.opt.force_generic && emit_tiles_ols(b, d, g, true)) return MI355FFT_OK;
   // ---- overlap-save in three dimensions on real brick pairs (emit_bricks_ols); the switch's rule is rconv_bricks_block
-  if (rank == 3 && C == 1 && (linear || b.opt.fuse_views) && b.opt.rconv_ols3d != 0 && b.opt.rconv_fused != 0 && !b.opt.force_generic && emit_bricks_ols(b, d, g, true)) return MI355FFT_OK;
+  if (rank == 3 && g.one_channel() && (linear || b.opt.fuse_views) && b.opt.rconv_ols3d != 0 && b.opt.rconv_fused != 0 && !b.opt.force_generic && emit_bricks_ols(b, d, g, true)) return MI355FFT_OK;
 
   // ---- route 1: one launch per kernel on the line kernels --------------------------------------------------------------------
   int64_t P1 = 0;
@@ -2412,8 +2473,8 @@ int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err
     if (rank > 1) return b.emit_nd(dst, dst, ps, rank, count, false, 1.0f, err, 1);
     return MI355FFT_OK;
   };
-  const PtrRef kf = b.alloc_work((uint64_t)K * C * pN * 8);
-  if ((rc = forward(kern, kf, ks, K * C, nullptr, conv_kernel_map(g, fs, 1)))) return rc;
+  const PtrRef kf = b.alloc_work((uint64_t)K * g.Cg * pN * 8);
+  if ((rc = forward(kern, kf, ks, K * g.Cg, nullptr, conv_kernel_map(g, fs, 1)))) return rc;
   const PtrRef xf = b.alloc_work((uint64_t)B * C * pN * 8);
   if ((rc = forward(in, xf, d.shape, B * C, d.zero_read.enabled ? &d.zero_read : nullptr, conv_load_map(d, g, fs, 1)))) return rc;
   const PtrRef y = b.alloc_work((uint64_t)B * pN * 8);
@@ -2422,8 +2483,8 @@ int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err
   const float inv_n = (float)(1.0 / (double)fN);
   for (int64_t k = 0; k < K; ++k) {
     Step& pm = b.push(ST_POINTWISE);
-    pm.p[P_SRC] = xf; pm.p[P_DST] = y; pm.p[PWP_KERNEL] = kf.plus(k * C * pN * 8);
-    pm.i[PW_L] = pN; pm.i[PW_TOTAL] = B * pN; pm.i[PW_CONJ] = corr ? 1 : 0; pm.i[PW_CHANNELS] = C > 1 ? C : 0; pm.f[F_SCALE] = 1.0f;
+    pm.p[P_SRC] = xf.plus((k / g.Kg) * g.Cg * pN * 8); pm.p[P_DST] = y; pm.p[PWP_KERNEL] = kf.plus(k * g.Cg * pN * 8);
+    pm.i[PW_L] = pN; pm.i[PW_TOTAL] = B * pN; pm.i[PW_CONJ] = corr ? 1 : 0; pm.i[PW_CHANNELS] = C > 1 ? g.Cg : 0; pm.i[PW_ITEM_LINES] = g.G > 1 ? C : 0; pm.f[F_SCALE] = 1.0f;
     pm.grid = b.generic_grid(B * pN);
     if (rank > 1 && (rc = b.emit_nd(y, y, ps, rank, B, true, 1.0f, err, 1))) return rc;
     const PtrRef dst = direct_out ? out.plus(g.lane_offset(k) * 4) : yr;
@@ -2432,7 +2493,7 @@ int build_fftconv_real(const mi355fft_plan_desc& d, Builder& b, std::string& err
     if (!direct_out) conv_staged_crop(b, d, g, out, yr, k, true);
   }
   if (d.zero_write.enabled) b.ir.route += "zero-write ";
-  b.ir.route += C > 1 ? "rconv-sum[K=" + std::to_string(K) + ",C=" + std::to_string(C) + "] " : "rconv[K=" + std::to_string(K) + "] ";
+  b.ir.route += C > 1 ? "rconv-sum[K=" + std::to_string(K) + ",C=" + std::to_string(C) + (g.G > 1 ? ",G=" + std::to_string(g.G) : std::string()) + "] " : "rconv[K=" + std::to_string(K) + "] ";
   return MI355FFT_OK;
 }
 

@@ -46,10 +46,14 @@ constexpr int tile_kernel_lds_bytes(int P, int R0, int R1) { return (P * (P + 1)
 // one store a tile): a list, ids and units of its own (tiles_conv_ols_sum.hip, tiles_rconv_ols_sum.hip).  P = 64 alone: the accumulators are E more complex
 // registers a thread, which P = 128 on 1024 threads (124 of 128 VGPRs) cannot hold
 #define MI355_TILE_SUM_KERNEL_LIST(X) X(64, 8, 8, 256)
-struct TileKernelMeta { int id, P, R0, R1, threads, lds_bytes; bool real; bool sum; };
+// the grouped forms (fftConv.groups > 1: fft_tiles_conv_ols_group_kernel, every output kernel in ONE launch, a work item carrying its kernel index): X(P, R0, R1,
+// threads, depthwise).  depthwise = 0: Cg = C / G > 1 channels summed per item (GTileCfg / GRTileCfg, the sum form's accumulators); 1: Cg = 1 (DTileCfg /
+// DRTileCfg: the single-channel form, no accumulators).  A list, ids and units of its own (tiles_conv_ols_group.hip, tiles_rconv_ols_group.hip); P = 64 alone
+#define MI355_TILE_GROUP_KERNEL_LIST(X) X(64, 8, 8, 256, 0) X(64, 8, 8, 256, 1)
+struct TileKernelMeta { int id, P, R0, R1, threads, lds_bytes; bool real; bool sum; int group = 0; };   // group: 0 none, 1 the grouped sum form, 2 the grouped depthwise form
 // `real`: the same list as instances of fft_tiles_conv_ols_kernel on an RTileCfg (real fftconv: two real tiles as re / im of a complex one), a unit of their own
 // (tiles_rconv_ols.hip); an id counts positions in the list for both forms, and the step's line mode says which form is launched
-const TileKernelMeta* find_tile_kernel(int P, bool real = false, bool sum = false);
+const TileKernelMeta* find_tile_kernel(int P, bool real = false, bool sum = false, int group = 0);
 // overlap-save brick kernels of rank-3 fftconv (kern_bricks.hpp fft_bricks_conv_ols_kernel): X(P, threads), id = position in the list.  LDS: the P^3 brick
 // at pitches of P + 1 and P (P + 1) elements.  `real`: the same list on an RBrickCfg (bricks_rconv_ols.hip), as with the tiles
 #define MI355_BRICK_KERNEL_LIST(X) X(16, 256)
@@ -180,10 +184,13 @@ enum : unsigned { LINES_CHIRP = 1, LINES_CHIRP_SWAP = 2 };   // multiply by the 
 // ST_LINES
 enum LinesSlot {
   LS_TILES = 0, LS_LINES, LS_IN_S, LS_IN_OUTER, LS_OUT_S, LS_OUT_OUTER,
-  LS_FS_SHIFT = 6, LS_MUL_CONJ = 6, LS_OLS2_FN_PLIM = 6,   // four-step roots: HI[m >> shift]; LM_MUL: multiply by the spectrum's conjugate; the brick modes: axis 2's fN (low 32 bits) and plim
-  LS_FS_LO_MASK = 7, LS_CHIRP_FLAGS = 7, LS_OLS2_NB_L = 7, // ... LO[m & mask]; mapped LM_C2C / LM_MUL of Bluestein: LINES_CHIRP bits; the brick modes: axis 2's nb and L
+  LS_FS_SHIFT = 6, LS_MUL_CONJ = 6, LS_OLS2_FN_PLIM = 6, LS_TILES_LANE_K = 6,   // four-step roots: HI[m >> shift]; LM_MUL: multiply by the spectrum's conjugate; the brick modes: axis 2's fN (low 32 bits) and plim
+  LS_FS_LO_MASK = 7, LS_CHIRP_FLAGS = 7, LS_OLS2_NB_L = 7, LS_TILES_KERNELS = 7, // ... LO[m & mask]; mapped LM_C2C / LM_MUL of Bluestein: LINES_CHIRP bits; the brick modes: axis 2's nb and L
   LS_FS_GROUP = 8, LS_OLS2_W0_PRE = 8, LS_TILES_CHANNELS = 8,   // PASS_B: rows per transform; COL_RAGGED: tiles per group (0 reads as 1); the brick modes: axis 2's w0 and pre;
                                              // LM_TILES_CONV_OLS / LM_TILES_RCONV_OLS: input channels summed per tile (0, 1: none; above: the sum instances, `variant` an id of their list)
+                                             // The grouped tile launch (fftConv.groups > 1, all output kernels in one launch: LS_TILES_KERNELS != 0, `variant` an id of
+                                             // MI355_TILE_GROUP_KERNEL_LIST): LS_TILES_CHANNELS holds Cg (low 32 bits) and C, LS_TILES_KERNELS K (low) and Kg = K / G,
+                                             // LS_TILES_LANE_K the step between the output lanes of consecutive kernels (ConvGeom::lane_k)
   LS_MODE = 9,                               // LineMode
   LS_MAPPED = 10,                            // sides through Step::imap / omap
   LS_H16 = 11,                               // binary16 sides (f16-storage)
@@ -199,6 +206,10 @@ static_assert(LS_LAST < STEP_INTS, "ST_LINES slots");
 static_assert(LS_OLS2_FN_PLIM == LS_FS_SHIFT && LS_OLS2_FN_PLIM < LS_MODE, "axis 2: fN, plim");
 static_assert(LS_OLS2_NB_L == LS_FS_LO_MASK && LS_OLS2_NB_L < LS_MODE, "axis 2: nb, L");
 static_assert(LS_OLS2_W0_PRE == LS_FS_GROUP && LS_OLS2_W0_PRE < LS_MODE && LS_MODE < LS_OLS_FN, "axis 2: w0, pre");
+// the grouped tile launch sits on the same three slots (a tile has no axis 2 and no root tables of four-step)
+static_assert(LS_TILES_CHANNELS == LS_FS_GROUP && LS_TILES_CHANNELS == LS_OLS2_W0_PRE, "grouped tiles: Cg, C");
+static_assert(LS_TILES_KERNELS == LS_FS_LO_MASK && LS_TILES_KERNELS == LS_OLS2_NB_L, "grouped tiles: K, Kg");
+static_assert(LS_TILES_LANE_K == LS_FS_SHIFT && LS_TILES_LANE_K == LS_OLS2_FN_PLIM && LS_TILES_LANE_K < LS_MODE, "grouped tiles: lane_k");
 // The block geometry of one axis of an overlap-save launch, host side (the kernels take it as RconvOls, kern_lines.hpp, or per axis as TileAxis, kern_tiles.hpp,
 // where the index map is): fN logical points cut into nb blocks, block j holding signal indices [j L - pre, j L - pre + P) and giving L results from its
 // window [w0, w0 + L), signal indices kept below plim
@@ -299,7 +310,8 @@ enum PackSlot { PH_N = 0, PH_P, PH_BATCH, PH_PACKED_STRIDE, PH_LAST = PH_PACKED_
 static_assert(PH_LAST < STEP_INTS, "ST_PACK_HALF / ST_UNPACK_HERM slots");
 
 // ST_POINTWISE (p: P_SRC, P_DST, PWP_KERNEL)
-enum PointwiseSlot { PW_L = 0, PW_TOTAL, PW_CONJ, PW_CHANNELS, PW_LAST = PW_CHANNELS };   // PW_CHANNELS C > 1: out[b][i] = sum_c data[b C + c][i] (conj?)kernel[c][i] (pointwise_sum_kernel)
+enum PointwiseSlot { PW_L = 0, PW_TOTAL, PW_CONJ, PW_CHANNELS, PW_ITEM_LINES, PW_LAST = PW_ITEM_LINES };   // PW_CHANNELS C > 1: out[b][i] = sum_c data[b C + c][i] (conj?)kernel[c][i] (pointwise_sum_kernel)
+// PW_ITEM_LINES (fftConv.groups; 0: none): the data lines of an item, of which the PW_CHANNELS of one group are summed, PW_CHANNELS = 1 included (pointwise_group_sum_kernel)
 static_assert(PW_LAST < STEP_INTS, "ST_POINTWISE slots");
 enum PointwisePtr { PWP_KERNEL = 2, PWP_LAST = PWP_KERNEL };
 static_assert(PWP_LAST < STEP_PTRS, "ST_POINTWISE pointers");
@@ -413,6 +425,15 @@ struct PlannerOptions {
                                        // OUTPUT kernel (kern_tiles.hpp on an STileCfg / SRTileCfg); 1: where measured ahead (plan.cpp sum_tiles_block); 0: the composed
                                        // routes fftconv-sum / rconv-sum; 64 or 128: that tile on every request it fits and an instance exists for (tests and measurement).
                                        // conv_ols2d / rconv_ols2d = 0 and the switches in front of them come first
+#ifdef MI355_HOST_EMU
+  int group_ols2d = std::getenv("MI355_EMU_GROUP_OLS2D") ? std::atoi(std::getenv("MI355_EMU_GROUP_OLS2D")) : 1;
+#else
+  int group_ols2d = 1;
+#endif
+                                       // fftconv / real fftconv with fftConv.groups > 1, rank 2, linear boundaries: the grouped tile kernel, every output kernel in one
+                                       // launch (kern_tiles.hpp fft_tiles_conv_ols_group_kernel); 1: where measured ahead (plan.cpp group_tiles_block); 0: never (depthwise
+                                       // requests take the single-channel overlap-save routes through a per-kernel load map, the rest the composed routes); 64: that tile
+                                       // on every request it fits; any other value: never.  conv_ols2d / rconv_ols2d = 0 and the switches in front of them come first
 #ifdef MI355_HOST_EMU
   int conv_ols3d = std::getenv("MI355_EMU_CONV_OLS3D") ? std::atoi(std::getenv("MI355_EMU_CONV_OLS3D")) : 1;
   int rconv_ols3d = std::getenv("MI355_EMU_RCONV_OLS3D") ? std::atoi(std::getenv("MI355_EMU_RCONV_OLS3D")) : 1;

@@ -373,6 +373,12 @@ export function resolvePlanOptions(opts) {
       }
       if (layout && layout.whdcn != null) throw new Error("fftConv.inputChannels > 1 cannot be combined with layout.whdcn");
     }
+    // groups G: output kernel k sums the C / G input channels of group floor(k / (kernelCount / G)); the kernel buffer holds kernelCount * C / G kernels,
+    // kernel (k, c) at k * (C / G) + c; input and output sides are those of G = 1
+    const groups = dflt(fc.groups, 1);
+    if (!Number.isInteger(groups) || groups <= 0) throw new Error("fftConv.groups must be a positive integer; got " + groups);
+    if (inputChannels % groups) throw new Error("fftConv.groups=" + groups + " must divide fftConv.inputChannels=" + inputChannels);
+    if (kernelCount % groups) throw new Error("fftConv.groups=" + groups + " must divide fftConv.kernelCount=" + kernelCount);
     const outputLayout = dflt(fc.outputLayout, "kernel-major");
     assertOneOf(outputLayout, FFTCONV_OUTPUT_LAYOUTS, "fftConv.outputLayout");
     const kernelShape = dflt(fc.kernelShape, shape);
@@ -410,14 +416,15 @@ export function resolvePlanOptions(opts) {
       convOutputLayout: CONV_LAYOUT_CODE[outputLayout], convKernelShape: kernelShape.slice(),
       convOutputKernelStrideElements: explicitKStride || pol.kernelStride || 0,
       convInputChannels: inputChannels > 1 ? inputChannels : 0,      // mi355fft_side_layout.reserved of the input side (include/mi355fft.h)
+      convGroups: groups > 1 ? groups : 0,                           // mi355fft_zero_range.reserved of zero_read
     });
     if (sides.input) desc.input = sides.input;
     if (sides.output) desc.output = sides.output;
-    Object.assign(meta, { mode, boundary, kernelCount, inputChannels, outputLayout, kernelShape: kernelShape.slice(), outputShape,
+    Object.assign(meta, { mode, boundary, kernelCount, inputChannels, groups, outputLayout, kernelShape: kernelShape.slice(), outputShape,
       inputLayout: sides.input, outputLayoutResolved: sides.output, outputKernelStrideElements: desc.convOutputKernelStrideElements });
     if (realConv) {      // element = one f32 on both sides and in the kernel buffer
       desc.type = FFTCONV_REAL_CODE;
-      Object.assign(meta, { real: true, inputBytes: 4 * batch * inputChannels * prod(shape), kernelBytes: 4 * kernelCount * inputChannels * prod(kernelShape),
+      Object.assign(meta, { real: true, inputBytes: 4 * batch * inputChannels * prod(shape), kernelBytes: 4 * kernelCount * (inputChannels / groups) * prod(kernelShape),
         outputBytes: 4 * batch * kernelCount * prod(outputShape) });
     }
     return { desc, meta };

@@ -66,9 +66,10 @@ export class Plan extends NativePlanBase {
   // one copyBufferToBuffer per kernel recorded ahead of the plan's own launches
   _prepareKernel(kernel, commandEncoder) {
     const single = (this.real ? 1 : 2) * prod(this.kernelShape);      // real fftconv plans take real kernels
-    const channels = this.inputChannels || 1;                         // kernel (k, c) is entry k * inputChannels + c
+    const groups = this.groups || 1;
+    const channels = (this.inputChannels || 1) / groups;              // kernel (k, c) is entry k * (inputChannels / groups) + c
     const count = this.kernelCount * channels;
-    const counts = "kernelCount=" + this.kernelCount + (channels > 1 ? " x inputChannels=" + channels : "");
+    const counts = "kernelCount=" + this.kernelCount + (groups > 1 ? " x inputChannels/groups=" + channels : channels > 1 ? " x inputChannels=" + channels : "");
     const packed = single * count;
     let payload = null;
     if (kernel instanceof Float32Array) {

@@ -337,6 +337,7 @@ static napi_value js_plan_create(napi_env env, napi_callback_info info) {
   fill_view(env, o, "ioOutput", &d.io_output);
   fill_range(env, o, "zeroRead", &d.zero_read);
   fill_range(env, o, "zeroWrite", &d.zero_write);
+  d.zero_read.reserved = (int32_t)prop_i64(env, o, "convGroups", 0);      /* fftConv.groups: zero_read's reserved word (mi355fft.h) */
   d.axes_mask = (uint32_t)prop_i64(env, o, "axesMask", 0);
   d.precision = (uint32_t)prop_i64(env, o, "precision", 0);   /* MI355FFT_PRECISION_* */
   mi355fft_plan* p = NULL;

@@ -203,10 +203,11 @@ class Plan:
         conv = self._resolved["conv"]
         kn = int(np.prod(conv.get("kernelShape") or self._resolved["shape"]))
         per = 1 if self._resolved.get("real") else 2      # real fftconv plans take real kernels
-        channels = conv.get("inputChannels", 1)           # kernel (k, c) is entry k * inputChannels + c
+        groups = conv.get("groups", 1)
+        channels = conv.get("inputChannels", 1) // groups  # kernel (k, c) is entry k * (inputChannels / groups) + c
         count = conv["kernelCount"] * channels
         single, packed = per * kn, per * kn * count
-        counts = f"kernelCount={conv['kernelCount']}" + (f" x inputChannels={channels}" if channels > 1 else "")
+        counts = f"kernelCount={conv['kernelCount']}" + (f" x inputChannels/groups={channels}" if groups > 1 else f" x inputChannels={channels}" if channels > 1 else "")
         if isinstance(kernel, (list, tuple)):
             if len(kernel) != count:
                 raise Mi355Error(1, f"kernel array length must equal fftConv.{counts}; got {len(kernel)}")

@@ -144,6 +144,8 @@ def make_desc(type, shape, batch=1, direction="forward", normalize="none", in_pl
         d.conv_output_kernel_stride_elements = int(conv.get("outputKernelStrideElements", 0))
         if int(conv.get("inputChannels", 1)) > 1:       # fftConv.inputChannels rides the input side's reserved word (include/mi355fft.h)
             d.input.reserved = int(conv["inputChannels"])
+        if int(conv.get("groups", 1)) > 1:              # fftConv.groups rides zero_read's reserved word
+            d.zero_read.reserved = int(conv["groups"])
     else:
         d.conv_kernel_count = 1
     if io_view:

@@ -468,6 +468,15 @@ def resolve_plan_options(opts):
                 raise ValueError("fftConv.inputChannels > 1 cannot be combined with fftConv.channelPolicy.input")
             if layout.get("whdcn") is not None:
                 raise ValueError("fftConv.inputChannels > 1 cannot be combined with layout.whdcn")
+        # groups G: output kernel k sums the C / G input channels of group k // (kernelCount / G); the kernel buffer holds kernelCount * C / G kernels,
+        # kernel (k, c) at k * (C / G) + c; input and output sides are those of G = 1
+        groups = fc.get("groups", 1)
+        if not _is_int(groups) or isinstance(groups, bool) or groups <= 0:
+            raise ValueError(f"fftConv.groups must be a positive integer; got {groups}")
+        if in_channels % groups:
+            raise ValueError(f"fftConv.groups={groups} must divide fftConv.inputChannels={in_channels}")
+        if kernel_count % groups:
+            raise ValueError(f"fftConv.groups={groups} must divide fftConv.kernelCount={kernel_count}")
         output_layout = fc.get("outputLayout", "kernel-major")
         _assert_one_of(output_layout, FFTCONV_OUTPUT_LAYOUTS, "fftConv.outputLayout")
         kshape = fc.get("kernelShape") or shape
@@ -498,11 +507,11 @@ def resolve_plan_options(opts):
         out.update({"direction": "forward", "normalize": "none", "input_layout": inp, "output_layout": outl,
                     "conv": {"mode": mode, "boundary": boundary, "kernelCount": kernel_count, "outputLayout": output_layout,
                              "kernelShape": kshape, "outputKernelStrideElements": explicit_kstride or policy_kstride or 0,
-                             "inputChannels": in_channels},
+                             "inputChannels": in_channels, "groups": groups},
                     "outputShape": out_shape})
         if real_conv:      # element = one f32 on both sides and in the kernel buffer
             out.update({"abi_type": "fftconv-real", "real": True, "inputBytes": 4 * batch * in_channels * _prod(shape),
-                        "kernelBytes": 4 * kernel_count * in_channels * _prod(kshape), "outputBytes": 4 * batch * kernel_count * _prod(out_shape)})
+                        "kernelBytes": 4 * kernel_count * (in_channels // groups) * _prod(kshape), "outputBytes": 4 * batch * kernel_count * _prod(out_shape)})
         if in_place:
             raise ValueError("fftconv inPlace=true is not supported in current implementation")
         return out
